@@ -13,6 +13,7 @@ initial cloud so the work per step is constant.
 
 python bench.py --gpus N --steps K --warmup W   (N>1: launched by torch.distributed.run,
 one rank per GPU, RCCL).  Prints ONE JSON line on rank 0.
+--dump-outputs DIR: rank 0 also writes what the last timed step returned as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -42,6 +43,8 @@ X3_PASSES = 3                      # fp16 MFMA passes per f32 product in the spl
                                    # operands cut into two fp16 numbers, W_l x_h + W_h x_l + W_h x_h; the fp16 and bf16
                                    # MFMA peaks are equal
 PEAK_HBM_TBS = 8.0
+DUMP_MAX_BYTES = 64000000          # --dump-outputs: all files together, headers included
+DUMP_ARRAY_BYTES = 16 << 20        # ... one array; a larger one (or one past what is left) keeps a seeded sample of its rows
 
 
 def sphere_cloud(P, seed, device):
@@ -153,6 +156,43 @@ class Cycle(object):
         cyc.run(cyc.project_resample())
         self._count_hook = None
         return counts
+
+
+def cycle_outputs(out):
+    """What one IsoCycle.step() hands its caller, copied to the host (graph replays overwrite the returned buffers):
+    the resampled cloud (points, normals, converged mask), the composited image with its front-most z, and d loss /
+    d NDC of the splat rows that were drawn (each view's first_idx .. + num_points; the rows beyond are capacity)."""
+    r1, img, grad, frags, fr = out
+    R = grad.shape[0]                    # (clamped: an overflowed count is reported by checked(), not indexed here)
+    rows = torch.cat([torch.arange(min(f, R), min(f + n, R), device=grad.device)
+                      for f, n in zip(fr["local_first"].tolist(), fr["own_num"].tolist())])
+    arrays = {"points": r1.points, "normals": r1.normals, "mask": r1.mask.float(), "image": img,
+              "zbuf_front": frags.zbuf[..., 0], "grad_ndc": grad[rows]}
+    return {k: v.detach().float().cpu().contiguous() for k, v in arrays.items()}
+
+
+def dump_outputs(arrays, out_dir):
+    """DIR/<name>.npy, float32, in the order given.  An array above min(DUMP_ARRAY_BYTES, what is left of
+    DUMP_MAX_BYTES) keeps a sample of its rows (all dimensions but the last flattened): randperm with seed 0, sorted --
+    the same rows for the same shapes, so two runs compare element for element.
+    Returns {name: [shape written, [rows kept, rows] or None]}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total, manifest = 0, {}
+    for i, (name, a) in enumerate(arrays.items()):
+        kept = None
+        limit = min(DUMP_ARRAY_BYTES, DUMP_MAX_BYTES - total - 256 * (len(arrays) - i))     # 256: room for each header
+        if a.numel() * 4 > limit:
+            a2 = a.reshape(-1, a.shape[-1]) if a.dim() > 1 else a
+            k = max(limit, 0) // (a2[0].numel() * 4)
+            pick = torch.randperm(a2.shape[0], generator=torch.Generator().manual_seed(0))[:k].sort().values
+            a, kept = a2[pick], [int(k), int(a2.shape[0])]
+        f = os.path.join(out_dir, name + ".npy")
+        np.save(f, a.numpy().astype(np.float32))
+        total += os.path.getsize(f)
+        manifest[name] = [list(a.shape), kept]
+    assert total <= DUMP_MAX_BYTES, "bench.py --dump-outputs: %d bytes written" % total
+    return manifest
 
 
 def measured_traffic(x3):
@@ -517,7 +557,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, 64 MB at most in all)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -559,13 +603,15 @@ def main():
     cyc.timed = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        cyc.step()
+        last = cyc.step()
     torch.cuda.synchronize()
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     cyc.timed = False
+    dumped = cycle_outputs(last) if args.dump_outputs and rank == 0 else None     # untimed; before any further step
+    last = None
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -664,6 +710,9 @@ def main():
             out["operator_api_small"] = operator_api_small(dev, model)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model)
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dump_outputs(dumped, args.dump_outputs),
+                                   "note": "last timed step, rank 0; arrays: [shape, [rows kept, rows] if sampled]"}
         print(json.dumps(out))
     if dist is not None:
         dist.destroy_process_group()

@@ -37,3 +37,31 @@ def test_bench_source_still_emits_the_fields():
         assert re.search(r'"%s"\s*[:\]]' % k, src), k
     for flag in ("--gpus", "--steps", "--warmup"):
         assert flag in src
+
+
+def test_dump_outputs_budget_and_sample(tmp_path):
+    """--dump-outputs: float32 .npy files, 64 MB at most for the headline's shapes, and the sample of an oversized array
+    is the same rows on every run."""
+    import numpy as np
+    import torch
+    import bench
+    g = torch.Generator().manual_seed(1)
+    P, rows = bench.P_TOTAL, 2 * bench.P_TOTAL
+    arrays = {"points": torch.rand(1, P, 3, generator=g), "normals": torch.rand(1, P, 3, generator=g),
+              "mask": torch.ones(1, P), "image": torch.rand(bench.VIEWS, bench.IMAGE, bench.IMAGE, 4, generator=g),
+              "zbuf_front": torch.rand(bench.VIEWS, bench.IMAGE, bench.IMAGE, generator=g),
+              "grad_ndc": torch.arange(rows * 3, dtype=torch.float32).view(rows, 3)}
+    m1 = bench.dump_outputs(arrays, str(tmp_path / "a"))
+    m2 = bench.dump_outputs(arrays, str(tmp_path / "b"))
+    assert m1 == m2 and set(m1) == set(arrays)
+    total = 0
+    for name in arrays:
+        a, b = np.load(str(tmp_path / "a" / (name + ".npy"))), np.load(str(tmp_path / "b" / (name + ".npy")))
+        assert a.dtype == np.float32 and np.array_equal(a, b)
+        total += os.path.getsize(str(tmp_path / "a" / (name + ".npy")))
+    assert total <= bench.DUMP_MAX_BYTES
+    kept, n = m1["grad_ndc"][1]
+    assert n == rows and 0 < kept < rows and m1["points"][1] is None
+    got = np.load(str(tmp_path / "a" / "grad_ndc.npy"))
+    assert got.shape == (kept, 3) and np.all(np.diff(got[:, 0]) > 0)          # whole rows, in order
+    assert np.array_equal(got[:, 1] - got[:, 0], np.ones(kept, dtype=np.float32))
