@@ -109,7 +109,7 @@ int iso_siren_get_gemm_mode(void);
 int iso_siren_set_tail_from(int first_tail_iteration);
 /* Which tile a workgroup of the step kernels takes next: drawn from a per-launch counter (1, the default: the XCDs of one
  * GPU do not run alike under the power cap, equal static shares end with the slowest) or every gridDim-th (0).  -1: back to
- * the environment (ISO_SIREN_DYN_TILES / ISO_IDR_DYN_TILES = 0) or the default.  Results do not depend on it. */
+ * the default.  Results do not depend on it. */
 int iso_siren_set_drawn_tiles(int on);
 int iso_idr_set_drawn_tiles(int on);
 /* step-kernel launches one iso_project_siren call with these arguments issues (max_iters + 1 without the tail) */

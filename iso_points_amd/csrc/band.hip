@@ -27,10 +27,7 @@ namespace {
 
 constexpr int kRec = 13;             // floats per record on the wire
 constexpr int kHdr = 16;             // ints in front of a segment: [0..7] records per view, [8] records wanted (unclipped)
-#ifndef BAND_ROWS_PER_LANE
-#define BAND_ROWS_PER_LANE 2      // (4 / 2 / 1: count + scan + fill of a rank of 8 = 35.6 / 29.4 / 30.9 us -- the scan walks capacity / chunk entries)
-#endif
-constexpr int kRowsPerLane = BAND_ROWS_PER_LANE;
+constexpr int kRowsPerLane = 2;     // (4 / 2 / 1: count + scan + fill of a rank of 8 = 35.6 / 29.4 / 30.9 us -- the scan walks capacity / chunk entries)
 constexpr int kChunkRows = 256 * kRowsPerLane;     // rows per workgroup: 256 lanes x kRowsPerLane consecutive rows
 constexpr int kMaxWorld = 64;
 

@@ -553,22 +553,6 @@ struct BrickStage {
   int qpre[NQRUN + 1];
 };
 
-// -DBK_DBG_PHASES (timing experiment, tools/diag/brick_phases.py): thread 0 of every workgroup adds the shader-clock time
-// between consecutive marks (barrier waits included) to bk_phase[i]; iso_dbg_brick_phases() reads and clears them.
-#ifdef BK_DBG_PHASES
-__device__ unsigned long long bk_phase[16384 * 8];
-__shared__ unsigned long long s_bk_t, s_bk_acc[8];
-#define BK_PH(i) do { if (threadIdx.x == 0) { const unsigned long long t_ = clock64(); \
-  if ((i) >= 0) s_bk_acc[(i) < 0 ? 0 : (i)] += t_ - s_bk_t; \
-  else for (int q_ = 0; q_ < 8; ++q_) s_bk_acc[q_] = 0; \
-  s_bk_t = t_; } } while (0)
-#define BK_PH_FLUSH() do { if (threadIdx.x == 0 && blockIdx.x < 16384) for (int q_ = 0; q_ < 8; ++q_) \
-  bk_phase[blockIdx.x * 8 + q_] += s_bk_acc[q_]; } while (0)
-#else
-#define BK_PH(i) do {} while (0)
-#define BK_PH_FLUSH() do {} while (0)
-#endif
-
 struct BrickGeo { int bx, by, bz, ox, oy, oz; };
 
 // All threads of the workgroup.  Returns the number of staged records, or -1 when they do not fit.
@@ -589,7 +573,6 @@ __device__ int stage_brick(BrickStage<WITH_NRM, SUB, CAP>& S, const BrickHdr& h,
   g.bz = b % nbz; g.by = (b / nbz) % nby; g.bx = b / (nbz * nby);
   g.ox = 4 * g.bx - 1; g.oy = 4 * g.by - 1; g.oz = 4 * g.bz - 1;
   __syncthreads();                                   // the previous brick's readers are done
-  BK_PH(6);
   for (int c = tid; c < NCELL; c += BK_THREADS) S.ccur[c] = 0;
   if (tid < kStageRuns) {
     // (rt: the thread index behind an opaque move -- the run's offsets below depend on the thread only, so the compiler
@@ -619,7 +602,6 @@ __device__ int stage_brick(BrickStage<WITH_NRM, SUB, CAP>& S, const BrickHdr& h,
     if (tid == 0) S.run_pre[0] = 0;
   }
   __syncthreads();
-  BK_PH(0);
   const int total_raw = S.run_pre[kStageRuns];
   auto index_of = [&](int j) {                       // the run r with run_pre[r] <= j < run_pre[r + 1]
     int lo = 0, hi = kStageRuns;
@@ -689,10 +671,8 @@ __device__ int stage_brick(BrickStage<WITH_NRM, SUB, CAP>& S, const BrickHdr& h,
       }
     }
     __syncthreads();
-    BK_PH(1);
     scan_cells();
     __syncthreads();
-    BK_PH(2);
     if (S.cstart[NCELL] > CAP) return -1;
     const float* __restrict__ rec1w = reinterpret_cast<const float*>(rec1) + 3;     // the payload word of a second record
     float uw[BK_RAW];
@@ -736,7 +716,6 @@ __device__ int stage_brick(BrickStage<WITH_NRM, SUB, CAP>& S, const BrickHdr& h,
     if (tid == 0) S.qpre[0] = 0;
   }
   __syncthreads();
-  BK_PH(3);
   return S.cstart[NCELL];
 }
 
@@ -824,11 +803,8 @@ __device__ __forceinline__ void walk_candidates_near_first(const BrickStage<WITH
 }
 
 // SUB = 2: the NW x NW x NW window of half cells whose first cell is (wx, wy, wz) = NW^2 contiguous slot ranges of NW
-// half cells each (NW = 4: the query's own window; NW = 6: the 3 x 3 x 3 fine cells around its cell); same
-// two-candidates-per-trip protocol.
-#ifndef BK_RESAMPLE_FLAT
-#define BK_RESAMPLE_FLAT 1
-#endif
+// half cells each (NW = 6: the 3 x 3 x 3 fine cells around its cell; the query's own 4 x 4 x 4 window takes
+// walk_window_flat); same two-candidates-per-trip protocol.
 template <int NW, bool WITH_NRM, class Body>
 __device__ __forceinline__ void walk_window(const BrickStage<WITH_NRM, 2>& S, int wx, int wy, int wz, Body&& body) {
   constexpr int NL = BrickStage<WITH_NRM, 2>::NL;
@@ -920,18 +896,15 @@ __device__ __forceinline__ bool pair_lt(float d1, int i1, float d2, int i2) {
 // Which brick of the list a workgroup takes.  Workgroup i of a launch runs on XCD i % 8 (tools/probes/simd_map.hip prints
 // it), and each XCD has its own L2: dealt out in list order, the eight neighbours of a brick -- whose records it stages,
 // and whose queries write into the same cache lines of the row-ordered outputs -- sit in eight different L2s.  With
-// BK_XCD_CHUNKS = 8 the list (x-major brick order: consecutive entries are neighbours along z, then y) is cut into eight
+// kXcdChunks = 8 the list (x-major brick order: consecutive entries are neighbours along z, then y) is cut into eight
 // contiguous chunks and XCD k walks chunk k.
-#ifndef BK_XCD_CHUNKS
-#define BK_XCD_CHUNKS 8
-#endif
+constexpr int kXcdChunks = 8;
 __device__ __forceinline__ int bk_xcd_span(int n_list) {
-  return BK_XCD_CHUNKS <= 1 ? n_list : BK_XCD_CHUNKS * ((n_list + BK_XCD_CHUNKS - 1) / BK_XCD_CHUNKS);
+  return kXcdChunks * ((n_list + kXcdChunks - 1) / kXcdChunks);
 }
 __device__ __forceinline__ int bk_xcd_item(int lj, int n_list) {
-  if (BK_XCD_CHUNKS <= 1) return lj;
-  const int chunk = (n_list + BK_XCD_CHUNKS - 1) / BK_XCD_CHUNKS;
-  return (lj % BK_XCD_CHUNKS) * chunk + lj / BK_XCD_CHUNKS;
+  const int chunk = (n_list + kXcdChunks - 1) / kXcdChunks;
+  return (lj % kXcdChunks) * chunk + lj / kXcdChunks;
 }
 
 // ---- fused resample step -------------------------------------------------------------------------
@@ -943,7 +916,6 @@ __global__ __launch_bounds__(BK_THREADS, 4) void k_brick_resample(
     int64_t* __restrict__ idx_out, float* __restrict__ d2_out, int32_t* __restrict__ tail,
     int32_t* __restrict__ counters) {
   __shared__ BrickStage<true, 2> S;
-  BK_PH(-1);
   __shared__ int s_unc[BK_THREADS], s_nunc;
   const BrickHdr h = *hp;
   const int n_list = counters[0];
@@ -955,11 +927,7 @@ __global__ __launch_bounds__(BK_THREADS, 4) void k_brick_resample(
     if (threadIdx.x == 0) s_nunc = 0;                  // (stage_brick starts with a barrier)
     const int C = stage_brick<true, 1, 2>(S, h, off, rec0, rec1, b, g);
     if (C < 0) { brick_to_tail(h, off, rec0, b, tail, counters, 1, 1); continue; }
-#ifdef BK_DBG_NOQUERY          // timing experiment (tools/build_variant.sh): staging only
-    const int nq = 0;
-#else
     const int nq = S.qpre[BrickStage<true, 2>::NQRUN];
-#endif
     // One query, start to finish.  WIDE = false: the 4 x 4 x 4 window of half cells picked by the half of its own half
     // cell the query lies in: two below and one above on the axes where it lies in the lower half, one below and two
     // above otherwise -- every point within (2 - m) half cells is inside, m = the largest distance of the query from
@@ -1008,8 +976,7 @@ __global__ __launch_bounds__(BK_THREADS, 4) void k_brick_resample(
         key[0] = min(key[0], kb);
       };
       if (WIDE) walk_window<6>(S, wx, wy, wz, visit);
-      else if (BK_RESAMPLE_FLAT) walk_window_flat<4>(S, wx, wy, wz, visit);
-      else walk_window<4>(S, wx, wy, wz, visit);
+      else walk_window_flat<4>(S, wx, wy, wz, visit);
       // exact (d2, id) order of the survivors
       float d[ML];
       int id[ML], ps[ML];
@@ -1087,17 +1054,13 @@ __global__ __launch_bounds__(BK_THREADS, 4) void k_brick_resample(
         if (at < BK_THREADS) s_unc[at] = pos; else to_tail(pos);
       }
     }
-    BK_PH(4);
     __syncthreads();
-    BK_PH(5);
     const int n_unc = min(s_nunc, BK_THREADS);
     for (int u = threadIdx.x; u < n_unc; u += BK_THREADS) {
       const int pos = s_unc[u];
       if (!one_query(pos, std::true_type())) to_tail(pos);                   // beyond one fine cell: rings of bricks
     }
-    BK_PH(7);
   }
-  BK_PH_FLUSH();
 }
 
 // ---- rings of bricks around a query (tail kernels: one wave per query) ---------------------------
@@ -1108,9 +1071,8 @@ __global__ __launch_bounds__(BK_THREADS, 4) void k_brick_resample(
 // farther than that from the query are dropped before their records are read (a stray point of the SIREN level
 // set 0.15 off the surface would otherwise scan the whole shell of bricks that reaches the surface anywhere).
 struct WalkGeo { float qx, qy, qz, mnx, mny, mnz, B; };
-#ifndef BK_WALK_ITEMS
-#define BK_WALK_ITEMS 8     // record loads a lane keeps in flight (4 until round 3: a stray query's few thousand records were a
-#endif                      // chain of ~40 batch latencies)
+constexpr int kWalkItems = 8;   // record loads a lane keeps in flight (4 until round 3: a stray query's few thousand records were a
+                                // chain of ~40 batch latencies)
 
 // bk_walk_shell: the bricks at Chebyshev distance rin + 1 .. rho from the query's brick (rin = rho - 1: one ring;
 // rin = -1: the whole cube).  A query that found too little in rings 0 and 1 -- a stray point -- takes all the remaining
@@ -1170,7 +1132,7 @@ __device__ __forceinline__ void bk_walk_shell(int rin, int rho, int qbx, int qby
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
     const int ex = inc - len, total = __shfl(inc, 63);
-    constexpr int NU = BK_WALK_ITEMS;                        // items per lane and trip: their loads overlap
+    constexpr int NU = kWalkItems;                           // items per lane and trip: their loads overlap
     for (int j0 = part * 64 * NU; j0 < total; j0 += nparts * 64 * NU) {
       const float near2 = local();
       const int live = (dm0 <= near2 ? 1 : 0) | (dm1 <= near2 ? 2 : 0);
@@ -1387,22 +1349,16 @@ __device__ __forceinline__ float h_from_list(const float* d /*7 ascending, FLT_M
   return fminf(fmaxf(0.5f * m, 5e-5f), 0.01f);
 }
 
-// (five waves per SIMD: 277 -> 257 us with a persistent grid; six with a workgroup per brick, see BK_H_WGS and h_grid();
+// (five waves per SIMD: 277 -> 257 us with a persistent grid; six with a workgroup per brick, see kHWgs and h_grid();
 // the resample kernel above is bound by its instruction count and gains nothing)
-#ifndef BK_H_CAP
-#define BK_H_CAP BK_CAP
-#endif
-#ifndef BK_H_WGS
-#define BK_H_WGS 6     // workgroups per CU (5 / 6 / 7: 189 / 181 / 196 us with a workgroup per brick)
-#endif
+constexpr int kHWgs = 6;     // workgroups per CU (5 / 6 / 7: 189 / 181 / 196 us with a workgroup per brick)
 template <int NV>
-__global__ __launch_bounds__(BK_THREADS, NV <= 4 ? BK_H_WGS : 4) void k_brick_h(
+__global__ __launch_bounds__(BK_THREADS, NV <= 4 ? kHWgs : 4) void k_brick_h(
     const BrickHdr* __restrict__ hp, const int32_t* __restrict__ off, const int32_t* __restrict__ list,
     const float4* __restrict__ rec0, const float4* __restrict__ rec1, const int32_t* __restrict__ view_total,
     int n_views, float* __restrict__ h_out /*(n_views, n_own)*/, int32_t* __restrict__ tail,
     int32_t* __restrict__ counters) {
-  __shared__ BrickStage<false, 1, BK_H_CAP> S;
-  BK_PH(-1);
+  __shared__ BrickStage<false, 1, BK_CAP> S;
   const BrickHdr h = *hp;
   const int n_list = counters[0];
   bool small_cloud[NV];
@@ -1417,13 +1373,9 @@ __global__ __launch_bounds__(BK_THREADS, NV <= 4 ? BK_H_WGS : 4) void k_brick_h(
     const int b = list[li];
     BrickGeo g;
     constexpr int VS = NV <= 4 ? 8 : 1;                 // staged view masks: one byte per view when they fit a word
-    const int C = stage_brick<false, VS, 1, BK_H_CAP>(S, h, off, rec0, rec1, b, g);
+    const int C = stage_brick<false, VS, 1, BK_CAP>(S, h, off, rec0, rec1, b, g);
     if (C < 0) { brick_to_tail(h, off, rec0, b, tail, counters, 3, 8); continue; }
-#ifdef BK_DBG_NOQUERY
-    const int nq = 0;
-#else
     const int nq = S.qpre[16];
-#endif
     for (int t0 = 0; t0 < nq; t0 += BK_THREADS) {
       const int t = t0 + threadIdx.x;
       float4 q = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -1477,7 +1429,6 @@ __global__ __launch_bounds__(BK_THREADS, NV <= 4 ? BK_H_WGS : 4) void k_brick_h(
           for (int v = 0; v < NV; ++v) all = all && (!((qmask >> (VS * v)) & 1) || cnt[v] >= 7);
           return all;
         });
-      BK_PH(4);
       bool open_ = false;
 #pragma unroll
       for (int v = 0; v < NV; ++v) open_ = open_ || (((qmask >> (VS * v)) & 1) && !small_cloud[v] && cnt[v] < 7);
@@ -1507,7 +1458,6 @@ __global__ __launch_bounds__(BK_THREADS, NV <= 4 ? BK_H_WGS : 4) void k_brick_h(
             d[v][0] = fminf(d[v][0], kb);
           }
         });
-      BK_PH(5);
       if (qmask) {
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
@@ -1527,7 +1477,6 @@ __global__ __launch_bounds__(BK_THREADS, NV <= 4 ? BK_H_WGS : 4) void k_brick_h(
       }
     }
   }
-  BK_PH_FLUSH();
 }
 
 template <int KMAX>
@@ -1573,9 +1522,7 @@ constexpr float kHSat = 0.02f;
 // longest such chain is what the launch takes (120 us in the SIREN cycle however many workgroups share the few thousand
 // entries).  The four waves deal the batches out among themselves and pool their seven smallest distances through LDS at
 // the ring ends.
-#ifndef BK_TAIL_WAVES
-#define BK_TAIL_WAVES 4
-#endif
+constexpr int kHTailWaves = 4;   // waves per workgroup of k_brick_h_tail (eight below kTailWideBelow points)
 // (kTailWaves <= 9: the pooled selection runs in one wave.  Eight waves instead of four: a rank's share of eight 51 -> 40 us,
 // the 1 M-point cycle 72-75 -> 83-86 -- the launcher takes eight for clouds below kTailWideBelow points.)
 constexpr int64_t kTailWideBelow = 300000;
@@ -2004,43 +1951,19 @@ extern "C" int iso_halo_import(void* workspace, int64_t n_max, const float* gath
   return ISO_OK;
 }
 
-static int env_grid(const char* name, int dflt) {
-  const char* e = getenv(name);
-  const int v = e ? atoi(e) : 0;
-  return v > 0 ? v : dflt;
-}
 // Grids of the two fused kernels: a workgroup per brick or two, handed out by the dispatcher as CUs free up.  Bricks differ
 // widely in cost (points per brick, lanes with an open view) and a persistent grid that strides over the list ends with a
 // long tail: measured on the cfg-3a cycle, k_brick_h 241 us at 2048 workgroups, 211 at 3840, 186 at 10240 (flat beyond);
 // k_brick_resample 291 / 287 / 270 us at 1024 / 2048 / >= 4096.  A workgroup past the end of the list reads one counter
-// and leaves.  (ISO_BK_H_GRID / ISO_BK_RESAMPLE_GRID override, tools/sweep_grid.sh)
-static int brick_grid(int forced, int64_t n_own, int cap) {
-  if (forced > 0) return forced;
+// and leaves.
+static int brick_grid(int64_t n_own, int cap) {
   int64_t g = n_own / 48;
   if (g < 1024) g = 1024;
   if (g > cap) g = cap;
   return (int)g;
 }
-static bool resample_m10() { static const int v = env_grid("ISO_BK_RESAMPLE_M10", 1); return v == 1; }   // 2: off (A/B)
-static int h_grid(int64_t n_own) { static const int f = env_grid("ISO_BK_H_GRID", 0); return brick_grid(f, n_own, 10240); }
-static int resample_grid(int64_t n_own) { static const int f = env_grid("ISO_BK_RESAMPLE_GRID", 0); return brick_grid(f, n_own, 8192); }
-
-#ifdef BK_DBG_PHASES
-extern "C" int iso_dbg_brick_phases(double* out16) {
-  static unsigned long long h[16384 * 8];
-  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(bk_phase), sizeof(h)) != hipSuccess) return -1;
-  for (int i = 0; i < 16; ++i) out16[i] = 0.0;
-  for (int w = 0; w < 16384; ++w) {
-    bool any = false;
-    for (int i = 0; i < 8; ++i) { out16[i] += (double)h[w * 8 + i]; any = any || h[w * 8 + i]; }
-    if (any) out16[8] += 1.0;                       // workgroups that did any work
-  }
-  void* dp = nullptr;
-  (void)hipGetSymbolAddress(&dp, HIP_SYMBOL(bk_phase));
-  (void)hipMemset(dp, 0, sizeof(h));
-  return 0;
-}
-#endif
+static int h_grid(int64_t n_own) { return brick_grid(n_own, 10240); }
+static int resample_grid(int64_t n_own) { return brick_grid(n_own, 8192); }
 
 extern "C" int iso_resample_fused(void* workspace, int64_t n_max, const float* points, int64_t n_own,
                                   int k_plus_one, float* points_out, int64_t* idx_out, float* d2_out,
@@ -2059,7 +1982,7 @@ extern "C" int iso_resample_fused(void* workspace, int64_t n_max, const float* p
   // (list length K + 1 is the shortest that can certify: the 10-entry list of the default K = 9 fails the list test for
   // ~0.1 % of the queries -- they take the wide window -- and saves two of twelve insertion steps per candidate)
   if (K <= 5) ISO_RS(8);
-  else if (K == 9 && resample_m10()) ISO_RS(10);
+  else if (K == 9) ISO_RS(10);
   else if (K <= 9) ISO_RS(12);
   else ISO_RS(16);
 #undef ISO_RS
@@ -2103,10 +2026,10 @@ extern "C" int iso_splat_h_fused(void* workspace, int64_t n_max, const float* po
   else ISO_H(8);
 #undef ISO_H
   if (n_own < kTailWideBelow)
-    hipLaunchKernelGGL((k_brick_h_tail<2 * BK_TAIL_WAVES>), dim3(4096), dim3(64 * 2 * BK_TAIL_WAVES), 0, s, w.hdr, w.off, w.rec0, w.rec1, points, mask, view_total,
+    hipLaunchKernelGGL((k_brick_h_tail<2 * kHTailWaves>), dim3(4096), dim3(64 * 2 * kHTailWaves), 0, s, w.hdr, w.off, w.rec0, w.rec1, points, mask, view_total,
                      n_views, h_out, w.tail, w.counters);
   else
-    hipLaunchKernelGGL((k_brick_h_tail<BK_TAIL_WAVES>), dim3(4096), dim3(64 * BK_TAIL_WAVES), 0, s, w.hdr, w.off, w.rec0, w.rec1, points, mask, view_total,
+    hipLaunchKernelGGL((k_brick_h_tail<kHTailWaves>), dim3(4096), dim3(64 * kHTailWaves), 0, s, w.hdr, w.off, w.rec0, w.rec1, points, mask, view_total,
                      n_views, h_out, w.tail, w.counters);
   ISO_CHECK_LAUNCH("iso_splat_h_fused");
   return ISO_OK;

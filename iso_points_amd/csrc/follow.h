@@ -101,9 +101,7 @@ struct FollowState {
   }
   // s_box: one row of 6 floats per wave
   __device__ __forceinline__ void finish(const FollowArgs& a, float (*s_box)[6]) {
-#ifndef FOLLOW_DBG_NOBOX       // (timing experiment, tools/build_variant.sh: results are then wrong by construction)
     box.commit(a.counters, s_box, seen);
-#endif
   }
 };
 #endif  // __HIPCC__

@@ -8,13 +8,13 @@
 //   * k_fps_reg (clouds below 4 k points): one workgroup, points and
 //     min-distances in registers, two barriers and no memory access per sample: 1.3 us per sample at
 //     5 000 points.
-//   * k_fps_grid (clouds of >= 4 k points): a cooperative launch of up to 256 workgroups; every
+//   * k_fps_grid (clouds above 2 M points, up to 4 M): a cooperative launch of 256 workgroups; every
 //     thread keeps its <= 16 points AND their min-distances in registers (nothing is read from
 //     memory inside the loop except the winner's coordinates); the workgroup maxima -- 64-bit keys
 //     (distance bits, ~index) -- meet through one store per workgroup and one polling load per lane of
 //     wave 0 (no atomics, no counter barrier: see the comment at the kernel).  One device-wide exchange
 //     (~2.2 us) per sample: 3.5-3.7 us per sample at 500 k points.
-//   * k_fps_lazy (the default for 4 k .. 2 M points): the same layout, but a workgroup publishes its FOUR
+//   * k_fps_lazy (4 k .. 2 M points): the same layout, but a workgroup publishes its FOUR
 //     largest keys and every workgroup replays the selection on the published lists for as long as its
 //     outcome is certain -- 35 samples per exchange on average at 500 k points: 0.8 us per sample
 //     (5 000 of 500 k: 18.3 -> 4.5 ms), the sequence identical sample for sample.
@@ -212,7 +212,8 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-// ---- one workgroup, points in registers (clouds below 8 k points: the reference's own sizes) --------------------
+// ---- one workgroup, points in registers (clouds below 4 k points: the reference's own sizes; up to 8 k when the device
+// refuses the cooperative launch of the grid-wide forms) -------------------------------------------------------------
 // k_fps walks the cloud in memory every sample (3 us per sample at 5 000 points: five dependent L2 round trips per thread,
 // a serial final reduction).  Here a thread keeps its <= 8 points and their min-distances in registers, the workgroup's
 // maximum is one DPP reduction per wave + sixteen LDS words read by everybody, and the winner's position comes from its owner
@@ -503,22 +504,17 @@ extern "C" int iso_farthest_point_sampling(const float* points, const int64_t* l
               "iso_farthest_point_sampling: null pointer");
   ISO_REQUIRE(p_stride < (1ll << 31), ISO_ERR_UNSUPPORTED, "iso_farthest_point_sampling: cloud too large");
   hipStream_t st = (hipStream_t)stream;
-  static int64_t grid_min = 0;                       // ISO_FPS_GRID_MIN: development override of the size the grid-wide forms start at
-  if (grid_min == 0) { const char* e = getenv("ISO_FPS_GRID_MIN"); grid_min = e ? atoll(e) : kFpsGridMin; if (grid_min < 2048) grid_min = 2048; }
-  if (p_stride >= grid_min && p_stride <= (int64_t)256 * FPS_BLOCK * 16 && !getenv("ISO_FPS_ONE_WORKGROUP")) {
-    // grid-wide form, cloud after cloud; the smallest grid that keeps <= 8 points per thread
-    // (measured: 2.8 us per sample up to 50 k points, 5.0 at 500 k, 7.1 at 1 M -- the barrier's atomic
-    // round trips, not the arithmetic; fewer, fatter workgroups are not faster)
-    static int lazy = -1;                           // ISO_FPS_LAZY=0: one sample per exchange (k_fps_grid)
-    if (lazy < 0) { const char* e = getenv("ISO_FPS_LAZY"); lazy = e ? atoi(e) != 0 : 1; }
-    // points per thread the grid is sized for (ISO_FPS_PPT: development override).  k_fps_grid: 8 (fewer, fatter workgroups
-    // shorten the exchange); k_fps_lazy: 1, i.e. as many workgroups as the cloud fills, up to 128 -- the exchange is shared by
-    // many samples, more lists make longer runs (24 k points: 13.9 ms at 4 points per thread, 10.1 at 1)
-    static int ppt_target = 0;
-    if (ppt_target == 0) { const char* e = getenv("ISO_FPS_PPT"); ppt_target = e ? atoi(e) : (lazy ? 1 : 8); if (ppt_target < 1 || ppt_target > 16) ppt_target = lazy ? 1 : 8; }
-    const bool use_lazy = lazy && p_stride <= (int64_t)kFpsLazyGrid * FPS_BLOCK * 16;
-    const int64_t nb_max = use_lazy ? kFpsLazyGrid : 256;
-    int64_t nb = (p_stride + FPS_BLOCK * ppt_target - 1) / (FPS_BLOCK * ppt_target);
+  // (the tests run the memory-walking kernel as the reference: read on every call)
+  const bool one_workgroup = getenv("ISO_FPS_ONE_WORKGROUP") != nullptr;
+  if (p_stride >= kFpsGridMin && p_stride <= (int64_t)256 * FPS_BLOCK * 16 && !one_workgroup) {
+    // grid-wide form, cloud after cloud: k_fps_lazy with one point per thread, i.e. as many workgroups as the cloud fills,
+    // up to 128 -- the exchange is shared by many samples, more lists make longer runs (24 k points: 13.9 ms at 4 points
+    // per thread, 10.1 at 1); above 128 x 1024 x 16 points k_fps_grid on 256 workgroups.  (k_fps_grid measured 2.8 us per
+    // sample up to 50 k points, 5.0 at 500 k, 7.1 at 1 M -- the barrier's atomic round trips, not the arithmetic; fewer,
+    // fatter workgroups are not faster.)
+    const bool use_lazy = p_stride <= (int64_t)kFpsLazyGrid * FPS_BLOCK * 16;
+    const int64_t nb_max = use_lazy ? kFpsLazyGrid : kFpsMaxGrid;
+    int64_t nb = (p_stride + FPS_BLOCK - 1) / FPS_BLOCK;
     nb = nb < 2 ? 2 : (nb > nb_max ? nb_max : nb);
     const int64_t ppt = (p_stride + nb * FPS_BLOCK - 1) / (nb * FPS_BLOCK);
     // (8-byte slots: the control block starts at the next 8-byte boundary; kFpsCtlFloats leaves room for it)
@@ -536,12 +532,9 @@ extern "C" int iso_farthest_point_sampling(const float* points, const int64_t* l
         else if (ppt <= 4) e = launch_fps_lazy<4>((int)nb, p, lengths, n_samples, start, n, p_stride, cl, out, st);
         else if (ppt <= 8) e = launch_fps_lazy<8>((int)nb, p, lengths, n_samples, start, n, p_stride, cl, out, st);
         else e = launch_fps_lazy<16>((int)nb, p, lengths, n_samples, start, n, p_stride, cl, out, st);
-      } else
-      if (ppt <= 1) e = launch_fps_grid<1>((int)nb, p, lengths, n_samples, start, n, p_stride, ctl, out, st);
-      else if (ppt <= 2) e = launch_fps_grid<2>((int)nb, p, lengths, n_samples, start, n, p_stride, ctl, out, st);
-      else if (ppt <= 4) e = launch_fps_grid<4>((int)nb, p, lengths, n_samples, start, n, p_stride, ctl, out, st);
-      else if (ppt <= 8) e = launch_fps_grid<8>((int)nb, p, lengths, n_samples, start, n, p_stride, ctl, out, st);
-      else e = launch_fps_grid<16>((int)nb, p, lengths, n_samples, start, n, p_stride, ctl, out, st);
+      } else {        // more than 128 x 1024 x 16 = 256 x 1024 x 8 points on 256 workgroups: 9 .. 16 points per thread
+        e = launch_fps_grid<16>((int)nb, p, lengths, n_samples, start, n, p_stride, ctl, out, st);
+      }
       if (e != hipSuccess) {
         (void)hipGetLastError();
         ISO_REQUIRE(n == 0, ISO_ERR_LAUNCH, "iso_farthest_point_sampling: cooperative launch failed: %s",
@@ -553,8 +546,8 @@ extern "C" int iso_farthest_point_sampling(const float* points, const int64_t* l
     if (!refused) { ISO_CHECK_LAUNCH("iso_farthest_point_sampling"); return ISO_OK; }
     // the device cannot co-schedule the grid (first cloud refused): the one-workgroup form below
   }
-  if (p_stride <= (int64_t)FPS_BLOCK * 8 && !getenv("ISO_FPS_ONE_WORKGROUP")) {
-    // the cloud fits one workgroup's registers (ISO_FPS_ONE_WORKGROUP keeps the memory-walking kernel for the tests)
+  if (p_stride <= (int64_t)FPS_BLOCK * 8 && !one_workgroup) {
+    // the cloud fits one workgroup's registers
     const int64_t ppt = (p_stride + FPS_BLOCK - 1) / FPS_BLOCK;
     if (ppt <= 1) hipLaunchKernelGGL(k_fps_reg<1>, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths, n_samples, start, p_stride, out_stride, out_idx);
     else if (ppt <= 2) hipLaunchKernelGGL(k_fps_reg<2>, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths, n_samples, start, p_stride, out_stride, out_idx);

@@ -25,12 +25,6 @@
 #include "iso_newton.h"
 #include "mlp_common.h"
 
-#ifdef ISO_IDR_PLAIN_GEMM          // the shared, non-pipelined pass (A/B timing)
-#define IDR_GEMM gemm_pass
-#else
-#define IDR_GEMM gemm_pass_pipe
-#endif
-
 #include "idr_common.h"
 
 namespace {
@@ -135,11 +129,11 @@ __global__ __launch_bounds__(256, 1) void k_idr_step(IdrArgs a) {
     // ---- forward
     for (int l = 0; l < nL; ++l) {
       if (l == 0) {
-        IDR_GEMM<NT, true>(a.packed + idr_off_fw0(H), a.packed + idr_off_b0(), hL, wbuf, acc, lane, g,
-                            kD0Pad / 16);
+        gemm_pass_pipe<NT, true>(a.packed + idr_off_fw0(H), a.packed + idr_off_b0(), hL, wbuf, acc, lane, g,
+                                 kD0Pad / 16);
       } else {
         const float* base = a.packed + idr_off_layer(H, l);
-        IDR_GEMM<NT, true>(base + H, base, hL, wbuf, acc, lane, g);
+        gemm_pass_pipe<NT, true>(base + H, base, hL, wbuf, acc, lane, g);
       }
       float* st_l = stash + (int64_t)l * NT * 256;
       const bool top = (l == nL - 1);
@@ -187,7 +181,7 @@ __global__ __launch_bounds__(256, 1) void k_idr_step(IdrArgs a) {
     float gx = 0.f, gy = 0.f, gz = 0.f;
     for (int l = nL - 1; l >= 1; --l) {
       const float* base = a.packed + idr_off_layer(H, l);
-      IDR_GEMM<NT, false>(base + H + (int64_t)H * H, nullptr, hL, wbuf, acc, lane, g);
+      gemm_pass_pipe<NT, false>(base + H + (int64_t)H * H, nullptr, hL, wbuf, acc, lane, g);
       const float* st_p = stash + (int64_t)(l - 1) * NT * 256;
       const bool cat = (l == s.skip);
 #pragma unroll
@@ -218,11 +212,7 @@ __global__ __launch_bounds__(256, 1) void k_idr_step(IdrArgs a) {
     //      folded with the encoding Jacobian (rolled over the D0 inputs)
     {
       const float* W0v = a.packed + idr_off_w0v(H) + (int64_t)g * kW0Row * (H / 4);
-#ifdef IDR_DBG_NOL0REV
-      for (int k = 0; k < 1; ++k) {
-#else
       for (int k = 0; k < s.D0; ++k) {
-#endif
         const f32x4* col = reinterpret_cast<const f32x4*>(W0v + (int64_t)k * (H / 4));
         float pk = 0.f;
         for (int e4i = 0; e4i < NT; ++e4i) {
@@ -261,7 +251,7 @@ __global__ __launch_bounds__(256, 1) void k_idr_step(IdrArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Feature-split form (the default; -DISO_IDR_STAGED selects the staged kernel above).
+// Feature-split form (the default; idr_launch keeps the staged kernel above for H = 128 gradients and wide encodings).
 //
 // Same idea as siren_x3.hip, with the f32 matrix cores: a workgroup holds the activations of
 // P = 64 points (NB = 4 point tiles of 16) in LDS in the B-operand layout, act[q][n][lane][4]
@@ -577,7 +567,6 @@ void idr_launch_fs(const IdrArgs& a, int blocks, hipStream_t st) {
 
 template <int NT>
 void idr_launch(const IdrArgs& a, int blocks, hipStream_t st) {
-#ifndef ISO_IDR_STAGED
   // H = 128 leaves only 32 MFMAs per q-chunk and wave: the staged kernel is 7 % faster there
   // (value-only evaluations always take it where it exists: the staged kernel has no forward-only form)
   if ((NT >= 16 || a.fwd_only) && a.s.D0 <= IdrFs<NT>::kEncRows) {
@@ -585,7 +574,6 @@ void idr_launch(const IdrArgs& a, int blocks, hipStream_t st) {
     else idr_launch_fs<NT, false>(a, blocks, st);
     return;
   }
-#endif
   const size_t lds = (size_t)(5 * NT * 256) * sizeof(float);
   static bool attr_done = false;
   if (!attr_done) {
@@ -661,13 +649,12 @@ extern "C" int64_t iso_project_idr_workspace_bytes(int64_t n, int hidden, int n_
 
 struct IdrTrace { const float* dirs; float alpha, bound; };
 
-static int g_idr_dyn_tiles = -1;                 // -1: from ISO_IDR_DYN_TILES (default on), 0 / 1: iso_idr_set_drawn_tiles
-static bool idr_dynamic_tiles_enabled() {        // off: every gridDim-th tile (A/B, tests)
-  if (g_idr_dyn_tiles < 0) { const char* e = getenv("ISO_IDR_DYN_TILES"); g_idr_dyn_tiles = (e && e[0] == '0') ? 0 : 1; }
-  return g_idr_dyn_tiles == 1;
+static int g_idr_dyn_tiles = -1;                 // -1: the default (on), 0 / 1: iso_idr_set_drawn_tiles
+static bool idr_dynamic_tiles_enabled() {        // off: every gridDim-th tile (tests)
+  return g_idr_dyn_tiles != 0;
 }
 extern "C" int iso_idr_set_drawn_tiles(int on) {
-  ISO_REQUIRE(on >= -1 && on <= 1, ISO_ERR_INVALID, "iso_idr_set_drawn_tiles: -1 (environment / default), 0 or 1");
+  ISO_REQUIRE(on >= -1 && on <= 1, ISO_ERR_INVALID, "iso_idr_set_drawn_tiles: -1 (default), 0 or 1");
   g_idr_dyn_tiles = on;
   return ISO_OK;
 }

@@ -66,7 +66,7 @@ __device__ __forceinline__ void posenc(int f, float x0, float x1, float x2, floa
 //   u = exp(-|t|)            two-term log2(e) reduction + v_exp_f32 on [-1/2, 1/2] + exact 2^n
 //   softplus(t) = max(t, 0) + log1p(u),   log1p(u) = ln(w) * u / (w - 1),  w = fl(1 + u)   (Kahan)
 //   sigmoid(t)  = t >= 0 ? 1/w : u/w      reciprocals by v_rcp_f32 + one Newton step
-// every piece is good to 1-2 ulp; -DISO_SOFTPLUS_LIBM restores the libm form.
+// every piece is good to 1-2 ulp.
 __device__ __forceinline__ float iso_rcp_nr(float d) {
   float r = __builtin_amdgcn_rcpf(d);
   return __builtin_fmaf(__builtin_fmaf(-d, r, 1.0f), r, r);
@@ -74,16 +74,6 @@ __device__ __forceinline__ float iso_rcp_nr(float d) {
 
 __device__ __forceinline__ void softplus_b(float z, float beta, float& y, float& dy) {
   // torch.nn.Softplus(beta, threshold=20) and its derivative (sigmoid)
-#ifdef IDR_DBG_NOACT      // timing experiment: results wrong by construction
-  y = z; dy = beta; return;
-#endif
-#ifdef ISO_SOFTPLUS_LIBM
-  const float t = z * beta;
-  if (t > 20.0f) { y = z; dy = 1.0f; return; }
-  const float e = expf(t);
-  y = log1pf(e) / beta;
-  dy = e / (e + 1.0f);
-#else
   const float t = z * beta;
   const float inv_beta = 1.0f / beta;                             // beta is uniform: one division per wave, hoisted
   const float at = __builtin_fabsf(t);
@@ -105,7 +95,6 @@ __device__ __forceinline__ void softplus_b(float z, float beta, float& y, float&
   const bool lin = t > 20.0f;
   y = lin ? z : sp;
   dy = lin ? 1.0f : sg;
-#endif
 }
 
 struct IdrArgs {

@@ -21,13 +21,12 @@
 #include <float.h>
 #include "idr_common.h"
 #include "iso_newton.h"
+#include "mfma_split.h"
+
 // weight fragments requested TWO K-steps ahead here (three in the SIREN kernel): with two output tiles per wave a set is
 // 16 registers, and the fourth set was paid for in spills (124 -> 100 spilled VGPRs; 1 M evaluations 29.1 -> 28.4 ms;
 // one K-step ahead: 27.5-28.5, not steadier)
-#ifndef X3_KAD
-#define X3_KAD 2
-#endif
-#include "mfma_split.h"
+constexpr int kAD = 2;
 
 static_assert(kAP == 2, "idr_x16.hip is written for the two-part fp16 layout");
 
@@ -196,14 +195,6 @@ struct I16Shape {
   static_assert(kLds <= 160 * 1024, "LDS budget");
 };
 
-// -DI16_DBG_TIMES (timing experiment): waves 0 and 4 of workgroup 0 stamp the shader clock at every stage
-// boundary of their second tile into the tail of the stash workspace (tools/idr_stage_times.py).
-#ifdef I16_DBG_TIMES
-#define I16_STAMP() do { if (dbg_on && lane == 0 && dbg_i < 128) dbg[w * 128 + dbg_i] = (long long)__builtin_amdgcn_s_memtime(); ++dbg_i; } while (0)
-#else
-#define I16_STAMP() do {} while (0)
-#endif
-
 template <int H, int NB, bool FWD>
 __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
   using S = I16Shape<H, NB>;
@@ -231,20 +222,14 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
   const float ln2_beta = 0.6931472f / a.beta;
 
   auto fwd_img = [&](int l) {
-#ifdef I16_DBG_ONEIMG      // timing experiment (results wrong): every hidden layer streams the SAME image (L2 resident)
-    if (l > 1) l = 1;
-#endif
     const float* base = a.packed + (l == 0 ? x16i_fw0(H, nL) : x16i_fw(H, nL, l));
     return reinterpret_cast<const u32x4*>(base) + (TW * w * 2) * 64;
   };
   auto rev_img = [&](int l) {
-#ifdef I16_DBG_ONEIMG
-    l = 1;
-#endif
     return reinterpret_cast<const u32x4*>(a.packed + x16i_bw(H, nL, l)) + (TW * w * 2) * 64;
   };
   u32x4 A[4][TW][3];
-  x3_prefetch_a<TW, NTO, 2>(A, fwd_img(0), 0, lane);
+  x3_prefetch_a<kAD, TW, NTO, 2>(A, fwd_img(0), 0, lane);
 
   float bscale[NB], amax[NB];
   auto put_amax = [&](int buf) {
@@ -266,9 +251,6 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
 
   const int64_t count = a.count_in ? (int64_t)(*a.count_in) : a.n;
   const int64_t n_tiles = (count + P - 1) / P;
-#ifdef I16_DBG_TIMES
-  long long* dbg = reinterpret_cast<long long*>(a.stash + (int64_t)gridDim.x * S::kStashPerWg(nL)) - NW * 128;
-#endif
   // (the next tile: every gridDim-th, or drawn from a.tile_ctr by thread 0 at the top of this one and handed over
   // through LDS at the tile's last two barriers)
   __shared__ int s_next_tile;
@@ -276,11 +258,6 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile = next_tile) {
     int drawn = 0;
     if (a.tile_ctr && tid == 0) drawn = (int)gridDim.x + atomicAdd(a.tile_ctr, 1);
-#ifdef I16_DBG_TIMES
-    const bool dbg_on = blockIdx.x == 0 && tile == (int64_t)gridDim.x;
-    int dbg_i = 0;
-#endif
-    I16_STAMP();
     // ---- encoding table: thread (k-row, point) pairs, value and d/dx_c -------------------------
     if (tid < (512 / P) * P) {
       const int pt = tid % P;
@@ -329,7 +306,6 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
     }
     __syncthreads();
 
-    I16_STAMP();
     f32x16 acc[TW][NB];
     float fsum[NB];
 #pragma unroll
@@ -345,16 +321,14 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
       for (int n = 0; n < NB; ++n) zs[n] = wsc * bscale[n];
       const bool top = (l == nL - 1);
       if (l == 0) {
-        gemm_x3<TW, NB, NTO, KS0, kBias, true, 2, 2>(img, bias, act + lane, acc, w, 0, A, fwd_img(1), 0, lane, 1.0f, zs);
+        gemm_x3<kAD, TW, NB, NTO, KS0, kBias, true, 2, 2>(img, bias, act + lane, acc, w, 0, A, fwd_img(1), 0, lane, 1.0f, zs);
       } else if (!top || FWD) {
-        gemm_x3<TW, NB, NTO, NS, kBias, true, 2, 2>(img, bias, act + lane, acc, w, 0, A, top ? fwd_img(0) : fwd_img(l + 1),
-                                                    0, lane, 1.0f, zs);
+        gemm_x3<kAD, TW, NB, NTO, NS, kBias, true, 2, 2>(img, bias, act + lane, acc, w, 0, A, top ? fwd_img(0) : fwd_img(l + 1),
+                                                         0, lane, 1.0f, zs);
       } else {
-        gemm_x3<TW, NB, NTO, NS, kBias, true, 2, 2>(img, bias, act + lane, acc, w, 0, A, rev_img(nL - 1), 0, lane, 1.0f, zs);
+        gemm_x3<kAD, TW, NB, NTO, NS, kBias, true, 2, 2>(img, bias, act + lane, acc, w, 0, A, rev_img(nL - 1), 0, lane, 1.0f, zs);
       }
-      I16_STAMP();
       __syncthreads();                                   // every wave has read the activations
-      I16_STAMP();
       // bound of this layer's output per point -> scale of the next operand
       const bool narrow = (s.skip >= 1 && l == s.skip - 1);
       float nscale[NB], iz[NB];
@@ -408,16 +382,12 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
             u32x4 p0, p1;
             split8_f16(hv, p0, p1, nscale[n]);
             own[(k * kAP + 0) * 64] = p0; own[(k * kAP + 1) * 64] = p1;
-#ifndef I16_NO_GROUP_BARRIER
             __builtin_amdgcn_sched_barrier(0);     // one group at a time: bounds register pressure
-#endif
           }
 #pragma unroll
       for (int n = 0; n < NB; ++n) bscale[n] = nscale[n];
       if (!(top && FWD)) { mbuf ^= 1; put_amax(mbuf); }
-      I16_STAMP();
       __syncthreads();                                   // the next stage's inputs (and maxima) are complete
-      I16_STAMP();
       if (!(top && FWD)) get_max(mbuf, Mp);
     }
     // ---- reverse (the seed W_n * sigma'_top is in LDS) -----------------------------------------
@@ -426,15 +396,13 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
     for (int n = 0; n < NB; ++n) gx[n] = gy[n] = gz[n] = 0.f;
     for (int l = FWD ? 0 : nL - 1; l >= 1; --l) {
       const u32x4* img = rev_img(l);
-      if (l > 1) gemm_x3<TW, NB, NTO, NS, kZero, true, 2, 2>(img, nullptr, act + lane, acc, w, 0, A, rev_img(l - 1), 0, lane);
-      else gemm_x3<TW, NB, NTO, NS, kZero, true, 2, 2>(img, nullptr, act + lane, acc, w, 0, A, fwd_img(0), 0, lane);
+      if (l > 1) gemm_x3<kAD, TW, NB, NTO, NS, kZero, true, 2, 2>(img, nullptr, act + lane, acc, w, 0, A, rev_img(l - 1), 0, lane);
+      else gemm_x3<kAD, TW, NB, NTO, NS, kZero, true, 2, 2>(img, nullptr, act + lane, acc, w, 0, A, fwd_img(0), 0, lane);
       const f32x4* st_p = stash + (int64_t)(l - 1) * NG * 128;
       // sigma' of the layer below: two groups in flight (all NG at once would cost 64 registers)
       f32x4 svq[2][2];
       svq[0][0] = st_p[lane]; svq[0][1] = st_p[64 + lane];
-      I16_STAMP();
       __syncthreads();
-      I16_STAMP();
       const bool cat = (l == s.skip);
       float inv[NB], nscale[NB];
       const float iw = 1.0f / hdr[l];
@@ -492,17 +460,11 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
         mbuf ^= 1;
         put_amax(mbuf);
       }
-      I16_STAMP();
       __syncthreads();
-      I16_STAMP();
       if (l > 1) get_max(mbuf, Mp);
     }
     // ---- layer 0 reverse on the VALU: acc holds a0 = adjoint of z0 for this lane's features -------
-#ifdef I16_DBG_NOL0REV
-    if (false) {
-#else
     if constexpr (!FWD) {
-#endif
       // weight rows of k+1 are requested while row k is multiplied (39 dependent L2 round trips otherwise)
       f32x4 wq[2][TW * 2][2];
       auto ldw = [&](f32x4 (&dst)[TW * 2][2], int k) {
@@ -552,7 +514,6 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
         for (int k = 0; k < s.D0; ++k) { ldw(wq[0], k); row(wq[0], k); }
       }
     }
-    I16_STAMP();
     // ---- reduce over the lane halves and the waves ---------------------------------------------
 #pragma unroll
     for (int n = 0; n < NB; ++n) {

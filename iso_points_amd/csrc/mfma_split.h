@@ -52,9 +52,6 @@ constexpr float kActScale = 4096.0f;             // 2^12
 // f32 from the fp16 half of h in place (the difference is exact) and round it to fp16 into the low / high half of the
 // destination -- bit for bit what the conversion back, the subtraction and the second conversion gave (three half-rate
 // instructions per value before; tools/probes/mix_split.hip: no mismatch in 2^20 values), 16 instead of 24 instructions per cut.
-#ifndef X3_MIX_SPLIT
-#define X3_MIX_SPLIT 1
-#endif
 __device__ __forceinline__ unsigned x3_low_half_pair(float x0, float x1, unsigned h) {
   unsigned l;
   asm("v_fma_mixlo_f16 %0, 1.0, %1, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l) : "v"(x0), "v"(h));
@@ -67,7 +64,6 @@ __device__ __forceinline__ void split8_f16(const float (&v)[8], u32x4& hi, u32x4
   const f32x2 sc = {scale, scale};
   ISO_X4(x[p] = ((f32x2){v[2 * p], v[2 * p + 1]}) * sc);
   ISO_X4(h[p] = __builtin_convertvector(x[p], f16x2));
-#if X3_MIX_SPLIT
   unsigned l[4];
   ISO_X4(asm("v_fma_mixlo_f16 %0, 1.0, %1, -%2 op_sel:[0,0,0] op_sel_hi:[0,0,1]" : "=v"(l[p]) : "v"(x[p].x), "v"(__builtin_bit_cast(unsigned, h[p]))));
   ISO_X4(asm("v_fma_mixhi_f16 %0, 1.0, %1, -%2 op_sel:[0,0,1] op_sel_hi:[0,0,1]" : "+v"(l[p]) : "v"(x[p].y), "v"(__builtin_bit_cast(unsigned, h[p]))));
@@ -76,22 +72,8 @@ __device__ __forceinline__ void split8_f16(const float (&v)[8], u32x4& hi, u32x4
     hi[d] = __builtin_bit_cast(unsigned, h[d]);
     lo[d] = l[d];
   }
-#else
-  f32x2 f[4];
-  f16x2 l[4];
-  ISO_X4(f[p] = __builtin_convertvector(h[p], f32x2));
-  ISO_X4(x[p] = x[p] - f[p]);
-  ISO_X4(l[p] = __builtin_convertvector(x[p], f16x2));
-#pragma unroll
-  for (int d = 0; d < 4; ++d) {
-    hi[d] = __builtin_bit_cast(unsigned, h[d]);
-    lo[d] = __builtin_bit_cast(unsigned, l[d]);
-  }
-#endif
 }
 
-// Timing experiments only (tools/build_variant.sh): -DX3_DBG_NOSINCOS / NOMMA / NOSTASH knock out
-// one ingredient each; results are then wrong by construction.
 __device__ __forceinline__ f32x4 as_f32x4(const u32x4& v) { return __builtin_bit_cast(f32x4, v); }
 __device__ __forceinline__ u32x4 as_u32x4(const f32x4& v) { return __builtin_bit_cast(u32x4, v); }
 
@@ -99,15 +81,11 @@ __device__ __forceinline__ u32x4 as_u32x4(const f32x4& v) { return __builtin_bit
 // acc[t][n] (32 features x 32 points each) += W[tiles of this wave] . act, K-steps 0..NS-1.
 // imgw = image + (TW*w*3)*64 + lane ;  actl = act + lane ;  bias_h = bias_k (K-order, wave-uniform)
 
-// Weight-fragment pipeline: 4 register sets, requested kAD = 3 K-steps ahead (an L2 hit under
-// load takes longer than one K-step of MFMAs).  The fragments of the first kAD K-steps are
-// expected in A[0..kAD-1] on entry (requested by the previous stage, so no L2 latency is exposed
-// after a barrier); on exit A[0..kAD-1] hold the first fragments of the next GEMM stage (image
+// Weight-fragment pipeline: 4 register sets, requested KAD K-steps ahead (KAD < 4; an L2 hit under
+// load takes longer than one K-step of MFMAs; each kernel file states its own value).  The fragments of the first KAD
+// K-steps are expected in A[0..KAD-1] on entry (requested by the previous stage, so no L2 latency is exposed
+// after a barrier); on exit A[0..KAD-1] hold the first fragments of the next GEMM stage (image
 // next_imgw, K-steps next_s..).  Activation fragments (LDS) run one K-step ahead.
-#ifndef X3_KAD
-#define X3_KAD 3
-#endif
-constexpr int kAD = X3_KAD;
 
 // imgw is WAVE-UNIFORM (no lane term): the loads take the scalar-base + 32-bit lane-offset form,
 // so no 64-bit per-lane address registers are needed.
@@ -130,10 +108,10 @@ __device__ __forceinline__ void x3_load_a(u32x4 (&Ar)[TW][3], IP imgw, int s, un
   }
 }
 
-template <int TW, int NTO, int PARTS, class IP>
+template <int KAD, int TW, int NTO, int PARTS, class IP>
 __device__ __forceinline__ void x3_prefetch_a(u32x4 (&A)[4][TW][3], IP imgw, int s, unsigned lane) {
 #pragma unroll
-  for (int d = 0; d < kAD; ++d) x3_load_a<TW, NTO, PARTS>(A[d], imgw, s + d, lane);
+  for (int d = 0; d < KAD; ++d) x3_load_a<TW, NTO, PARTS>(A[d], imgw, s + d, lane);
 }
 
 enum { kAccumulate = 0, kZero = 1, kBias = 2 };
@@ -155,10 +133,12 @@ __device__ __forceinline__ void x3_keep_alive(const u32x4 (&X)[N][3]) {
 // bias_scale multiplies the bias (the accumulator scale of a split-fp16 stage; 1 otherwise).
 struct x3_no_hook { __device__ __forceinline__ void operator()() const {} };
 
-// `hook` runs once, in front of the first request for the NEXT stage's fragments (K-step KS - kAD): memory requests
-// return in order per wave, so a request for data that is far away (the derivative stash) belongs behind the last
-// fragment this stage still waits for and in front of those nobody needs before the next stage.
-template <int TW, int NB, int NTO, int KS, int INIT, bool IL, int PARTS = 2, int NEXT_PARTS = 2, class IP = const u32x4*,
+// `hook` runs once, in front of the first request for the NEXT stage's fragments (K-step KS - KAD): memory requests
+// return in order per wave, so a request for data that is far away belongs behind the last fragment this stage still
+// waits for and in front of those nobody needs before the next stage.  No caller passes one today (the derivative stash
+// of the SIREN step was measured there and is loaded after the GEMM); the parameter stays because removing it changes
+// the machine code of k_idr_step_x16.
+template <int KAD, int TW, int NB, int NTO, int KS, int INIT, bool IL, int PARTS = 2, int NEXT_PARTS = 2, class IP = const u32x4*,
           class Hook = x3_no_hook>
 __device__ __forceinline__ void gemm_x3(IP imgw, const float* __restrict__ bias_h,
                                         const u32x4* actl, f32x16 (&acc)[TW][NB], int w, int s0,
@@ -204,15 +184,6 @@ __device__ __forceinline__ void gemm_x3(IP imgw, const float* __restrict__ bias_
       for (int c = 0; c < PARTS; ++c) Br[n][c] = p[(n * kAP + c) * 64];
   };
   auto mma = [&](const u32x4 (&Ar)[TW][3], const u32x4 (&Br)[NB][3]) {
-#ifdef X3_DBG_NOMMA
-#pragma unroll
-    for (int t = 0; t < TW; ++t)
-#pragma unroll
-      for (int n = 0; n < NB; ++n)
-#pragma unroll
-        for (int c = 0; c < 2; ++c) acc[t][n][c] += __builtin_bit_cast(f32x4, Ar[t][c]).x * __builtin_bit_cast(f32x4, Br[n][c]).y;
-    return;
-#endif
     static_assert(PARTS == 2, "two fp16 parts per operand");
     // W_l x_h + W_h x_l + W_h x_h
     constexpr int QA[3] = {1, 0, 0};
@@ -228,63 +199,36 @@ __device__ __forceinline__ void gemm_x3(IP imgw, const float* __restrict__ bias_
                                                              acc[t][n], 0, 0, 0);
   };
   ldB(B[0], s0);
-#ifndef X3_GEMM_PRIO
-#define X3_GEMM_PRIO 0
-#endif
-#ifndef X3_STATIC_PRIO
-  __builtin_amdgcn_s_setprio(X3_GEMM_PRIO);
-#endif
-#ifdef X3_KROLLED
-#pragma unroll 1
-#endif
+  __builtin_amdgcn_s_setprio(0);
   for (int i = 0; i < KS; i += 4) {
 #pragma unroll
     for (int jj = 0; jj < 4; ++jj) {
       const int k = i + jj;                       // K-step of this stage being multiplied
       // set (jj+3)%4 was consumed one K-step ago: refill it with K-step k+3 (or the next stage's)
-      if (k + kAD < KS) x3_load_a<TW, NTO, PARTS>(A[(jj + kAD) & 3], imgw, s0 + k + kAD, lane);
+      if (k + KAD < KS) x3_load_a<TW, NTO, PARTS>(A[(jj + KAD) & 3], imgw, s0 + k + KAD, lane);
       else {
-        if (k + kAD == KS) hook();
-        x3_load_a<TW, NTO, NEXT_PARTS>(A[(jj + kAD) & 3], next_imgw, next_s + (k + kAD - KS), lane);
+        if (k + KAD == KS) hook();
+        x3_load_a<TW, NTO, NEXT_PARTS>(A[(jj + KAD) & 3], next_imgw, next_s + (k + KAD - KS), lane);
       }
       if (k + 1 < KS) ldB(B[(jj + 1) & 1], s0 + k + 1);
-#ifndef X3_INTERLEAVE_LOADS
-#define X3_INTERLEAVE_LOADS 1
-#endif
-      if constexpr (IL && X3_INTERLEAVE_LOADS) {
+      if constexpr (IL) {
       // the operand requests for the coming K-steps ride in the shadow of this K-step's MFMAs (one
-      // memory instruction behind each of the first MFMAs) instead of draining the matrix pipe
-      // between K-steps
+      // memory instruction behind each of the first MFMAs: the LDS reads, then the global loads) instead of
+      // draining the matrix pipe between K-steps
       mma(A[jj], B[jj & 1]);
-#ifndef X3_IL_DS
-#define X3_IL_DS 1
-#endif
-#ifndef X3_IL_VM
-#define X3_IL_VM 1
-#endif
-#if X3_IL_DS
 #pragma unroll
       for (int g = 0; g < NB * PARTS; ++g) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
-#endif
-#if X3_IL_VM
 #pragma unroll
       for (int g = 0; g < TW * (PARTS > NEXT_PARTS ? PARTS : NEXT_PARTS) && g < TW * NB * 3 - NB * PARTS; ++g) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
       }
-#endif
       __builtin_amdgcn_sched_barrier(0);
-#ifndef X3_NO_KEEPALIVE
       x3_keep_alive<TW, PARTS>(A[jj]);
       x3_keep_alive<NB, PARTS>(B[jj & 1]);
-#endif
-#ifdef X3_IL_GUARD_NOP      // experiment: wait states between the end of a K-step and the first MFMA of the next
-      asm volatile("s_nop %0" ::"n"(X3_IL_GUARD_NOP));
-      __builtin_amdgcn_sched_barrier(0);
-#endif
       } else {
       __builtin_amdgcn_sched_barrier(0);
       mma(A[jj], B[jj & 1]);
@@ -293,9 +237,7 @@ __device__ __forceinline__ void gemm_x3(IP imgw, const float* __restrict__ bias_
     }
   }
   // the next stage starts again at set 0: with KS % 4 == 0 the rotation is already aligned
-#ifndef X3_STATIC_PRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
 }
 
 }  // namespace

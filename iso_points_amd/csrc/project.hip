@@ -199,7 +199,7 @@ extern "C" int iso_project_sphere_follow(const float* pts_in, float* pts_out, fl
   constexpr int BLOCK = 256;
   SphereSdf sdf{cx, cy, cz, radius};
   // (one round of resident workgroups, each looping over its tiles: the box is committed once per workgroup)
-  static const int cap = []() { const char* e = getenv("ISO_FOLLOW_GRID"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 2048; }();
+  constexpr int cap = 2048;
   int follow_grid = iso_stream_grid(n, BLOCK);
   if (follow_grid > cap) follow_grid = cap;
 #define ISO_PSF(NV)                                                                                                    \

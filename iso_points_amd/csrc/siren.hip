@@ -96,13 +96,8 @@ __global__ void k_siren_pack(const float* __restrict__ raw, float* __restrict__ 
 }
 
 // ---- the step kernel -------------------------------------------------------
-#ifdef ISO_SIREN_DIRECT
-#define ISO_GEMM_FWD(img, bias) gemm_pass_direct<NT, true>(img, bias, hL, acc, lane, g)
-#define ISO_GEMM_BWD(img) gemm_pass_direct<NT, false>(img, nullptr, hL, acc, lane, g)
-#else
 #define ISO_GEMM_FWD(img, bias) gemm_pass<NT, true>(img, bias, hL, wbuf, acc, lane, g)
 #define ISO_GEMM_BWD(img) gemm_pass<NT, false>(img, nullptr, hL, wbuf, acc, lane, g)
-#endif
 
 template <int NT>
 __global__ __launch_bounds__(256, 2) void k_siren_step(SirenArgs a) {
@@ -350,43 +345,26 @@ extern "C" int64_t iso_project_siren_counts_offset(int64_t n, int hidden, int n_
   return stash_floats_any(hidden, n_hidden) * 4 + 2 * n * 4 + tail_ints(n) * 4;
 }
 
-static bool siren_small_tiles_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("ISO_SIREN_SMALL_TILES"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
-}
-
-static int g_siren_dyn_tiles = -1;              // -1: from ISO_SIREN_DYN_TILES (default on), 0 / 1: iso_siren_set_drawn_tiles
-static bool siren_dynamic_tiles_enabled() {     // off: static tile assignment (A/B, tests)
-  if (g_siren_dyn_tiles < 0) { const char* e = getenv("ISO_SIREN_DYN_TILES"); g_siren_dyn_tiles = (e && e[0] == '0') ? 0 : 1; }
-  return g_siren_dyn_tiles == 1;
+static int g_siren_dyn_tiles = -1;              // -1: the default (on), 0 / 1: iso_siren_set_drawn_tiles
+static bool siren_dynamic_tiles_enabled() {     // off: static tile assignment (tests)
+  return g_siren_dyn_tiles != 0;
 }
 extern "C" int iso_siren_set_drawn_tiles(int on) {
-  ISO_REQUIRE(on >= -1 && on <= 1, ISO_ERR_INVALID, "iso_siren_set_drawn_tiles: -1 (environment / default), 0 or 1");
+  ISO_REQUIRE(on >= -1 && on <= 1, ISO_ERR_INVALID, "iso_siren_set_drawn_tiles: -1 (default), 0 or 1");
   g_siren_dyn_tiles = on;
   return ISO_OK;
 }
 
-static bool siren_merged_shapes_enabled() {      // ISO_SIREN_MERGED=0: the two tile shapes as two launches (A/B)
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("ISO_SIREN_MERGED"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
-}
-
 // One evaluation of a list whose length only the device knows: for the H = 256 gradient kernels the list is cut at
-// siren_split_point into a 96-point-tile launch and a 32-point-tile launch (per-point results do not depend on the
-// tile shape); everything else is one launch.
+// siren_split_point into 96-point and 32-point tiles, both served by one launch of k_siren_step_x3_both (per-point
+// results do not depend on the tile shape); everything else is one launch of one shape.
 static int run_step_split(SirenArgs a, int hidden, int64_t n, hipStream_t s) {
-  const bool split = hidden == 256 && !a.fwd_only && use_x3(hidden, a.L) && siren_small_tiles_enabled();
-  if (split && siren_merged_shapes_enabled()) {
-    a.small_tiles = 0; a.split = 3;
+  if (hidden == 256 && !a.fwd_only && use_x3(hidden, a.L)) {
+    a.split = 3;
     return run_step(a, hidden, n, s);
   }
-  a.small_tiles = 0; a.split = split ? 1 : 0;
+  a.split = 0;
   a.tile_ctr = nullptr;                      // (the counters are per launch of k_siren_step_x3_both)
-  int rc = run_step(a, hidden, n, s);
-  if (rc != 0 || !split) return rc;
-  a.small_tiles = 1; a.split = 2;
   return run_step(a, hidden, n, s);
 }
 
@@ -394,18 +372,17 @@ static int run_step_split(SirenArgs a, int hidden, int64_t n, hipStream_t s) {
 // the list launch it-1 left (device-side counts, no host read), the last one does not move.
 // From which iteration on the Newton projection runs as ONE tail launch (k_siren_tail_x3): the lists of the first
 // iterations are long (launch-per-iteration, 96-point tiles), the late ones a few hundred points or none.  T >= 6: after
-// four launches; shorter projections (the T = 3 re-projection of resample): after two.  ISO_SIREN_TAIL_FROM overrides
-// (0: never, the launch-per-iteration form).
-static int g_tail_from = -2;       // -1: default policy, 0: never, k > 0: from iteration k
+// four launches; shorter projections (the T = 3 re-projection of resample): after two.  iso_siren_set_tail_from
+// overrides (0: never, the launch-per-iteration form).
+static int g_tail_from = -1;       // -1: default policy, 0: never, k > 0: from iteration k
 static int siren_tail_from(int max_iters) {
-  if (g_tail_from == -2) { const char* e = getenv("ISO_SIREN_TAIL_FROM"); g_tail_from = e ? atoi(e) : -1; }
   if (g_tail_from == 0) return max_iters + 1;
   if (g_tail_from > 0) return g_tail_from;
   return max_iters >= 6 ? 4 : 2;
 }
 extern "C" int iso_siren_step_launches(int hidden, int n_hidden, int max_iters) {
   if (max_iters < 0) return 0;
-  const bool can_tail = hidden == 256 && use_x3(hidden, n_hidden) && siren_small_tiles_enabled();
+  const bool can_tail = hidden == 256 && use_x3(hidden, n_hidden);
   const int from = can_tail ? siren_tail_from(max_iters) : max_iters + 1;
   return from <= max_iters && from > 0 ? from + 1 : max_iters + 1;
 }
@@ -433,7 +410,7 @@ static int run_iterations(SirenArgs a, int hidden, int64_t n, int max_iters, voi
   const int blocks = siren_x3_tail_blocks();
   const int64_t cap = tail_cap_of(n);
   int32_t* tail_counts = tail + (int64_t)blocks * 2 * cap;
-  const bool can_tail = hidden == 256 && !a.dirs && !a.fwd_only && use_x3(hidden, a.L) && siren_small_tiles_enabled();
+  const bool can_tail = hidden == 256 && !a.dirs && !a.fwd_only && use_x3(hidden, a.L);
   const int tail_from = can_tail ? siren_tail_from(max_iters) : max_iters + 1;
   int32_t* tile_ctr = counts + 64;          // [launch][2]: drawn from by the workgroups of k_siren_step_x3_both (zeroed with the counts)
   hipLaunchKernelGGL(k_zero_tail, dim3((2 * blocks + 255) / 256), dim3(256), 0, s, counts, 64 + kTileCtrInts, tail_counts,

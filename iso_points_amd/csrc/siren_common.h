@@ -28,11 +28,11 @@ struct SirenArgs {
   // twice, as the 96-point-tile kernel for long lists and as the 32-point-tile kernel for short ones
   // (a short list costs one tile time per launch whatever its length: 54 us against 25 us)
   int64_t cnt_lo = -1, cnt_hi = INT64_MAX;
-  int small_tiles = 0;
-  // split != 0 (H = 256 step kernels): the list is served by TWO launches, 96-point tiles for the slots
-  // [0, siren_split_point(count)) (split = 1) and 32-point tiles for the rest (split = 2), so that the last, partly
-  // filled round of the persistent grid costs a 32-point tile time instead of a 96-point one
-  int split = 0;             // 3: both in one launch (k_siren_step_x3_both)
+  int small_tiles = 0;       // (no longer read: kept for the layout)
+  // split != 0 (H = 256 step kernels): 96-point tiles for the slots [0, siren_split_point(count)) (split = 1) and 32-point
+  // tiles for the rest (split = 2), so that the last, partly filled round of the persistent grid costs a 32-point tile time
+  // instead of a 96-point one
+  int split = 0;             // 3: both in one launch (k_siren_step_x3_both, which runs 1 and 2 itself)
   int big_blocks = 0;        // split = 3: workgroups of the 96-point-tile shape (set by the launcher)
   // Newton tail (k_siren_tail_x3): ONE launch runs iterations it_first .. it_last; a workgroup keeps the survivors of
   // its own tiles in a private pair of lists and iterates them alone -- no launch, no grid-wide step per iteration
@@ -44,7 +44,7 @@ struct SirenArgs {
   // assignment.  A workgroup draws its next tile from them (x3_step_body) instead of taking every nblk-th.
   int32_t* tile_ctr = nullptr;
   int draw_first = 0;        // 1: the first tile of a workgroup comes from the counter too (no tile is anyone's by index)
-  int ps_guard = 0;          // 1: this launch follows one of k_siren_step_ps on the same list and only works where that one declines
+  int ps_guard = 0;          // always 0 here; kept for the layout and for x3_step_body's machine code (siren_ps_takes)
 };
 
 // Slots served by the 96-point-tile launch of a split list.  A round of the persistent grid is 256 tiles: 24 576
@@ -104,8 +104,10 @@ void siren_x3_pack(const float* raw, float* packed, int H, int L, hipStream_t s)
 int siren_x3_launch(const SirenArgs& a, int H, int64_t n_upper, hipStream_t s);
 int siren_x3_tail_blocks();                                          // workgroups of the Newton-tail launch
 int siren_x3_launch_tail(const SirenArgs& a, int H, hipStream_t s);  // H = 256 only
-// ---- siren_ps.hip: the point-stationary form of the H = 256 step (bit-identical results) -------
-// Which lists it serves (decided on the device by both kernels from the same data, so exactly one of them works): at
+// ---- the point-stationary form of the H = 256 step (tools/experiments/siren_ps, not part of this library) -------
+// x3_step_body keeps its ps_guard check on this predicate (never true here: ps_guard is 0), because removing the check
+// changes that kernel's machine code.  Which lists the experiment served (decided on the device by both kernels from the
+// same data, so exactly one of them works): at
 // least kPsMinList points -- a list is dealt out in tiles of 128 points over 256 workgroups, the last round is partly
 // filled -- and hidden layers whose sine arguments provably stay below the large-argument threshold of iso_sin_wcos8
 // (|w z| < 1e4: the kernel has no such path for them; true for every trained SIREN, r_l w ~ 10..100).
@@ -116,6 +118,4 @@ __host__ __device__ inline bool siren_ps_takes(int64_t count, int L, const float
   for (int l = 0; l < L; ++l) r = hdr[17 + l] > r ? hdr[17 + l] : r;
   return (wh * r) * 1.01f < 1.0e4f;
 }
-bool siren_ps_supported(int H, int L);
-int siren_ps_launch(const SirenArgs& a, int64_t n_upper, hipStream_t s);
 

@@ -41,22 +41,14 @@
 
 #include "mfma_split.h"
 
-#ifdef ISO_WITH_SIREN_PS      // tools/experiments/siren_ps: the point-stationary step, not part of the product library
-static bool siren_ps_enabled();
-#else
-static inline bool siren_ps_enabled() { return false; }
-#endif
+// weight fragments requested three K-steps ahead (gemm_x3): an L2 hit under load takes longer than one K-step of MFMAs
+constexpr int kAD = 3;
 
 namespace {
 
 // s = sin(w_in * z), c = w * cos(w_in * z); w_in = w / (accumulator scale), an exact power-of-two quotient
 __device__ __forceinline__ void x3_sin_wcos8(float w_in, float w, const float (&z)[8], float (&s)[8], float (&c)[8]) {
-#ifdef X3_DBG_NOSINCOS
-#pragma unroll
-  for (int e = 0; e < 8; ++e) { s[e] = w_in * z[e]; c[e] = w; }
-#else
   iso_sin_wcos8(w_in, w, z, s, c);
-#endif
 }
 
 
@@ -148,59 +140,6 @@ __global__ void k_siren_wscale(const float* __restrict__ raw, float* __restrict_
   }
 }
 
-// Bounds of the sine arguments for k_siren_step_ps (siren_ps_takes, siren_common.h; header slots 17..23); one workgroup per
-// hidden layer.  Only launched when that kernel is enabled.
-__global__ void k_siren_ps_bounds(const float* __restrict__ raw, float* __restrict__ packed, int H, int L) {
-  __shared__ float s_m[256];
-  const int l = blockIdx.x;
-  const int64_t HH = (int64_t)H * H;
-  const float* Wl = raw + (int64_t)H * 4 + (int64_t)l * (HH + H);
-  // r_l = max_f (sum_k |W_l[f][k]| + |b_l[f]|): |W_l h + b_l| <= r_l for |h| <= 1 -- with it a kernel knows that no argument
-  // of a hidden sine can reach the large-argument path (siren_ps_takes, siren_common.h); layers 0..4 have a slot
-  if (l < 5) {
-    float rs = 0.f;
-    for (int f = threadIdx.x; f < H; f += 256) {
-      float t = fabsf(Wl[HH + f]);
-#pragma unroll 16
-      for (int k = 0; k < H; ++k) t += fabsf(Wl[(int64_t)f * H + k]);
-      rs = (t == t && t > rs) ? t : (t == t ? rs : 3.0e38f);
-    }
-    s_m[threadIdx.x] = rs;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) s_m[threadIdx.x] = fmaxf(s_m[threadIdx.x], s_m[threadIdx.x + o]);
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) packed[x16_base(H, L) + 17 + l] = s_m[0];
-  }
-  if (l == 0) {
-    // layer 0: |W_0 x + b_0| <= (max_f sum_c |W_0[f][c]|) max|x_c| + max_f |b_0[f]|
-    __syncthreads();
-    float a0 = 0.f, b0m = 0.f;
-    for (int f = threadIdx.x; f < H; f += 256) {
-      const float t = (fabsf(raw[f * 3]) + fabsf(raw[f * 3 + 1])) + fabsf(raw[f * 3 + 2]);
-      const float b = fabsf(raw[(int64_t)H * 3 + f]);
-      a0 = (t == t) ? fmaxf(a0, t) : 3.0e38f;
-      b0m = (b == b) ? fmaxf(b0m, b) : 3.0e38f;
-    }
-    s_m[threadIdx.x] = a0;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) s_m[threadIdx.x] = fmaxf(s_m[threadIdx.x], s_m[threadIdx.x + o]);
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) packed[x16_base(H, L) + 22] = s_m[0];
-    __syncthreads();
-    s_m[threadIdx.x] = b0m;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) s_m[threadIdx.x] = fmaxf(s_m[threadIdx.x], s_m[threadIdx.x + o]);
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) packed[x16_base(H, L) + 23] = s_m[0];
-  }
-}
-
 __global__ void k_siren_pack_f16(const float* __restrict__ raw, float* __restrict__ packed, int H, int L) {
   const int64_t HH = (int64_t)H * H;
   const int NTO = H / 32;
@@ -230,15 +169,6 @@ __global__ void k_siren_pack_f16(const float* __restrict__ raw, float* __restric
 }
 
 // ---- the step kernel -------------------------------------------------------------------------
-#ifndef X3_LDS_STASH
-#define X3_LDS_STASH 1
-#endif
-#ifndef X3_TILE_PIPE
-#define X3_TILE_PIPE 1     // the tile boundary without its two load chains and its closing barrier (k_siren_step_x3)
-#endif
-#ifndef X3_LDS_SLOT
-#define X3_LDS_SLOT 0      // which stash slot keeps its first LG groups in LDS (0: the longest-lived one)
-#endif
 template <int H, int NW, int NB>
 struct X3Shape {
   static constexpr int NS = H / 16;        // K-steps of a hidden layer
@@ -254,25 +184,13 @@ struct X3Shape {
   // hidden layer 0, read back last of all by reverse stage 1 -- the longest-lived slot) stay in the CU; 2 KiB per
   // group and wave, as many groups as the 160 KiB of a gfx950 CU leave room for
   static constexpr int kLdsGroupsFit = (int)((163840 - (kActBytes + kRedBytes + kPtsBytes)) / ((size_t)NW * 2048));
-  static constexpr int LG = X3_LDS_STASH ? (kLdsGroupsFit < NG ? kLdsGroupsFit : NG) : 0;
+  static constexpr int LG = kLdsGroupsFit < NG ? kLdsGroupsFit : NG;
   static constexpr size_t kLds = kActBytes + kRedBytes + kPtsBytes + (size_t)NW * LG * 2048;
   // slot l of the global stash = w cos(w z) of hidden layer l's output (layer 0's is recomputed, the top layer's is
   // consumed on the spot): L - 1 slots in use, one kept for L = 1
   static constexpr int64_t kStashPerWg(int L) { return (int64_t)NW * (L > 1 ? L : 1) * NG * 512; }  // floats
   static_assert(NTO % NW == 0 && TW >= 1, "features must split evenly over the waves");
 };
-
-// -DX3_DBG_TIMES (timing experiment): waves of workgroup 0 stamp the shader clock at every stage
-// boundary of their second tile into the tail of the stash workspace (tools/siren_stage_times.py).
-#ifdef X3_DBG_TIMES
-#define X3_STAMP()                                                                         \
-  do {                                                                                     \
-    if (dbg_on && lane == 0) dbg[w * 128 + (dbg_i)] = (long long)__builtin_amdgcn_s_memtime(); \
-    ++dbg_i;                                                                               \
-  } while (0)
-#else
-#define X3_STAMP() do {} while (0)
-#endif
 
 // FWD: value only (iso_siren_sdf, sphere tracing) -- no stash, no reverse sweep, no w cos(w z)
 // bid / nblk: this workgroup's index among the nblk workgroups that share the list (the kernels below)
@@ -298,11 +216,7 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
   // be scheduled between the MFMAs (tools/siren_stress.py: every repeat differs; the same source
   // with one workgroup per CU, and the 8-wave H = 256 build over 60 chaotic-weight repeats, are
   // bit-stable).  Cause not found yet, so that shape keeps the loads in front of the MFMA block.
-#ifdef X3_FORCE_IL
-  constexpr bool IL = true;
-#else
   constexpr bool IL = (NW == 8);
-#endif
   const int L = a.L;
   const float* X = a.packed + x3_base(H, L);
   // wave-uniform bases (SGPRs) + small per-lane offsets: no 64-bit per-lane pointers are kept live
@@ -332,25 +246,21 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
       if (h == 0) redm[(buf * P + 32 * n + j) * NW + w] = m;
     }
   };
-#ifdef X3_STATIC_PRIO      // experiment (MI355X guide, "static priority for the younger half"): waves NW/2.. at a fixed higher priority
-  if (w >= NW / 2) __builtin_amdgcn_s_setprio(X3_STATIC_PRIO);
-#endif
   u32x4 A[4][TW][3];                     // weight-fragment pipeline, carried across stages
-  x3_prefetch_a<TW, NTO, FP>(A, fwd_img(0), 0, lane);
+  x3_prefetch_a<kAD, TW, NTO, FP>(A, fwd_img(0), 0, lane);
 
   // (agent-scope load: in the Newton tail the count was written by this workgroup's own atomics a moment ago)
   const int64_t total = a.count_in ? (int64_t)__hip_atomic_load(a.count_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : a.n;
   if (total <= a.cnt_lo || total > a.cnt_hi) return;       // the other tile shape serves this list (uniform)
-  if (a.ps_guard && H == 256 && siren_ps_takes(total, L, a.packed + x16_base(H, L), a.wh)) return;   // k_siren_step_ps has done it
+  // ps_guard is always 0 in this library (it served an experimental point-stationary kernel, tools/experiments/siren_ps);
+  // the check stays because removing it changes this kernel's machine code
+  if (a.ps_guard && H == 256 && siren_ps_takes(total, L, a.packed + x16_base(H, L), a.wh)) return;
   // this launch's share of the list: slots [slot0, count)  (SirenArgs::split)
   const int64_t cut = a.split ? siren_split_point(total) : total;
   const int64_t slot0 = a.split == 2 ? cut : 0;
   const int64_t count = a.split == 1 ? cut : total;
   const int64_t n_tiles = (count - slot0 + P - 1) / P;
-#ifdef X3_DBG_TIMES
-  long long* dbg = reinterpret_cast<long long*>(a.stash + (int64_t)nblk * S::kStashPerWg(L)) - NW * 128;
-#endif
-  // Tile boundary (X3_TILE_PIPE).  A tile used to end with two chains of dependent loads during which the whole CU
+  // Tile boundary.  A tile used to end with two chains of dependent loads during which the whole CU
   // idled: the epilogue (list entry -> position -> returning atomic of the survivor list; 4.6 k cycles, one and a
   // half waves busy, the others parked at a closing barrier) and then the next tile's points (list entry -> position,
   // 2.3 k).  Now the next tile's list entries are requested during reverse stage 0 and its positions before the
@@ -382,46 +292,32 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
     }
   };
   int64_t first_tile = bid;
-  if (!FWD && X3_TILE_PIPE && a.tile_ctr != nullptr && a.draw_first) {       // (uniform) the first tile is drawn as well
+  if (!FWD && a.tile_ctr != nullptr && a.draw_first) {       // (uniform) the first tile is drawn as well
     if (tid == 0) s_first_tile = atomicAdd(a.tile_ctr, 1);
     __syncthreads();
     first_tile = s_first_tile;
   }
-  if constexpr (X3_TILE_PIPE) { fetch_idx(first_tile); fetch_pts(); }
+  fetch_idx(first_tile);
+  fetch_pts();
   // Which tile comes next.  Static: bid + k nblk -- every CU takes the same number of tiles, and the launch ends with the
-  // slowest XCD (under the power cap the eight XCDs of one MI355X ran this kernel 6.8 % apart, tools/diag/x3_end_times.py).
+  // slowest XCD (under the power cap the eight XCDs of one MI355X ran this kernel 6.8 % apart, measured with per-workgroup clock stamps).
   // Dynamic (a.tile_ctr, reverse kernels): thread 0 draws the next tile from a counter (zero when the launch starts) while
   // stage 0's GEMM runs and hands it to the workgroup through LDS at the barrier that ends that GEMM.  A point's result
   // does not depend on the tile it sits in or on the workgroup that takes the tile.
-  const bool dyn = !FWD && X3_TILE_PIPE && a.tile_ctr != nullptr;
+  const bool dyn = !FWD && a.tile_ctr != nullptr;
   const int draw_base = a.draw_first ? 0 : nblk;
   int64_t next_tile = 0;
   for (int64_t tile = first_tile; tile < n_tiles; tile = next_tile) {
-#ifdef X3_DBG_TIMES
-    const bool dbg_on = bid == 0 && tile == (int64_t)nblk;
-    int dbg_i = 0;
-#endif
-    X3_STAMP();
     float px[NB], py[NB], pz[NB];
     int j_e = j;
     asm volatile("" : "+v"(j_e));
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
-      if constexpr (X3_TILE_PIPE) {
-        px[n] = npx[n]; py[n] = npy[n]; pz[n] = npz[n];
-      } else {
-        const int64_t slot = slot0 + tile * P + 32 * n + j_e;
-        px[n] = py[n] = pz[n] = 0.f;
-        if (slot < count) {
-          const int64_t idx = a.idx_in ? (int64_t)a.idx_in[slot] : slot;
-          px[n] = a.pts[idx * 3]; py[n] = a.pts[idx * 3 + 1]; pz[n] = a.pts[idx * 3 + 2];
-        }
-      }
+      px[n] = npx[n]; py[n] = npy[n]; pz[n] = npz[n];
       if constexpr (!FWD) {                // kept for the reverse sweep's layer 0 (visible after the barrier below)
         if (w == 0 && h == 0) ptl[32 * n + j_e] = (f32x4){px[n], py[n], pz[n], 0.f};
       }
     }
-    X3_STAMP();
     // ---- layer 0 (3 -> H) on the VALU: this wave's H/NW features of all P points ------------
     for (int sl = 0; sl < SL; ++sl) {
       f32x4 wv[8];
@@ -443,9 +339,7 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
         (void)sv;
       }
     }
-    X3_STAMP();
     __syncthreads();
-    X3_STAMP();
 
     f32x16 acc[TW][NB];
     float fpart[NB];
@@ -459,18 +353,16 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
       const float w_in = a.wh / zscale;              // exact: zscale is a power of two
       if (l + 1 < L || FWD) {
         // the next stage is a forward one again (layer l+1, or layer 0 of the next tile)
-        gemm_x3<TW, NB, NTO, NS, kBias, IL, FP, FP>(img, lay, act + lane, acc, w, 0, A,
-                                                    l + 1 < L ? fwd_img(l + 1) : fwd_img(0), 0, lane, zscale);
+        gemm_x3<kAD, TW, NB, NTO, NS, kBias, IL, FP, FP>(img, lay, act + lane, acc, w, 0, A,
+                                                         l + 1 < L ? fwd_img(l + 1) : fwd_img(0), 0, lane, zscale);
       } else {
-        gemm_x3<TW, NB, NTO, NS, kBias, IL, FP, BP>(img, lay, act + lane, acc, w, 0, A, rev_img(L - 1), 0, lane,
-                                                    zscale);
+        gemm_x3<kAD, TW, NB, NTO, NS, kBias, IL, FP, BP>(img, lay, act + lane, acc, w, 0, A, rev_img(L - 1), 0, lane,
+                                                         zscale);
       }
-      X3_STAMP();
       __syncthreads();                      // both teams have read this team's K-half
-      X3_STAMP();
       const bool top = (l == L - 1);
       f32x4* st_l = stash + (int64_t)l * NG * 128;
-      const bool lds_slot = (l == X3_LDS_SLOT);        // the first LG groups of this slot stay in LDS
+      const bool lds_slot = (l == 0);        // the first LG groups of slot 0 (the longest-lived one) stay in LDS
       // one 8-value group: sin / w cos, head or stash, split, store as the next layer's B entry
       // scale of the adjoint seed (uniform): |W_head[f] * w cos| <= max|W_head| * w
       const float seed_scale = x3_scale_for(a.packed[x16_base(H, L) + 16] * a.wh * 1.01f);
@@ -500,7 +392,6 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
           own[(k * kAP + 0) * 64] = p0; own[(k * kAP + 1) * 64] = p1;
           return;
         } else {
-#ifndef X3_DBG_NOSTASH
           if constexpr (!FWD) {
             if (k < LG && lds_slot) {
               lst[(k * 2 + 0) * 64] = (f32x4){sv[0], sv[1], sv[2], sv[3]};
@@ -510,22 +401,12 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
               st_l[(k * 2 + 1) * 64 + lane] = (f32x4){sv[4], sv[5], sv[6], sv[7]};
             }
           }
-#endif
         }
         u32x4 p0, p1;                           // input of the next forward layer
         split8_f16(hv, p0, p1);
         own[(k * kAP + 0) * 64] = p0; own[(k * kAP + 1) * 64] = p1;
       };
-#ifndef X3_DIRECT_ACT
-#define X3_DIRECT_ACT 1
-#endif
-#ifndef X3_EARLY_STASH
-#define X3_EARLY_STASH 0
-#endif
-#ifndef X3_DIRECT_NG
-#define X3_DIRECT_NG 8
-#endif
-      if constexpr (NG <= X3_DIRECT_NG && X3_DIRECT_ACT) {
+      if constexpr (NG <= 8) {
         // few enough values per lane to walk the accumulators with static indices
 #pragma unroll
         for (int t = 0; t < TW; ++t)
@@ -570,9 +451,7 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
         }
       }
       if constexpr (!FWD) { if (top) put_amax(0); }
-      X3_STAMP();
       __syncthreads();                      // the next layer's inputs are complete
-      X3_STAMP();
     }
     // ---- hidden layers, reverse --------------------------------------------------------------
     float gx[NB], gy[NB], gz[NB];
@@ -597,32 +476,18 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
       auto ld_stash = [&]() {
 #pragma unroll
         for (int k = 0; k < NG; ++k) {
-#ifdef X3_DBG_NOSTASH
-          sv[k][0] = sv[k][1] = (f32x4){1.f, 1.f, 1.f, (float)l};
-#else
-          if (k < LG && l == X3_LDS_SLOT + 1) {
+          if (k < LG && l == 1) {
             sv[k][0] = lst[(k * 2) * 64]; sv[k][1] = lst[(k * 2 + 1) * 64];
           } else {
             sv[k][0] = st_l[(k * 2) * 64 + lane]; sv[k][1] = st_l[(k * 2 + 1) * 64 + lane];
           }
-#endif
         }
       };
       float Mp[NB];
       get_amax(Mp);
-      // w cos(w z) of the layer below: requested before the GEMM when the registers allow it
-      // X3_EARLY_STASH 1: before the GEMM; 2: inside it, behind the stage's last own fragment request (gemm_x3's hook)
-      if constexpr (NG <= 6 && X3_EARLY_STASH == 1) ld_stash();
-      if constexpr (NG <= 6 && X3_EARLY_STASH == 2) {
-        gemm_x3<TW, NB, NTO, NS, kZero, IL, BP, BP>(img, nullptr, act + lane, acc, w, 0, A, rev_img(l - 1), 0, lane, 1.0f,
-                                                    nullptr, ld_stash);
-      } else {
-        gemm_x3<TW, NB, NTO, NS, kZero, IL, BP, BP>(img, nullptr, act + lane, acc, w, 0, A, rev_img(l - 1), 0, lane);
-      }
-      if constexpr (NG > 6 || !X3_EARLY_STASH) ld_stash();
-      X3_STAMP();
+      gemm_x3<kAD, TW, NB, NTO, NS, kZero, IL, BP, BP>(img, nullptr, act + lane, acc, w, 0, A, rev_img(l - 1), 0, lane);
+      ld_stash();                             // w cos(w z) of the layer below
       __syncthreads();
-      X3_STAMP();
       // split-fp16 reverse: the accumulators hold 2^s_l * bscale[p] * (W_l^T a_l); the scale comes out
       // exactly, the next adjoint gets the scale its bound allows
       float inv[NB], nscale[NB];
@@ -659,22 +524,18 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
       for (int n = 0; n < NB; ++n) bscale[n] = nscale[n];
       put_amax(mbuf ^ 1);
       mbuf ^= 1;
-      X3_STAMP();
       __syncthreads();
-      X3_STAMP();
     }
     // stage 0: d sdf / d x = W_0^T [ (W_1^T a_1) * w0 cos(w0 z_0) ] -- z_0 = W_0 x + b_0 is formed again from the point
     // (three FMAs; the same expression on the same operands as in the forward sweep) instead of being stashed
     if constexpr (!FWD) {
       int drawn = 0;
       if (dyn && tid == 0) drawn = draw_base + atomicAdd(a.tile_ctr, 1);
-      gemm_x3<TW, NB, NTO, NS, kZero, IL, BP, FP>(rev_img(0), nullptr, act + lane, acc, w, 0, A, fwd_img(0), 0, lane);
+      gemm_x3<kAD, TW, NB, NTO, NS, kZero, IL, BP, FP>(rev_img(0), nullptr, act + lane, acc, w, 0, A, fwd_img(0), 0, lane);
       if (dyn && tid == 0) s_next_tile = drawn;
-      X3_STAMP();
       __syncthreads();
-      X3_STAMP();
       next_tile = dyn ? (int64_t)s_next_tile : tile + nblk;
-      if constexpr (X3_TILE_PIPE) fetch_idx(next_tile);
+      fetch_idx(next_tile);
       float inv[NB];
       {
         const float iw = 1.0f / a.packed[x16_base(H, L)];
@@ -696,12 +557,7 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
             float zz[8], cv[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) zz[e] = ((wv[e].x * q[n].x + wv[e].y * q[n].y) + wv[e].z * q[n].z) + wv[e].w;
-#ifdef X3_DBG_NOSTASH
-#pragma unroll
-            for (int e = 0; e < 8; ++e) cv[e] = zz[e];
-#else
             iso_wcos8(a.w0, a.w0, zz, cv);
-#endif
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
               const float av = (acc[t][n][8 * p + e] * inv[n]) * cv[e];
@@ -712,14 +568,11 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
             __builtin_amdgcn_sched_barrier(0);     // one group at a time: bounds register pressure
           }
         }
-      X3_STAMP();
-      // (no barrier here with X3_TILE_PIPE: between the one that ends this stage's GEMM and the one after the
+      // (no barrier here: between the one that ends this stage's GEMM and the one after the
       // reduction nothing reads what the reduction writes)
-      if constexpr (!X3_TILE_PIPE) __syncthreads();
-      X3_STAMP();
     } else {
       next_tile = tile + nblk;
-      if constexpr (X3_TILE_PIPE) fetch_idx(next_tile);
+      fetch_idx(next_tile);
     }
     // ---- reduce head + gradient over the lane halves and the waves -----------------------------
 #pragma unroll
@@ -735,9 +588,9 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
     // spilled, across the whole tile)
     int tid_e = tid, lane_e = lane;
     asm volatile("" : "+v"(tid_e), "+v"(lane_e));
-    int eidx = -1;                              // X3_TILE_PIPE: the epilogue's list entry and position, requested
+    int eidx = -1;                              // the epilogue's list entry and position, requested
     f32x4 qe = {0.f, 0.f, 0.f, 0.f};            // before the barrier (the position while `ptl` still holds this tile)
-    if constexpr (X3_TILE_PIPE) {
+    {
       const int64_t slot = slot0 + tile * P + tid_e;
       if (tid_e < P && slot < count) {
         eidx = a.idx_in ? a.idx_in[slot] : (int)slot;
@@ -745,9 +598,7 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
       }
       fetch_pts();
     }
-    X3_STAMP();
     __syncthreads();
-    X3_STAMP();
     // ---- epilogue: thread tid handles point `tid` of the tile ----------------------------------
     bool survive = false;
     int64_t idx = -1;
@@ -761,14 +612,9 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
           r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
         }
         const float f = r.x + bL;
-        if constexpr (X3_TILE_PIPE) {
-          idx = eidx;
-          if constexpr (!FWD) survive = iso_step_finish<SirenArgs, true>(a, idx, f, r.y, r.z, r.w, qe.x, qe.y, qe.z);
-          else survive = iso_step_finish(a, idx, f, r.y, r.z, r.w);
-        } else {
-          idx = a.idx_in ? (int64_t)a.idx_in[slot] : slot;
-          survive = iso_step_finish(a, idx, f, r.y, r.z, r.w);
-        }
+        idx = eidx;
+        if constexpr (!FWD) survive = iso_step_finish<SirenArgs, true>(a, idx, f, r.y, r.z, r.w, qe.x, qe.y, qe.z);
+        else survive = iso_step_finish(a, idx, f, r.y, r.z, r.w);
       }
     }
     if (!a.eval_only && a.do_move) {
@@ -784,33 +630,12 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
         }
       }
     }
-    X3_STAMP();
-    if constexpr (!X3_TILE_PIPE) __syncthreads();
-    X3_STAMP();
   }
 }
 
-// -DX3_DBG_END (timing experiment, tools/diag/x3_end_times.py): thread 0 of every workgroup of k_siren_step_x3 leaves the
-// constant-rate clock at its start and end and the XCD it ran on
-#ifdef X3_DBG_END
-__device__ unsigned long long x3_end[2048 * 3];
-extern "C" int iso_dbg_x3_end(unsigned long long* out, int n_blocks) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(x3_end), sizeof(unsigned long long) * 3 * n_blocks) == hipSuccess ? 0 : -1;
-}
-#endif
 template <int H, int NW, int NB, int MINB, bool FWD>
 __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3(SirenArgs a) {
-#ifdef X3_DBG_END
-  const unsigned long long t0 = wall_clock64();
-#endif
   x3_step_body<H, NW, NB, FWD>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
-#ifdef X3_DBG_END
-  if (threadIdx.x == 0 && blockIdx.x < 2048) {
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    x3_end[blockIdx.x * 3] = t0; x3_end[blockIdx.x * 3 + 1] = wall_clock64(); x3_end[blockIdx.x * 3 + 2] = xcc;
-  }
-#endif
 }
 
 // Both tile shapes of a split list (SirenArgs::split) in ONE launch: workgroups [0, big_blocks) serve the slots below
@@ -818,20 +643,8 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3(SirenArgs a) {
 // behind the first group's).  The dispatcher places workgroups in index order, one per CU, so the small tiles start
 // on the CUs that finish their large ones first; a launch that finds nothing to do for one of the shapes costs nothing
 // (issued separately, the idle one of the two launches took ~4.4 us, 15 times per headline cycle).
-#ifndef X3_BIG_TAKES_SMALL
-#define X3_BIG_TAKES_SMALL 1
-#endif
 template <int H, int NW, int NB, int MINB>
 __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(SirenArgs a) {
-#ifdef X3_DBG_END
-  const unsigned long long t0 = wall_clock64();
-  struct EndStamp { unsigned long long t0; __device__ ~EndStamp() {
-    if (threadIdx.x == 0 && blockIdx.x < 2048) {
-      unsigned xcc;
-      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-      x3_end[blockIdx.x * 3] = t0; x3_end[blockIdx.x * 3 + 1] = wall_clock64(); x3_end[blockIdx.x * 3 + 2] = xcc;
-    } } } stamp{t0};
-#endif
   const bool big = (int)blockIdx.x < a.big_blocks;
   const int small_blocks = (int)gridDim.x - a.big_blocks;
   if (big) {
@@ -844,12 +657,12 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(SirenArgs 
   // within one tile time (68 us) of each other, and the small tiles are what the early ones fill that time with
   // (headline cycle 13.33-13.38 -> 13.22-13.25 ms; with half a round to one and a half rounds of the large tiles' points
   // handed to the small ones on top: 13.26-13.28).
-  if (!big || (X3_BIG_TAKES_SMALL && a.tile_ctr != nullptr)) {
+  if (!big || a.tile_ctr != nullptr) {
     if (big) __syncthreads();              // (the last large tile's epilogue reads LDS the other shape lays out differently)
     SirenArgs b = a;
     b.split = 2;
     if (a.tile_ctr) b.tile_ctr = a.tile_ctr + 1;
-    const bool joint = X3_BIG_TAKES_SMALL && a.tile_ctr != nullptr;
+    const bool joint = a.tile_ctr != nullptr;
     b.draw_first = joint ? 1 : 0;          // (a workgroup that joins late must not own a tile nobody else may take)
     const int bid = big ? small_blocks + (int)blockIdx.x : (int)blockIdx.x - a.big_blocks;
     const int nblk = joint ? small_blocks + a.big_blocks : small_blocks;
@@ -908,11 +721,7 @@ int launch_x3(const SirenArgs& a, int64_t n_upper, hipStream_t s) {
     attr_done = true;
   }
   const int64_t tiles = (n_upper + S::P - 1) / S::P;
-#ifdef X3_CAP_BLOCKS
-  const int64_t cap = X3_CAP_BLOCKS;
-#else
   const int64_t cap = 256 * MINB;
-#endif
   const int blocks = (int)(tiles < cap ? (tiles < 1 ? 1 : tiles) : cap);
   hipLaunchKernelGGL((k_siren_step_x3<H, NW, NB, MINB, FWD>), dim3(blocks), dim3(64 * NW), S::kLds, s, a);
   return 0;
@@ -939,27 +748,19 @@ int launch_x3_both(SirenArgs a, int64_t n_upper, hipStream_t s) {
 
 }  // namespace
 
-#ifndef X3_NW
-#define X3_NW 8
-#endif
-#ifndef X3_MINB256
-#define X3_MINB256 1   // workgroups per CU at H = 256
-#endif
-#ifndef X3_NB256
-#define X3_NB256 3   // point tiles of 32 per workgroup at H = 256 (4 would fit LDS with the two-part layout, but needs
-                     // 64 + 64 + 32 accumulator / operand registers: 101 spilled VGPRs, 3.63 instead of 3.26 ms)
-#endif
-#ifndef X3_MINB128
-#define X3_MINB128 1   // workgroups per CU for H = 128: 2 would fit (78 KiB LDS each) but the 256-VGPR budget then forces
-                       // scratch spills, and that build is not repeatable from run to run (tools/siren_repeat_check.py)
-#endif
+constexpr int kNW256 = 8;      // waves per workgroup at H = 256
+constexpr int kMinB256 = 1;    // workgroups per CU at H = 256
+constexpr int kNB256 = 3;      // point tiles of 32 per workgroup at H = 256 (4 would fit LDS with the two-part layout, but needs
+                               // 64 + 64 + 32 accumulator / operand registers: 101 spilled VGPRs, 3.63 instead of 3.26 ms)
+constexpr int kMinB128 = 1;    // workgroups per CU for H = 128: 2 would fit (78 KiB LDS each) but the 256-VGPR budget then forces
+                               // scratch spills, and that build is not repeatable from run to run (tools/siren_repeat_check.py)
 bool siren_x3_supported(int H, int L) { return (H == 256 || H == 128) && L >= 1 && L <= 8; }
 
 int64_t siren_x3_stash_floats(int H, int L) {
   if (H == 256) {     // both tile shapes of a split list run in one launch: a region each
-    return 256 * X3_MINB256 * (X3Shape<256, X3_NW, X3_NB256>::kStashPerWg(L) + X3Shape<256, X3_NW, 1>::kStashPerWg(L));
+    return 256 * kMinB256 * (X3Shape<256, kNW256, kNB256>::kStashPerWg(L) + X3Shape<256, kNW256, 1>::kStashPerWg(L));
   }
-  if (H == 128) return 256 * X3_MINB128 * X3Shape<128, 4, 3>::kStashPerWg(L);
+  if (H == 128) return 256 * kMinB128 * X3Shape<128, 4, 3>::kStashPerWg(L);
   return 0;
 }
 
@@ -968,56 +769,32 @@ void siren_x3_pack(const float* raw, float* packed, int H, int L, hipStream_t s)
   hipLaunchKernelGGL(k_siren_pack_x3, dim3(iso_stream_grid(words, 256)), dim3(256), 0, s, raw, packed, H, L);
   if (L > 0) {
     hipLaunchKernelGGL(k_siren_wscale, dim3(L), dim3(256), 0, s, raw, packed, H, L);
-#ifdef ISO_WITH_SIREN_PS
-    if (siren_ps_enabled() && siren_ps_supported(H, L)) hipLaunchKernelGGL(k_siren_ps_bounds, dim3(L), dim3(256), 0, s, raw, packed, H, L);
-#endif
     hipLaunchKernelGGL(k_siren_pack_f16, dim3(iso_stream_grid(2 * (int64_t)L * H * H, 256)), dim3(256), 0, s, raw, packed, H, L);
   }
 }
 
-int siren_x3_tail_blocks() { return 256 * X3_MINB256; }
+int siren_x3_tail_blocks() { return 256 * kMinB256; }
 
 int siren_x3_launch_tail(const SirenArgs& a, int H, hipStream_t s) {
   if (H != 256) return -1;
-  using SS = X3Shape<256, X3_NW, 1>;
+  using SS = X3Shape<256, kNW256, 1>;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_tail_x3<256, X3_NW, X3_MINB256>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_tail_x3<256, kNW256, kMinB256>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)SS::kLds);
     attr_done = true;
   }
-  hipLaunchKernelGGL((k_siren_tail_x3<256, X3_NW, X3_MINB256>), dim3(siren_x3_tail_blocks()), dim3(64 * X3_NW), SS::kLds, s, a);
+  hipLaunchKernelGGL((k_siren_tail_x3<256, kNW256, kMinB256>), dim3(siren_x3_tail_blocks()), dim3(64 * kNW256), SS::kLds, s, a);
   return 0;
 }
 
-// ISO_SIREN_PS=1: lists the point-stationary kernel takes (siren_ps_takes) are served by it; the launch of this file's
-// kernels that follows carries ps_guard and returns at once for them
-#ifdef ISO_WITH_SIREN_PS
-static bool siren_ps_enabled() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("ISO_SIREN_PS"); v = (e && e[0] == '1') ? 1 : 0; }
-  return v == 1;
-}
-#endif
-
 int siren_x3_launch(const SirenArgs& a, int H, int64_t n_upper, hipStream_t s) {
-#ifdef ISO_WITH_SIREN_PS
-  if (siren_ps_enabled() && H == 256 && !a.fwd_only && !a.dirs && siren_ps_supported(H, a.L) && n_upper >= kPsMinList &&
-      (a.split == 3 || (a.split == 0 && !a.small_tiles)) && a.cnt_lo < 0 && a.cnt_hi == INT64_MAX) {
-    siren_ps_launch(a, n_upper, s);
-    SirenArgs g = a;
-    g.ps_guard = 1;
-    if (g.split == 3) return launch_x3_both<256, X3_NW, X3_NB256, X3_MINB256>(g, n_upper, s);
-    return launch_x3<256, X3_NW, X3_NB256, X3_MINB256, false>(g, n_upper, s);
-  }
-#endif
-  if (a.split == 3 && H == 256 && !a.fwd_only) return launch_x3_both<256, X3_NW, X3_NB256, X3_MINB256>(a, n_upper, s);
-  if (a.small_tiles && H == 256 && !a.fwd_only) return launch_x3<256, X3_NW, 1, X3_MINB256, false>(a, n_upper, s);
+  if (a.split == 3 && H == 256 && !a.fwd_only) return launch_x3_both<256, kNW256, kNB256, kMinB256>(a, n_upper, s);
   if (a.fwd_only) {
-    if (H == 256) return launch_x3<256, X3_NW, X3_NB256, X3_MINB256, true>(a, n_upper, s);
-    if (H == 128) return launch_x3<128, 4, 3, X3_MINB128, true>(a, n_upper, s);
+    if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, true>(a, n_upper, s);
+    if (H == 128) return launch_x3<128, 4, 3, kMinB128, true>(a, n_upper, s);
   }
-  if (H == 256) return launch_x3<256, X3_NW, X3_NB256, X3_MINB256, false>(a, n_upper, s);
-  if (H == 128) return launch_x3<128, 4, 3, X3_MINB128, false>(a, n_upper, s);
+  if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, false>(a, n_upper, s);
+  if (H == 128) return launch_x3<128, 4, 3, kMinB128, false>(a, n_upper, s);
   return -1;
 }

@@ -593,37 +593,12 @@ struct PixK {
     id[0] = m[0] ? ci : id[0];
   }
   // The same insertion for the (z, id) part only (the caller recomputes q for the K survivors at the end).
-  // Compares are half-rate instructions here and the swap chain above spends three per level plus six
-  // selects; this form takes one `<` and one `==` per level (the id compare only when some lane of the wave
-  // meets an equal depth), the depths move with one v_med3_f32 per level and the ids with two selects.
   __device__ __forceinline__ void push_zi(float cz, int ci, int K) {
-#ifdef RS_OLD_PUSH
-    bool lt[KMAX], eq[KMAX];
-    bool tie = false;
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) {
-      lt[j] = j < K && cz < z[j];
-      eq[j] = j < K && cz == z[j];
-      tie = tie || eq[j];
-    }
-    if (__any(tie)) {
-#pragma unroll
-      for (int j = 0; j < KMAX; ++j) lt[j] = lt[j] || (eq[j] && ci < id[j]);
-    }
-#pragma unroll
-    for (int j = KMAX - 1; j >= 1; --j) {
-      id[j] = lt[j - 1] ? id[j - 1] : (lt[j] ? ci : id[j]);
-      if (K == KMAX) z[j] = __builtin_amdgcn_fmed3f(z[j - 1], cz, z[j]);     // sorted list: the middle one
-      else z[j] = lt[j - 1] ? z[j - 1] : (lt[j] ? cz : z[j]);
-    }
-    id[0] = lt[0] ? ci : id[0];
-    z[0] = lt[0] ? cz : z[0];
-#else
     // Depths here are >= +0 and never NaN (binning drops z < 0 and NaN, the caller adds +0.0f so that -0 is +0): their
     // float order is the order of their bit patterns as unsigned integers, and (z, id) "less" is three integer compares
     // whose masks go straight into the selects -- no tie pass, no ballot, no boolean arrays in vector registers (the
-    // first form compiled to ~200 instructions per insertion; knock-outs of round 5: the insertions were 98 of the
-    // kernel's 207 us).
+    // first form, a tie pass and v_med3_f32 per level, compiled to ~200 instructions per insertion; knock-outs of round 5:
+    // the insertions were 98 of the kernel's 207 us).
     const unsigned cu = __float_as_uint(cz);
     bool m[KMAX];
     const bool full = K == KMAX;                        // (uniform: the usual case drops the slot test)
@@ -635,17 +610,11 @@ struct PixK {
     }
 #pragma unroll
     for (int j = KMAX - 1; j >= 1; --j) {
-      // (sorted list, all slots live: the new z[j] is the middle one of z[j-1], cz, z[j])
-#ifdef RS_MED3
-      z[j] = full ? __builtin_amdgcn_fmed3f(z[j - 1], cz, z[j]) : (m[j - 1] ? z[j - 1] : (m[j] ? cz : z[j]));
-#else
       z[j] = m[j - 1] ? z[j - 1] : (m[j] ? cz : z[j]);
-#endif
       id[j] = m[j - 1] ? id[j - 1] : (m[j] ? ci : id[j]);
     }
     z[0] = m[0] ? cz : z[0];
     id[0] = m[0] ? ci : id[0];
-#endif
   }
 };
 
@@ -692,47 +661,15 @@ __device__ __forceinline__ void composite_pixel(const PixK<KMAX>& best, int K, f
   ca.img[pix * (ca.C + 1) + ca.C] = hit ? 1.0f : 0.0f;
 }
 
-// -DRS_DBG_PHASES (timing experiment, tools/diag/raster_phases.py): thread 0 of every workgroup of k_raster adds the
-// shader-clock time between consecutive marks (barrier waits included) to its slot of rs_phase.
-#ifdef RS_DBG_PHASES
-__device__ unsigned long long rs_phase[32768 * 8];
-__shared__ unsigned long long s_rs_t, s_rs_acc[8];
-#define RS_PH(i) do { if (threadIdx.x == 0) { const unsigned long long t_ = clock64(); \
-  if ((i) >= 0) s_rs_acc[(i) < 0 ? 0 : (i)] += t_ - s_rs_t; \
-  else for (int q_ = 0; q_ < 8; ++q_) s_rs_acc[q_] = 0; \
-  s_rs_t = t_; } } while (0)
-#define RS_PH_FLUSH() do { if (threadIdx.x == 0 && blockIdx.x < 32768) for (int q_ = 0; q_ < 8; ++q_) \
-  rs_phase[blockIdx.x * 8 + q_] += s_rs_acc[q_]; } while (0)
-extern "C" int iso_dbg_raster_phases(double* out16) {
-  static unsigned long long h[32768 * 8];
-  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(rs_phase), sizeof(h)) != hipSuccess) return -1;
-  for (int i = 0; i < 16; ++i) out16[i] = 0.0;
-  for (int w = 0; w < 32768; ++w) {
-    bool any = false;
-    for (int i = 0; i < 8; ++i) { out16[i] += (double)h[w * 8 + i]; any = any || h[w * 8 + i]; }
-    if (any) out16[8] += 1.0;
-  }
-  void* dp = nullptr;
-  (void)hipGetSymbolAddress(&dp, HIP_SYMBOL(rs_phase));
-  (void)hipMemset(dp, 0, sizeof(h));
-  return 0;
-}
-#else
-#define RS_PH(i) do {} while (0)
-#define RS_PH_FLUSH() do {} while (0)
-#endif
-
-// CP ("candidate parallel"): how the hits of a chunk of 256 candidates reach the pixels.
-//   false: every pixel thread walks the candidates that reach its wave's four rows and tests each one (the first
-//          form: the K-best insertion, ~50 instructions, runs for the whole wave whenever ANY of its lanes is hit --
-//          with splats a few pixels wide that is nearly every candidate, for a handful of lanes each time);
-//   true:  thread t walks the few pixels of candidate t's bounding box inside the tile, tests them exactly as the
-//          pixel thread would (same expressions on the same operands) and appends t to the hit list of every pixel
-//          it covers (LDS counters); the pixel threads then insert only their own hits.  The K-best rule is a total
-//          order on (z, id), so the arrival order in the lists does not matter.  A pixel's first kHitList hits of a
-//          chunk go to its list, the others set the candidate's bit in the pixel's mask (s_more: 256 bits), which the
-//          pixel thread walks after its list.  Up to kWideCap candidates per chunk whose box covers more than
-//          kWideArea pixels take the first form (tested by every pixel thread).
+// How the hits of a chunk of 256 candidates reach the pixels ("candidate parallel"): thread t walks the few pixels of
+// candidate t's bounding box inside the tile, tests them exactly as the pixel thread would (same expressions on the same
+// operands) and appends t to the hit list of every pixel it covers (LDS counters); the pixel threads then insert only
+// their own hits.  The K-best rule is a total order on (z, id), so the arrival order in the lists does not matter.  A
+// pixel's first kHitList hits of a chunk go to its list, the others set the candidate's bit in the pixel's mask (s_more:
+// 256 bits), which the pixel thread walks after its list.  Up to kWideCap candidates per chunk whose box covers more than
+// kWideArea pixels are tested by every pixel thread instead.  (The first form had every pixel thread walk the
+// candidates that reach its wave's four rows and test each one: the K-best insertion, ~50 instructions, ran for the whole
+// wave whenever ANY of its lanes was hit -- with splats a few pixels wide that is nearly every candidate.)
 // (Round 4, when a pixel with more hits than list entries tested ALL 256 candidates: 32 / 24 / 16-entry lists 316 / 333 /
 // 429 us against 302 with 40; wide boxes from 24 / 48 / 96 / 192 pixels: 367 / 302 / 294 / 298 us.  Round 5 knock-outs at the
 // scale of one rank's band of 8, SIREN surface: that overfull path was 43 of the kernel's 98 us -- a silhouette tile
@@ -743,8 +680,8 @@ constexpr int kHitList = 32, kWideArea = 96, kWideCap = 32;
 // per-slot `j < K` tests, the selection of the list's last live entry and their scalar branches fold away (a third of
 // the instructions of an insertion).  (Seven workgroups per CU leave 72 vector registers; the runtime-K form needs one
 // more and takes six -- a raster kernel must not spill, tests/test_abi.py.)
-template <int KMAX, bool CP, bool KFULL = false>
-__global__ __launch_bounds__(256, (CP && KMAX <= 8) ? (KFULL ? 7 : 6) : 1) void k_raster(
+template <int KMAX, bool KFULL = false>
+__global__ __launch_bounds__(256, KMAX <= 8 ? (KFULL ? 7 : 6) : 1) void k_raster(
     const float* __restrict__ pts, const float* __restrict__ ellipse,
     const float* __restrict__ cutoff, const float* __restrict__ radii,
     const int32_t* __restrict__ tile_order, const int4* __restrict__ items, const int32_t* __restrict__ item_count,
@@ -753,16 +690,9 @@ __global__ __launch_bounds__(256, (CP && KMAX <= 8) ? (KFULL ? 7 : 6) : 1) void 
     int K_arg, float depth_thres, int32_t* __restrict__ idx_out, float* __restrict__ zbuf_out, float* __restrict__ q_out,
     float* __restrict__ occ_out, CompositeArgs ca) {
   const int K = KFULL ? KMAX : K_arg;
-  constexpr int NSOA = CP ? 1 : 256;
-  __shared__ float s_px[NSOA], s_py[NSOA], s_pz[NSOA], s_a[NSOA], s_b[NSOA], s_c[NSOA], s_rx[NSOA], s_ry[NSOA], s_cut[NSOA];
-  __shared__ int s_id[NSOA];
-  // per-wave candidate lists: wave w owns pixel rows 4w..4w+3 of the tile and only walks the
-  // candidates whose y-extent reaches those rows (splats are a few pixels wide: ~40 % of them)
-  __shared__ short s_list[4][NSOA];
-  __shared__ int s_cntw[4][4];       // [source wave][target wave]
-  __shared__ int s_hits[CP ? 256 : 1];                      // CP: hits of the chunk per pixel
-  __shared__ __attribute__((aligned(16))) unsigned char s_hit[CP ? 256 : 1][CP ? kHitList : 1];   // the first kHitList of them
-  __shared__ unsigned s_more[CP ? 8 : 1][CP ? 256 : 1];     // the others: bit k % 32 of word [k / 32][pixel]
+  __shared__ int s_hits[256];                                                // hits of the chunk per pixel
+  __shared__ __attribute__((aligned(16))) unsigned char s_hit[256][kHitList];   // the first kHitList of them
+  __shared__ unsigned s_more[8][256];                                        // the others: bit k % 32 of word [k / 32][pixel]
   // workgroups take the tiles of the band heaviest first (k_tile_order): a tile on the sphere's
   // silhouette holds 8x the mean number of candidates and would otherwise finish long after the rest
   // a work item = a tile, or -- for the tiles that hold many times the mean number of candidates (a
@@ -781,9 +711,8 @@ __global__ __launch_bounds__(256, (CP && KMAX <= 8) ? (KFULL ? 7 : 6) : 1) void 
   const int xi = tx * TILE + lx, yi = ty * TILE + ly;  // NDC pixel index
   const bool inside = xi < F.W && yi < F.H;
   const float xf = ndc_x(xi, F), yf = ndc_y(yi, F);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  // NDC y-range of the four row bands (pix_to_ndc is increasing), widened a little so that the
-  // band test is a strict superset of the exact per-pixel test below
+  // NDC y-range of the tile's four row bands.  Nothing reads them since the per-row candidate walk is gone; they stay
+  // because dropping them changes this kernel's machine code (the compiler schedules their ndc_y work with yf's).
   float band_lo[4], band_hi[4];
 #pragma unroll
   for (int w = 0; w < 4; ++w) {
@@ -803,205 +732,127 @@ __global__ __launch_bounds__(256, (CP && KMAX <= 8) ? (KFULL ? 7 : 6) : 1) void 
     c_begin = (int)((int64_t)chunks * slice / nslices) * 256;
     cnt = min(cnt, (int)((int64_t)chunks * (slice + 1) / nslices) * 256);
   }
-  if constexpr (CP) {
-    // records of a chunk: {x, y, z, id} in LDS (the pixel threads read depth and id of their hits); {a, b, c, cutoff}
-    // {rx, ry} stay in the registers of the thread that walks the candidate's box -- only the few wide candidates put
-    // theirs in a small table for the pixel threads.  The next chunk's records are requested (into registers) while
-    // this one is worked on.
-    // ONE record buffer (a third barrier per chunk): 22.5 KB of LDS instead of 37 put seven workgroups on a CU
-    // instead of four -- 387 -> 302 us; the kernel is bound by what the resident waves can overlap
-    __shared__ float4 s_r0[256];
-    __shared__ short s_wide[2][kWideCap];
-    __shared__ float s_wrec[2][kWideCap][6];              // {a, b, c, cutoff, rx, ry}
-    __shared__ int s_nw[2];
-    float4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = r0;
-    float2 r2 = {0.f, 0.f};
-    auto fetch = [&](int c0) {
-      if (c0 + (int)threadIdx.x < cnt) {
-        const int p = pairs[off + c0 + threadIdx.x];
-        r0 = make_float4(pts[(int64_t)p * 3], pts[(int64_t)p * 3 + 1], pts[(int64_t)p * 3 + 2], __int_as_float(p));
-        r1 = make_float4(ellipse[(int64_t)p * 3], ellipse[(int64_t)p * 3 + 1], ellipse[(int64_t)p * 3 + 2], cutoff[p]);
-        r2 = make_float2(radii[(int64_t)p * 2], radii[(int64_t)p * 2 + 1]);
-      }
-    };
-    int par = 0;
-    auto push_if_better = [&](const float4& c0v) {
-      const float pz = c0v.z + 0.0f;                     // (-0 -> +0: push_zi orders depths by their bit patterns)
-      const int id = __float_as_int(c0v.w);
-      if (pz < wz || (pz == wz && id < wi)) {
-        best.push_zi(pz, id, K);
-        if (K == KMAX) { wz = best.z[KMAX - 1]; wi = best.id[KMAX - 1]; }
-        else {
+  // records of a chunk: {x, y, z, id} in LDS (the pixel threads read depth and id of their hits); {a, b, c, cutoff}
+  // {rx, ry} stay in the registers of the thread that walks the candidate's box -- only the few wide candidates put
+  // theirs in a small table for the pixel threads.  The next chunk's records are requested (into registers) while
+  // this one is worked on.
+  // ONE record buffer (a third barrier per chunk): 22.5 KB of LDS instead of 37 put seven workgroups on a CU
+  // instead of four -- 387 -> 302 us; the kernel is bound by what the resident waves can overlap
+  __shared__ float4 s_r0[256];
+  __shared__ short s_wide[2][kWideCap];
+  __shared__ float s_wrec[2][kWideCap][6];              // {a, b, c, cutoff, rx, ry}
+  __shared__ int s_nw[2];
+  float4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = r0;
+  float2 r2 = {0.f, 0.f};
+  auto fetch = [&](int c0) {
+    if (c0 + (int)threadIdx.x < cnt) {
+      const int p = pairs[off + c0 + threadIdx.x];
+      r0 = make_float4(pts[(int64_t)p * 3], pts[(int64_t)p * 3 + 1], pts[(int64_t)p * 3 + 2], __int_as_float(p));
+      r1 = make_float4(ellipse[(int64_t)p * 3], ellipse[(int64_t)p * 3 + 1], ellipse[(int64_t)p * 3 + 2], cutoff[p]);
+      r2 = make_float2(radii[(int64_t)p * 2], radii[(int64_t)p * 2 + 1]);
+    }
+  };
+  int par = 0;
+  auto push_if_better = [&](const float4& c0v) {
+    const float pz = c0v.z + 0.0f;                     // (-0 -> +0: push_zi orders depths by their bit patterns)
+    const int id = __float_as_int(c0v.w);
+    if (pz < wz || (pz == wz && id < wi)) {
+      best.push_zi(pz, id, K);
+      if (K == KMAX) { wz = best.z[KMAX - 1]; wi = best.id[KMAX - 1]; }
+      else {
 #pragma unroll
-          for (int j = 0; j < KMAX; ++j) if (j == K - 1) { wz = best.z[j]; wi = best.id[j]; }
+        for (int j = 0; j < KMAX; ++j) if (j == K - 1) { wz = best.z[j]; wi = best.id[j]; }
+      }
+    }
+  };
+  auto hit_push = [&](int k) { push_if_better(s_r0[k]); };                      // a listed hit: it passed the tests already
+  auto wide_push = [&](int i) {                                                  // entry i of the wide table, tested here
+    const float4 c0v = s_r0[s_wide[par][i]];
+    const float* wr = s_wrec[par][i];
+    const float dx = xf - c0v.x, dy = yf - c0v.y;
+    if (fabsf(dx) > wr[4] || fabsf(dy) > wr[5]) return;                          // rasterize_points.cu:92
+    const float q = wr[0] * dx * dx + wr[1] * dx * dy + wr[2] * dy * dy;          // :94
+    if (q > wr[3]) return;                                                       // :96
+    push_if_better(c0v);
+  };
+  s_hits[threadIdx.x] = 0;
+#pragma unroll
+  for (int w = 0; w < 8; ++w) s_more[w][threadIdx.x] = 0u;
+  if (threadIdx.x < 2) s_nw[threadIdx.x] = 0;
+  fetch(c_begin);
+  for (int c0 = c_begin; c0 < cnt; c0 += 256, par ^= 1) {
+    const int m = min(256, cnt - c0);
+    const float4 c0v = r0, c1v = r1;                    // this thread's candidate of the chunk
+    const float2 c2v = r2;
+    if ((int)threadIdx.x < m) s_r0[threadIdx.x] = r0;
+    __syncthreads();                                    // records visible; the hit counters are zero
+    fetch(c0 + 256);
+    if ((int)threadIdx.x < m) {
+      const int k = threadIdx.x;
+      int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
+      const bool any = pixel_range(c0v.x, c2v.x, F.W, F.ex, F.m, x0, x1) && pixel_range(c0v.y, c2v.y, F.H, F.ey, F.m, y0, y1);
+      x0 = max(x0, tx * TILE); x1 = min(x1, tx * TILE + TILE - 1);
+      y0 = max(y0, ty * TILE); y1 = min(y1, ty * TILE + TILE - 1);
+      bool walk = any && x0 <= x1 && y0 <= y1;
+      if (walk && (x1 - x0 + 1) * (y1 - y0 + 1) > kWideArea) {
+        const int ws = atomicAdd(&s_nw[par], 1);
+        if (ws < kWideCap) {                            // (a full table: the box is walked like the others)
+          s_wide[par][ws] = (short)k;
+          float* wr = s_wrec[par][ws];
+          wr[0] = c1v.x; wr[1] = c1v.y; wr[2] = c1v.z; wr[3] = c1v.w; wr[4] = c2v.x; wr[5] = c2v.y;
+          walk = false;
         }
       }
-    };
-    auto hit_push = [&](int k) { push_if_better(s_r0[k]); };                      // a listed hit: it passed the tests already
-    auto wide_push = [&](int i) {                                                  // entry i of the wide table, tested here
-      const float4 c0v = s_r0[s_wide[par][i]];
-      const float* wr = s_wrec[par][i];
-      const float dx = xf - c0v.x, dy = yf - c0v.y;
-      if (fabsf(dx) > wr[4] || fabsf(dy) > wr[5]) return;                          // rasterize_points.cu:92
-      const float q = wr[0] * dx * dx + wr[1] * dx * dy + wr[2] * dy * dy;          // :94
-      if (q > wr[3]) return;                                                       // :96
-      push_if_better(c0v);
-    };
+      if (walk) {
+        for (int y = y0; y <= y1; ++y) {
+          const float dy = ndc_y(y, F) - c0v.y;
+          if (fabsf(dy) > c2v.y) continue;
+          for (int x = x0; x <= x1; ++x) {
+            const float dx = ndc_x(x, F) - c0v.x;
+            if (fabsf(dx) > c2v.x) continue;
+            const float q = c1v.x * dx * dx + c1v.y * dx * dy + c1v.z * dy * dy;
+            if (q > c1v.w) continue;
+            const int pl = (y - ty * TILE) * TILE + (x - tx * TILE);
+            const int slot = atomicAdd(&s_hits[pl], 1);
+            if (slot < kHitList) s_hit[pl][slot] = (unsigned char)k;
+            else atomicOr(&s_more[k >> 5][pl], 1u << (k & 31));         // beyond the list: the pixel's bit mask
+          }
+        }
+      }
+    }
+    __syncthreads();                                    // hit lists complete
+    const int nh = s_hits[threadIdx.x];
     s_hits[threadIdx.x] = 0;
-#pragma unroll
-    for (int w = 0; w < 8; ++w) s_more[w][threadIdx.x] = 0u;
-    if (threadIdx.x < 2) s_nw[threadIdx.x] = 0;
-    RS_PH(-1);
-    fetch(c_begin);
-    for (int c0 = c_begin; c0 < cnt; c0 += 256, par ^= 1) {
-      const int m = min(256, cnt - c0);
-      const float4 c0v = r0, c1v = r1;                    // this thread's candidate of the chunk
-      const float2 c2v = r2;
-      if ((int)threadIdx.x < m) s_r0[threadIdx.x] = r0;
-      __syncthreads();                                    // records visible; the hit counters are zero
-      RS_PH(0);
-      fetch(c0 + 256);
-#ifdef RS_KO_A        // timing experiment (results wrong): no candidate phase
-      if (false) {
-#else
-      if ((int)threadIdx.x < m) {
-#endif
-        const int k = threadIdx.x;
-        int x0 = 0, x1 = -1, y0 = 0, y1 = -1;
-        const bool any = pixel_range(c0v.x, c2v.x, F.W, F.ex, F.m, x0, x1) && pixel_range(c0v.y, c2v.y, F.H, F.ey, F.m, y0, y1);
-        x0 = max(x0, tx * TILE); x1 = min(x1, tx * TILE + TILE - 1);
-        y0 = max(y0, ty * TILE); y1 = min(y1, ty * TILE + TILE - 1);
-        bool walk = any && x0 <= x1 && y0 <= y1;
-        if (walk && (x1 - x0 + 1) * (y1 - y0 + 1) > kWideArea) {
-          const int ws = atomicAdd(&s_nw[par], 1);
-          if (ws < kWideCap) {                            // (a full table: the box is walked like the others)
-            s_wide[par][ws] = (short)k;
-            float* wr = s_wrec[par][ws];
-            wr[0] = c1v.x; wr[1] = c1v.y; wr[2] = c1v.z; wr[3] = c1v.w; wr[4] = c2v.x; wr[5] = c2v.y;
-            walk = false;
-          }
-        }
-        if (walk) {
-          for (int y = y0; y <= y1; ++y) {
-            const float dy = ndc_y(y, F) - c0v.y;
-            if (fabsf(dy) > c2v.y) continue;
-            for (int x = x0; x <= x1; ++x) {
-              const float dx = ndc_x(x, F) - c0v.x;
-              if (fabsf(dx) > c2v.x) continue;
-              const float q = c1v.x * dx * dx + c1v.y * dx * dy + c1v.z * dy * dy;
-              if (q > c1v.w) continue;
-              const int pl = (y - ty * TILE) * TILE + (x - tx * TILE);
-              const int slot = atomicAdd(&s_hits[pl], 1);
-              if (slot < kHitList) s_hit[pl][slot] = (unsigned char)k;
-              else atomicOr(&s_more[k >> 5][pl], 1u << (k & 31));         // beyond the list: the pixel's bit mask
-            }
-          }
-        }
-      }
-      __syncthreads();                                    // hit lists complete
-      RS_PH(1);
-      const int nh = s_hits[threadIdx.x];
-      s_hits[threadIdx.x] = 0;
-      if (threadIdx.x == 0) s_nw[par ^ 1] = 0;
-#ifdef RS_KO_B          // timing experiment (results wrong): no insertions
-      if (false) {
-#else
-      if (inside) {
-#endif
-        const int nl = min(nh, kHitList);
-        for (int i = 0; i < nl; ++i) hit_push(s_hit[threadIdx.x][i]);
-        if (nh > kHitList) {
-#pragma unroll 1
-          for (int w = 0; w < 8; ++w) {
-            unsigned mm = s_more[w][threadIdx.x];
-            s_more[w][threadIdx.x] = 0u;
-            while (mm) {
-              const int b = __ffs((int)mm) - 1;
-              mm &= mm - 1u;
-              hit_push(w * 32 + b);
-            }
-          }
-        }
-        const int nw = min(s_nw[par], kWideCap);
-        for (int i = 0; i < nw; ++i) wide_push(i);
-      }
-      RS_PH(2);
-      __syncthreads();                                    // one record buffer: all reads done before the next chunk lands
-      RS_PH(3);
-    }
-    // q of the K survivors (:94; the same expression on the same operands as the hit test): their records are
-    // re-read once per tile instead of carrying q through every insertion
-#ifdef RS_KO_EPI        // timing experiment (results wrong): no epilogue
-    if (best.z[0] == 12345.f) occ_out[0] = 1.f;
-    return;
-#endif
+    if (threadIdx.x == 0) s_nw[par ^ 1] = 0;
     if (inside) {
-#pragma unroll
-      for (int j = 0; j < KMAX; ++j) {
-        if (j < K && best.z[j] < FLT_MAX) {
-          const int64_t p = best.id[j];
-          const float dx = xf - pts[p * 3], dy = yf - pts[p * 3 + 1];
-          best.q[j] = ellipse[p * 3] * dx * dx + ellipse[p * 3 + 1] * dx * dy + ellipse[p * 3 + 2] * dy * dy;
-        }
-      }
-    }
-    RS_PH(4);
-  } else {
-  for (int c0 = c_begin; c0 < cnt; c0 += 256) {
-      const int m = min(256, cnt - c0);
-      __syncthreads();
-      bool hit_band[4] = {false, false, false, false};
-      if ((int)threadIdx.x < m) {
-        const int p = pairs[off + c0 + threadIdx.x];
-        const float py = pts[(int64_t)p * 3 + 1], ry = radii[(int64_t)p * 2 + 1];
-        s_px[threadIdx.x] = pts[(int64_t)p * 3];
-        s_py[threadIdx.x] = py;
-        s_pz[threadIdx.x] = pts[(int64_t)p * 3 + 2];
-        s_a[threadIdx.x] = ellipse[(int64_t)p * 3];
-        s_b[threadIdx.x] = ellipse[(int64_t)p * 3 + 1];
-        s_c[threadIdx.x] = ellipse[(int64_t)p * 3 + 2];
-        s_rx[threadIdx.x] = radii[(int64_t)p * 2];
-        s_ry[threadIdx.x] = ry;
-        s_cut[threadIdx.x] = cutoff[p];
-        s_id[threadIdx.x] = p;
-        const float ylo = py - ry * 1.000001f - 1.0e-6f, yhi = py + ry * 1.000001f + 1.0e-6f;
-  #pragma unroll
-        for (int w = 0; w < 4; ++w) hit_band[w] = !(yhi < band_lo[w]) && !(ylo > band_hi[w]);   // NaN -> kept
-      }
-      int rank[4];
-  #pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        const unsigned long long bal = __ballot(hit_band[w]);
-        rank[w] = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) s_cntw[wave][w] = __popcll(bal);
-      }
-      __syncthreads();
-  #pragma unroll
-      for (int w = 0; w < 4; ++w) {
-        if (hit_band[w]) {
-          int base = 0;
-  #pragma unroll
-          for (int sw = 0; sw < 4; ++sw) base += (sw < wave) ? s_cntw[sw][w] : 0;
-          s_list[w][base + rank[w]] = (short)threadIdx.x;
-        }
-      }
-      const int mine = s_cntw[0][wave] + s_cntw[1][wave] + s_cntw[2][wave] + s_cntw[3][wave];
-      __syncthreads();
-      if (inside) {
-        for (int i = 0; i < mine; ++i) {
-          const int k = s_list[wave][i];
-          const float dx = xf - s_px[k], dy = yf - s_py[k];
-          if (fabsf(dx) > s_rx[k] || fabsf(dy) > s_ry[k]) continue;  // rasterize_points.cu:92
-          const float q = s_a[k] * dx * dx + s_b[k] * dx * dy + s_c[k] * dy * dy;  // :94
-          if (q > s_cut[k]) continue;                                              // :96
-          const float pz = s_pz[k] + 0.0f;            // (-0 -> +0: the slice merge orders depths by their bit patterns)
-          const int id = s_id[k];
-          if (pz < wz || (pz == wz && id < wi)) {
-            best.push(pz, id, q, K);
-  #pragma unroll
-            for (int j = 0; j < KMAX; ++j) if (j == K - 1) { wz = best.z[j]; wi = best.id[j]; }
+      const int nl = min(nh, kHitList);
+      for (int i = 0; i < nl; ++i) hit_push(s_hit[threadIdx.x][i]);
+      if (nh > kHitList) {
+#pragma unroll 1
+        for (int w = 0; w < 8; ++w) {
+          unsigned mm = s_more[w][threadIdx.x];
+          s_more[w][threadIdx.x] = 0u;
+          while (mm) {
+            const int b = __ffs((int)mm) - 1;
+            mm &= mm - 1u;
+            hit_push(w * 32 + b);
           }
         }
+      }
+      const int nw = min(s_nw[par], kWideCap);
+      for (int i = 0; i < nw; ++i) wide_push(i);
+    }
+    __syncthreads();                                    // one record buffer: all reads done before the next chunk lands
+  }
+  // q of the K survivors (:94; the same expression on the same operands as the hit test): their records are
+  // re-read once per tile instead of carrying q through every insertion
+  if (inside) {
+#pragma unroll
+    for (int j = 0; j < KMAX; ++j) {
+      if (j < K && best.z[j] < FLT_MAX) {
+        const int64_t p = best.id[j];
+        const float dx = xf - pts[p * 3], dy = yf - pts[p * 3 + 1];
+        best.q[j] = ellipse[p * 3] * dx * dx + ellipse[p * 3 + 1] * dx * dy + ellipse[p * 3 + 2] * dy * dy;
       }
     }
   }
@@ -1013,8 +864,6 @@ __global__ __launch_bounds__(256, (CP && KMAX <= 8) ? (KFULL ? 7 : 6) : 1) void 
       sc[(KMAX + j) * 256 + threadIdx.x] = best.q[j];
       sc[(2 * KMAX + j) * 256 + threadIdx.x] = __int_as_float(best.id[j]);
     }
-    RS_PH(5);
-    RS_PH_FLUSH();
     return;
   }
   if (!inside) return;
@@ -1035,8 +884,6 @@ __global__ __launch_bounds__(256, (CP && KMAX <= 8) ? (KFULL ? 7 : 6) : 1) void 
     }
   }
   if (ca.scaler) composite_pixel<KMAX>(best, K, z0, depth_thres, hit, ca, pix);
-  RS_PH(5);
-  RS_PH_FLUSH();
 }
 
 // points_per_pixel above 32 (the reference allows 150, rasterization_utils.cuh:18): the K-best list of a pixel does
@@ -1828,9 +1675,6 @@ __global__ __launch_bounds__(256) void k_splat_backward(
 // the sparse gradient image of cfg 3a but 159 -> 228 us on the denser one of the SIREN cycle.  A lane adds its terms in
 // image order, the eight partial sums meet in a fixed tree -> bit-stable, no atomics, independent of the launch geometry.
 // (one lane per point: 100 -> 64 us, bound by the lane's chain of dependent loads at 2.4 waves per SIMD)
-#ifndef SB_RY
-#define SB_RY 4      // block rows whose flag words are requested together (1 / 2 / 4 / 8 / 16: 56 / 53 / 54 / 59 / 66 us on cfg 3a)
-#endif
 __global__ __launch_bounds__(256) void k_splat_backward_heavy(
     const float* __restrict__ pts, const float* __restrict__ radii, const float* __restrict__ rs,
     const int64_t* __restrict__ first, const int64_t* __restrict__ num, int n_clouds,
@@ -1862,7 +1706,8 @@ __global__ __launch_bounds__(256) void k_splat_backward_heavy(
     if (live && out_range(px, sx, F.W, F.ex, F.m, x0, x1) && out_range(py, sy, F.H, F.ey, F.m, y0, y1)) {
       const float* __restrict__ gimg = grad_occ + (int64_t)n * F.H * F.W;
       const int bx0 = x0 / GB, bx1 = x1 / GB, by0 = y0 / GB, by1 = y1 / GB;
-      constexpr int RY = SB_RY;                           // block rows per round: their flag words are requested together
+      // block rows per round: their flag words are requested together (1 / 2 / 4 / 8 / 16: 56 / 53 / 54 / 59 / 66 us on cfg 3a)
+      constexpr int RY = 4;
       for (int cx = bx0 >> 3; cx <= bx1 >> 3; cx += 4) {  // 32 blocks (four row bytes = one unaligned word) per round
         // blocks of the window in this word, and of those the ones on this lane's diagonals
         const int ka = max(bx0 - cx * 8, 0), kb = min(bx1 - cx * 8, 31);
@@ -2318,13 +2163,6 @@ extern "C" int64_t iso_splat_forward_workspace_bytes(int64_t n_tiles, int points
   return 64 + 32 * n_tiles + slots * (16 + (int64_t)3 * KM * 256 * 4);
 }
 
-// ISO_RASTER_CP=0 in the environment selects the first form of the hit distribution (k_raster)
-static bool raster_cp() {
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("ISO_RASTER_CP"); v = (e && e[0] == '0') ? 0 : 1; }
-  return v == 1;
-}
-
 static int splat_forward_impl(CompositeArgs ca, const float* points, const float* ellipse, const float* cutoff,
                                  const float* radii, const int64_t* first_idx,
                                  const int64_t* num_pts, int n_clouds, int64_t max_pts,
@@ -2366,15 +2204,13 @@ static int splat_forward_impl(CompositeArgs ca, const float* points, const float
     heavy = items + tiles + max_slots;
     scratch = (float*)(heavy + tiles);
   }
-  static int target = -1;               // ISO_RASTER_ITEMS: development override of the work-item target (sweeps)
-  if (target < 0) { const char* e = getenv("ISO_RASTER_ITEMS"); target = e ? atoi(e) : kTargetItems; if (target < 1) target = kTargetItems; }
   bool items_done = false;
   if (max_pts > 0) {
     ISO_REQUIRE(points && ellipse && cutoff && radii, ISO_ERR_INVALID, "iso_splat_forward: null pointer");
     // the fill launch also makes the raster's work items (one more workgroup: they only need the offsets)
     items_done = launch_bin<true>(points, radii, first_idx, num_pts, n_clouds, max_pts, F, tile_row_begin,
                                   tile_row_end, tile_cursor, tile_off, pairs, pair_capacity, overflow_flag, s,
-                                  TileItemsJob{ty_rows, n_clouds, max_slots, target, items, heavy, counters});
+                                  TileItemsJob{ty_rows, n_clouds, max_slots, kTargetItems, items, heavy, counters});
   }
   if (K > 32) {                               // lists too deep for registers: one workgroup per tile, lists in the outputs
     hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, tile_off, F, tile_row_begin, ty_rows, n_clouds, tile_cursor);
@@ -2386,23 +2222,19 @@ static int splat_forward_impl(CompositeArgs ca, const float* points, const float
   if (items) {
     if (!items_done)
       hipLaunchKernelGGL(k_tile_items, dim3(1), dim3(1024), 0, s, tile_off, F, tile_row_begin, ty_rows, n_clouds, max_slots,
-                         target, items, heavy, counters);
+                         kTargetItems, items, heavy, counters);
   } else {
     // the fill cursors are dead now: their array takes the heaviest-first tile order
     hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, tile_off, F, tile_row_begin, ty_rows, n_clouds,
                        tile_cursor);
   }
 #define ISO_LAUNCH_R(KM_)                                                                            \
-  if (raster_cp() && K == KM_)                                                                   \
-    hipLaunchKernelGGL((k_raster<KM_, true, true>), dim3(tiles + max_slots), dim3(256), 0, s, points, ellipse, cutoff, radii, \
-                       tile_cursor, items, counters, scratch, tile_off, pairs, pair_capacity, F,                \
-                       K, depth_merging_thres, idx_out, zbuf_out, qvalue_out, occ_out, ca);             \
-  else if (raster_cp())                                                                                   \
+  if (K == KM_)                                                                                      \
     hipLaunchKernelGGL((k_raster<KM_, true>), dim3(tiles + max_slots), dim3(256), 0, s, points, ellipse, cutoff, radii, \
                        tile_cursor, items, counters, scratch, tile_off, pairs, pair_capacity, F,                \
                        K, depth_merging_thres, idx_out, zbuf_out, qvalue_out, occ_out, ca);             \
   else                                                                                               \
-    hipLaunchKernelGGL((k_raster<KM_, false>), dim3(tiles + max_slots), dim3(256), 0, s, points, ellipse, cutoff, radii, \
+    hipLaunchKernelGGL((k_raster<KM_>), dim3(tiles + max_slots), dim3(256), 0, s, points, ellipse, cutoff, radii, \
                        tile_cursor, items, counters, scratch, tile_off, pairs, pair_capacity, F,                \
                        K, depth_merging_thres, idx_out, zbuf_out, qvalue_out, occ_out, ca);             \
   if (items && K == KM_)                                                                              \
@@ -2889,8 +2721,8 @@ extern "C" int iso_splat_backward(const float* points, const float* radii, const
     hipLaunchKernelGGL(k_z_scatter, dim3(iso_stream_grid(npix, 256)), dim3(256), 0, s, idx, grad_zbuf,
                        points_per_pixel, npix, zs, zacc, (int64_t)0, terms_log2);
   // eight lanes per heavy point; the cost of a point varies with the gradient pixels under its disc, so the list is spread
-  // over short-lived workgroups (a workgroup past the end of the list reads the count and leaves; ISO_HEAVY_GRID overrides)
-  static const int heavy_grid = []() { const char* e = getenv("ISO_HEAVY_GRID"); const int v = e ? atoi(e) : 0; return v > 0 ? v : 4096; }();
+  // over short-lived workgroups (a workgroup past the end of the list reads the count and leaves)
+  constexpr int heavy_grid = 4096;
   hipLaunchKernelGGL(k_splat_backward_heavy, dim3(heavy_grid + r2.blocks), dim3(256), 0, s, points, radii, search_radius,
                      first_idx, num_pts, n_clouds, grad_occ, pixmask, rowbytes, G, F, rect_mode, radii_s,
                      heavy, heavy_count, grad_points, r2, heavy_grid);

@@ -111,7 +111,7 @@ SPILL_ALLOWED = {
     "10k_fps_lazyILi16E": (40, "test_fps_repeat_stress_500k"),
     "16k_brick_resampleILi16E": (32, "test_resample_k12_repeat_stress"),      # K + 1 in 10..13: not on the cycle
     "9k_brick_hILi2E": (1, "test_bandwidth_two_views_repeat_stress"),         # two views: not on the cycle
-    "8k_rasterILi8ELb1ELb1E": (1, "test_forward_massive_depth_ties_bit_exact"),  # a pixel coordinate; tests/test_ties_gpu.py
+    "8k_rasterILi8ELb1EE": (1, "test_forward_massive_depth_ties_bit_exact"),  # a pixel coordinate; tests/test_ties_gpu.py
 }
 
 

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Development aid: build a variant of libisopoints_hip.so with extra flags for ONE source file
-# (timing experiments; see the X3_DBG_* hooks in csrc/siren_x3.hip).
+# (timing experiments: -mllvm scheduler / code-generation options, or -D defines of a local experiment).
 # usage: tools/build_variant.sh NAME FILE.hip "-DFLAG ..."   -> tools/variants/libiso_NAME.so
 set -e
 cd "$(dirname "$0")/.."

@@ -1,5 +1,5 @@
-"""FPS at the reference's working sizes (wlop: half of 5 k .. 50 k points): ms and us per sample.  One process per mode
-(ISO_FPS_LAZY / ISO_FPS_PPT / ISO_FPS_ONE_WORKGROUP are read once or per call): python tools/diag/fps_small.py"""
+"""FPS at the reference's working sizes (wlop: half of 5 k .. 50 k points): ms and us per sample.
+usage: [ISO_FPS_ONE_WORKGROUP=1] python tools/diag/fps_small.py"""
 import sys, torch
 sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tools")
 from tools_common import timeit

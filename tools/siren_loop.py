@@ -1,5 +1,5 @@
 """Keep iso_siren_sdf_grad (the bench's dominant kernel) busy for SECONDS on 1 M points; prints ms per evaluation pass.
-usage: [ISO_SIREN_PS=1] [ISO_SIREN_GEMM=f32] python tools/siren_loop.py [SECONDS] [P]"""
+usage: [ISO_SIREN_GEMM=f32] python tools/siren_loop.py [SECONDS] [P]"""
 import os
 import sys
 import time
@@ -47,5 +47,5 @@ while time.time() - t0 < SEC:
     first = first if first is not None else ms
     last = ms
     n += 20
-print("siren_loop PS=%s GEMM=%s: %d passes of %d evaluations in %.2f s; ms per pass: first block %.3f, last block %.3f"
-      % (os.environ.get("ISO_SIREN_PS", "0"), os.environ.get("ISO_SIREN_GEMM", "split16"), n, P, time.time() - t0, first, last))
+print("siren_loop GEMM=%s: %d passes of %d evaluations in %.2f s; ms per pass: first block %.3f, last block %.3f"
+      % (os.environ.get("ISO_SIREN_GEMM", "split16"), n, P, time.time() - t0, first, last))
