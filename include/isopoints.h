@@ -134,6 +134,31 @@ int iso_siren_sdf_grad(const float* pts, float* sdf_out, float* grad_out,
                        int n_hidden, float omega_first, float omega_hidden,
                        void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Latent-conditioned SIREN (the reference's Siren(c_dim = C), DSS/models/common.py:90-165: forward concatenates the
+ * code in front of the point, [c, x], :150-152; its callers pass one code per cloud / batch row: combined_modeling.py:449,
+ * implicit_modeling.py:156-159 (projection), :305,313 (sphere tracing), :318-319 (secant search)).  Layer 0 of code u is
+ * sin(w0 (W0[:, C:] x + b_u)) with b_u = b0 + W0[:, :C] c_u: only layer 0's bias depends on the code.
+ * iso_siren_fold_codes: table[u * padded_hidden + f] = b0[f] + sum_k w0c[f * c_dim + k] codes[u * c_dim + k] for
+ *   f < hidden (accumulated in double in the order b0, k = 0, 1, ..; rounded once), 0 for hidden <= f < padded_hidden.
+ *   w0c = W0[:, :C] row-major (hidden x c_dim), b0 (hidden), codes (n_codes x c_dim); table (n_codes x padded_hidden) f32.
+ * The *_coded entry points take the image of the network whose W0 is W0[:, C:] (iso_siren_pack_weights; its b0 is not
+ * read) plus the table (padded_hidden = `hidden` of the call) and code_of (n int32, the table row of point / ray i, each
+ * in [0, n_codes); NULL: row 0 for every point, n_codes must then be 1).  A coded evaluation with row u is bit-identical
+ * to the uncoded one of the network whose b0 is row u.                                                               */
+int iso_siren_fold_codes(const float* w0c, const float* b0, const float* codes, float* table, int hidden,
+                         int padded_hidden, int c_dim, int64_t n_codes, void* stream);
+int iso_project_siren_coded(const float* pts_in, float* pts_out, float* normals_out,
+                            uint8_t* mask_out, int64_t n, const float* packed,
+                            int hidden, int n_hidden, float omega_first,
+                            float omega_hidden, int max_iters, float tol,
+                            void* workspace, int64_t workspace_bytes, void* stream,
+                            const float* code_bias, const int32_t* code_of, int64_t n_codes);
+int iso_siren_sdf_grad_coded(const float* pts, float* sdf_out, float* grad_out,
+                             int64_t n, const float* packed, int hidden,
+                             int n_hidden, float omega_first, float omega_hidden,
+                             void* workspace, int64_t workspace_bytes, void* stream,
+                             const float* code_bias, const int32_t* code_of, int64_t n_codes);
+
 /* IDR-style SDF (DSS/models/common.py:220-310): positional encoding with n_freq
  * frequencies (D0 = 3 + 6*n_freq <= 63), n_layers softplus(beta) layers of width `hidden`
  * (128/256/512), optional skip connection [h, e(x)]/sqrt(2) into layer skip_layer (< 0: none;
@@ -175,6 +200,13 @@ int iso_trace_siren(const float* ray0, const float* dirs, float* pts_out, float*
                     uint8_t* mask_out, int64_t n, const float* packed, int hidden, int n_hidden,
                     float omega_first, float omega_hidden, float alpha, float bound, int max_iters,
                     float tol, void* workspace, int64_t workspace_bytes, void* stream);
+/* the same for a latent-conditioned SIREN (implicit_modeling.py:305,313: SphereTracing.project_points(latent=c)); the
+ * code arguments as iso_project_siren_coded, code_of indexed by ray */
+int iso_trace_siren_coded(const float* ray0, const float* dirs, float* pts_out, float* sdf_out,
+                          uint8_t* mask_out, int64_t n, const float* packed, int hidden, int n_hidden,
+                          float omega_first, float omega_hidden, float alpha, float bound, int max_iters,
+                          float tol, void* workspace, int64_t workspace_bytes, void* stream,
+                          const float* code_bias, const int32_t* code_of, int64_t n_codes);
 int iso_trace_idr(const float* ray0, const float* dirs, float* pts_out, float* sdf_out,
                   uint8_t* mask_out, int64_t n, const float* packed, int hidden, int n_layers,
                   int skip_layer, int n_freq, float beta, float alpha, float bound, int max_iters,

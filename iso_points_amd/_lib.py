@@ -47,6 +47,10 @@ SIGNATURES = {
     "iso_idr_sdf_grad": (_I, [_P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _P, _L, _P]),
     "iso_trace_sphere": (_I, [_P, _P, _P, _P, _P, _L, _F, _F, _F, _F, _F, _F, _I, _F, _P]),
     "iso_trace_siren": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _F, _F, _F, _F, _I, _F, _P, _L, _P]),
+    "iso_siren_fold_codes": (_I, [_P, _P, _P, _P, _I, _I, _I, _L, _P]),
+    "iso_project_siren_coded": (_I, [_P, _P, _P, _P, _L, _P, _I, _I, _F, _F, _I, _F, _P, _L, _P, _P, _P, _L]),
+    "iso_siren_sdf_grad_coded": (_I, [_P, _P, _P, _L, _P, _I, _I, _F, _F, _P, _L, _P, _P, _P, _L]),
+    "iso_trace_siren_coded": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _F, _F, _F, _F, _I, _F, _P, _L, _P, _P, _P, _L]),
     "iso_trace_idr": (_I, [_P, _P, _P, _P, _P, _L, _P, _I, _I, _I, _I, _F, _F, _F, _I, _F, _P, _L, _P]),
     "iso_ray_nearest_point_workspace_bytes": (_L, [_L]),
     "iso_ray_nearest_point": (_I, [_P, _L, _F, _F, _F, _P, _L, _P, _P, _P, _P, _L, _P]),

@@ -99,8 +99,10 @@ __global__ void k_siren_pack(const float* __restrict__ raw, float* __restrict__ 
 #define ISO_GEMM_FWD(img, bias) gemm_pass<NT, true>(img, bias, hL, wbuf, acc, lane, g)
 #define ISO_GEMM_BWD(img) gemm_pass<NT, false>(img, nullptr, hL, wbuf, acc, lane, g)
 
-template <int NT>
-__global__ __launch_bounds__(256, 2) void k_siren_step(SirenArgs a) {
+// CODED: layer 0's bias is row code_of[idx] of the per-code table a.code_bias (SirenCodedArgs) instead of the image's
+// bias slot; the expression is the same, so a coded evaluation equals the uncoded one of the network whose b0 is that row
+template <int NT, bool CODED>
+__global__ __launch_bounds__(256, 2) void k_siren_step(typename SirenArgsOf<CODED>::type a) {
   constexpr int H = NT * 16;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x;
@@ -120,10 +122,16 @@ __global__ __launch_bounds__(256, 2) void k_siren_step(SirenArgs a) {
     const bool valid = slot < count;
     int64_t idx = -1;
     float px = 0.f, py = 0.f, pz = 0.f;
+    int row = 0;
     if (valid) {
       idx = a.idx_in ? (int64_t)a.idx_in[slot] : slot;
       px = a.pts[idx * 3]; py = a.pts[idx * 3 + 1]; pz = a.pts[idx * 3 + 2];
+      if constexpr (CODED) row = a.code_of ? a.code_of[idx] : 0;
     }
+    // this lane's 4 features 16 e4 + 4g .. +3 of the code's bias row: one 16-B load per e4
+    const f32x4* cb = nullptr;
+    if constexpr (CODED) cb = reinterpret_cast<const f32x4*>(a.code_bias + (int64_t)row * H) + g;
+    (void)cb;
     // ---- layer 0 (3 -> H) on the VALU -------------------------------------
     // The TOP sine layer needs no stash: its adjoint seed is the head weight, so
     // gs = WL * w cos(w z) is formed on the spot (and the head dot product with it).
@@ -131,10 +139,14 @@ __global__ __launch_bounds__(256, 2) void k_siren_step(SirenArgs a) {
     const bool top0 = (a.L == 0);
     for (int e4 = 0; e4 < NT; ++e4) {
       f32x4 h4, s4;
+      f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (CODED) b4 = cb[4 * e4];
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const f32x4 w = reinterpret_cast<const f32x4*>(W0img)[g * (H / 4) + e4 * 4 + i];
-        float z = ((w.x * px + w.y * py) + w.z * pz) + w.w;
+        float z;
+        if constexpr (CODED) z = ((w.x * px + w.y * py) + w.z * pz) + b4[i];
+        else z = ((w.x * px + w.y * py) + w.z * pz) + w.w;
         float s, c;
         iso_sincos(a.w0 * z, s, c);
         h4[i] = s;
@@ -236,24 +248,25 @@ constexpr int kSirenBlocks = 512;  // persistent: two workgroups per CU (80 KiB 
 
 inline int64_t stash_floats(int H, int L) { return (int64_t)kSirenBlocks * 4 * (L + 1) * H * 16; }
 
-template <int NT>
-int launch_step(const SirenArgs& a, int blocks, hipStream_t s) {
+template <int NT, bool CODED>
+int launch_step(const typename SirenArgsOf<CODED>::type& a, int blocks, hipStream_t s) {
   const size_t lds = (size_t)(5 * NT * 256) * sizeof(float);
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step<NT>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step<NT, CODED>),
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_done = true;
   }
-  hipLaunchKernelGGL(k_siren_step<NT>, dim3(blocks), dim3(256), lds, s, a);
+  hipLaunchKernelGGL((k_siren_step<NT, CODED>), dim3(blocks), dim3(256), lds, s, a);
   return 0;
 }
 
-int dispatch_step(const SirenArgs& a, int H, int blocks, hipStream_t s) {
+template <bool CODED>
+int dispatch_step(const typename SirenArgsOf<CODED>::type& a, int H, int blocks, hipStream_t s) {
   switch (H / 16) {
-    case 4: return launch_step<4>(a, blocks, s);
-    case 8: return launch_step<8>(a, blocks, s);
-    case 16: return launch_step<16>(a, blocks, s);
+    case 4: return launch_step<4, CODED>(a, blocks, s);
+    case 8: return launch_step<8, CODED>(a, blocks, s);
+    case 16: return launch_step<16, CODED>(a, blocks, s);
     default: return -1;
   }
 }
@@ -285,11 +298,11 @@ int64_t stash_floats_any(int H, int L) {
   return a > b ? a : b;
 }
 
-int run_step(const SirenArgs& a, int H, int64_t n, hipStream_t s) {
+int run_step(const SirenCodedArgs& a, int H, int64_t n, hipStream_t s) {
   if (use_x3(H, a.L)) return siren_x3_launch(a, H, n, s);
   int64_t tiles = (n + 63) / 64;
   int blocks = (int)(tiles < kSirenBlocks ? tiles : kSirenBlocks);
-  return dispatch_step(a, H, blocks, s);
+  return a.code_bias ? dispatch_step<true>(a, H, blocks, s) : dispatch_step<false>(a, H, blocks, s);
 }
 
 }  // namespace
@@ -358,7 +371,7 @@ extern "C" int iso_siren_set_drawn_tiles(int on) {
 // One evaluation of a list whose length only the device knows: for the H = 256 gradient kernels the list is cut at
 // siren_split_point into 96-point and 32-point tiles, both served by one launch of k_siren_step_x3_both (per-point
 // results do not depend on the tile shape); everything else is one launch of one shape.
-static int run_step_split(SirenArgs a, int hidden, int64_t n, hipStream_t s) {
+static int run_step_split(SirenCodedArgs a, int hidden, int64_t n, hipStream_t s) {
   if (hidden == 256 && !a.fwd_only && use_x3(hidden, a.L)) {
     a.split = 3;
     return run_step(a, hidden, n, s);
@@ -400,7 +413,7 @@ __global__ void k_zero_tail(int32_t* c, int n, int32_t* tc, int m) {
 
 // The iteration driver shared by the Newton projection and sphere tracing: launch `it` evaluates
 // the list launch it-1 left (device-side counts, no host read), the last one does not move.
-static int run_iterations(SirenArgs a, int hidden, int64_t n, int max_iters, void* workspace,
+static int run_iterations(SirenCodedArgs a, int hidden, int64_t n, int max_iters, void* workspace,
                           hipStream_t s, const char* who) {
   float* stash = (float*)workspace;
   int32_t* idxA = (int32_t*)(stash + stash_floats_any(hidden, a.L));
@@ -435,11 +448,49 @@ static int run_iterations(SirenArgs a, int hidden, int64_t n, int max_iters, voi
   return ISO_OK;
 }
 
-extern "C" int iso_project_siren(const float* pts_in, float* pts_out, float* normals_out,
-                                 uint8_t* mask_out, int64_t n, const float* packed,
-                                 int hidden, int n_hidden, float omega_first,
-                                 float omega_hidden, int max_iters, float tol,
-                                 void* workspace, int64_t workspace_bytes, void* stream) {
+// ---- latent-conditioned SIREN: the per-code bias table of layer 0 ------------------------------
+// The reference concatenates the code in front of the point (DSS/models/common.py:150-152), so layer 0 of code u is
+// sin(w0 (W0[:, C:] x + b_u)) with b_u = b0 + W0[:, :C] c_u: the code only moves layer 0's bias.
+// table[u * Hp + f] = b0[f] + sum_k W0c[f][k] c_u[k], accumulated in double in ONE fixed order (b0, then k = 0, 1, .. by
+// fma; products of two floats are exact in double) and rounded once to f32; the padded features f >= H get 0.
+__global__ void k_siren_fold_codes(const float* __restrict__ w0c, const float* __restrict__ b0,
+                                   const float* __restrict__ codes, float* __restrict__ table, int H, int Hp, int C,
+                                   int64_t U) {
+  const int64_t total = U * Hp;
+  for (int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; o < total; o += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t u = o / Hp;
+    const int f = (int)(o - u * Hp);
+    float v = 0.f;
+    if (f < H) {
+      double acc = (double)b0[f];
+      const float* wr = w0c + (int64_t)f * C;
+      const float* cu = codes + u * C;
+      for (int k = 0; k < C; ++k) acc = fma((double)wr[k], (double)cu[k], acc);
+      v = (float)acc;
+    }
+    table[o] = v;
+  }
+}
+
+extern "C" int iso_siren_fold_codes(const float* w0c, const float* b0, const float* codes, float* table, int hidden,
+                                    int padded_hidden, int c_dim, int64_t n_codes, void* stream) {
+  ISO_REQUIRE(hidden >= 1 && padded_hidden >= hidden && c_dim >= 1 && n_codes >= 0, ISO_ERR_INVALID,
+              "iso_siren_fold_codes: bad sizes (hidden %d, padded %d, c_dim %d, codes %lld)", hidden, padded_hidden,
+              c_dim, (long long)n_codes);
+  if (n_codes == 0) return ISO_OK;
+  ISO_REQUIRE(w0c && b0 && codes && table, ISO_ERR_INVALID, "iso_siren_fold_codes: null pointer");
+  const int64_t total = n_codes * padded_hidden;
+  hipLaunchKernelGGL(k_siren_fold_codes, dim3(iso_stream_grid(total, 256)), dim3(256), 0, (hipStream_t)stream, w0c, b0,
+                     codes, table, hidden, padded_hidden, c_dim, n_codes);
+  ISO_CHECK_LAUNCH("iso_siren_fold_codes");
+  return ISO_OK;
+}
+
+// code_bias / code_of as SirenCodedArgs documents them; null code_bias: the uncoded network (the image's own b0)
+static int project_siren(const float* pts_in, float* pts_out, float* normals_out, uint8_t* mask_out, int64_t n,
+                         const float* packed, int hidden, int n_hidden, float omega_first, float omega_hidden,
+                         int max_iters, float tol, void* workspace, int64_t workspace_bytes, void* stream,
+                         const float* code_bias, const int32_t* code_of) {
   ISO_REQUIRE(siren_shape_ok(hidden, n_hidden), ISO_ERR_UNSUPPORTED,
               "iso_project_siren: hidden must be 64/128/256 and 0<=n_hidden<=8 (got %d, %d)",
               hidden, n_hidden);
@@ -454,21 +505,42 @@ extern "C" int iso_project_siren(const float* pts_in, float* pts_out, float* nor
   hipStream_t s = (hipStream_t)stream;
   if (pts_out != pts_in)
     (void)hipMemcpyAsync(pts_out, pts_in, (size_t)n * 12, hipMemcpyDeviceToDevice, s);
-  SirenArgs a;
+  SirenCodedArgs a;
   a.pts = pts_out; a.normals = normals_out; a.mask = mask_out;
   a.packed = packed; a.L = n_hidden;
   a.w0 = omega_first; a.wh = omega_hidden; a.tol = tol;
+  a.code_bias = code_bias; a.code_of = code_of;
   int rc = run_iterations(a, hidden, n, max_iters, workspace, s, "iso_project_siren");
   if (rc != ISO_OK) return rc;
   ISO_CHECK_LAUNCH("iso_project_siren");
   return ISO_OK;
 }
 
-extern "C" int iso_trace_siren(const float* ray0, const float* dirs, float* pts_out, float* sdf_out,
-                               uint8_t* mask_out, int64_t n, const float* packed, int hidden,
-                               int n_hidden, float omega_first, float omega_hidden, float alpha,
-                               float bound, int max_iters, float tol, void* workspace,
-                               int64_t workspace_bytes, void* stream) {
+extern "C" int iso_project_siren(const float* pts_in, float* pts_out, float* normals_out,
+                                 uint8_t* mask_out, int64_t n, const float* packed,
+                                 int hidden, int n_hidden, float omega_first,
+                                 float omega_hidden, int max_iters, float tol,
+                                 void* workspace, int64_t workspace_bytes, void* stream) {
+  return project_siren(pts_in, pts_out, normals_out, mask_out, n, packed, hidden, n_hidden, omega_first, omega_hidden,
+                       max_iters, tol, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+extern "C" int iso_project_siren_coded(const float* pts_in, float* pts_out, float* normals_out,
+                                       uint8_t* mask_out, int64_t n, const float* packed,
+                                       int hidden, int n_hidden, float omega_first,
+                                       float omega_hidden, int max_iters, float tol,
+                                       void* workspace, int64_t workspace_bytes, void* stream,
+                                       const float* code_bias, const int32_t* code_of, int64_t n_codes) {
+  ISO_REQUIRE(code_bias && n_codes >= 1 && (code_of || n_codes == 1), ISO_ERR_INVALID,
+              "iso_project_siren_coded: needs a bias table of n_codes >= 1 rows (and code_of when n_codes > 1)");
+  return project_siren(pts_in, pts_out, normals_out, mask_out, n, packed, hidden, n_hidden, omega_first, omega_hidden,
+                       max_iters, tol, workspace, workspace_bytes, stream, code_bias, code_of);
+}
+
+static int trace_siren(const float* ray0, const float* dirs, float* pts_out, float* sdf_out, uint8_t* mask_out,
+                       int64_t n, const float* packed, int hidden, int n_hidden, float omega_first, float omega_hidden,
+                       float alpha, float bound, int max_iters, float tol, void* workspace, int64_t workspace_bytes,
+                       void* stream, const float* code_bias, const int32_t* code_of) {
   ISO_REQUIRE(siren_shape_ok(hidden, n_hidden), ISO_ERR_UNSUPPORTED,
               "iso_trace_siren: hidden must be 64/128/256 and 0<=n_hidden<=8 (got %d, %d)",
               hidden, n_hidden);
@@ -483,7 +555,7 @@ extern "C" int iso_trace_siren(const float* ray0, const float* dirs, float* pts_
   hipStream_t s = (hipStream_t)stream;
   if (pts_out != ray0)
     (void)hipMemcpyAsync(pts_out, ray0, (size_t)n * 12, hipMemcpyDeviceToDevice, s);
-  SirenArgs a;
+  SirenCodedArgs a;
   a.pts = pts_out; a.normals = nullptr; a.mask = mask_out; a.sdf_out = sdf_out;
   a.packed = packed; a.L = n_hidden;
   a.w0 = omega_first; a.wh = omega_hidden;
@@ -491,16 +563,37 @@ extern "C" int iso_trace_siren(const float* ray0, const float* dirs, float* pts_
   a.tol = 0.1f * tol;                  // levelset_sampling.py:764: still active above 1e-1 * tolerance
   a.tol_valid = tol;                   // :790: valid projection = |sdf| <= tolerance
   a.fwd_only = 1;
+  a.code_bias = code_bias; a.code_of = code_of;
   int rc = run_iterations(a, hidden, n, max_iters, workspace, s, "iso_trace_siren");
   if (rc != ISO_OK) return rc;
   ISO_CHECK_LAUNCH("iso_trace_siren");
   return ISO_OK;
 }
 
-extern "C" int iso_siren_sdf_grad(const float* pts, float* sdf_out, float* grad_out,
-                                  int64_t n, const float* packed, int hidden,
-                                  int n_hidden, float omega_first, float omega_hidden,
-                                  void* workspace, int64_t workspace_bytes, void* stream) {
+extern "C" int iso_trace_siren(const float* ray0, const float* dirs, float* pts_out, float* sdf_out,
+                               uint8_t* mask_out, int64_t n, const float* packed, int hidden,
+                               int n_hidden, float omega_first, float omega_hidden, float alpha,
+                               float bound, int max_iters, float tol, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  return trace_siren(ray0, dirs, pts_out, sdf_out, mask_out, n, packed, hidden, n_hidden, omega_first, omega_hidden,
+                     alpha, bound, max_iters, tol, workspace, workspace_bytes, stream, nullptr, nullptr);
+}
+
+extern "C" int iso_trace_siren_coded(const float* ray0, const float* dirs, float* pts_out, float* sdf_out,
+                                     uint8_t* mask_out, int64_t n, const float* packed, int hidden,
+                                     int n_hidden, float omega_first, float omega_hidden, float alpha,
+                                     float bound, int max_iters, float tol, void* workspace,
+                                     int64_t workspace_bytes, void* stream,
+                                     const float* code_bias, const int32_t* code_of, int64_t n_codes) {
+  ISO_REQUIRE(code_bias && n_codes >= 1 && (code_of || n_codes == 1), ISO_ERR_INVALID,
+              "iso_trace_siren_coded: needs a bias table of n_codes >= 1 rows (and code_of when n_codes > 1)");
+  return trace_siren(ray0, dirs, pts_out, sdf_out, mask_out, n, packed, hidden, n_hidden, omega_first, omega_hidden,
+                     alpha, bound, max_iters, tol, workspace, workspace_bytes, stream, code_bias, code_of);
+}
+
+static int siren_sdf_grad(const float* pts, float* sdf_out, float* grad_out, int64_t n, const float* packed,
+                          int hidden, int n_hidden, float omega_first, float omega_hidden, void* workspace,
+                          int64_t workspace_bytes, void* stream, const float* code_bias, const int32_t* code_of) {
   ISO_REQUIRE(siren_shape_ok(hidden, n_hidden), ISO_ERR_UNSUPPORTED,
               "iso_siren_sdf_grad: hidden must be 64/128/256 and 0<=n_hidden<=8 (got %d, %d)",
               hidden, n_hidden);
@@ -511,13 +604,14 @@ extern "C" int iso_siren_sdf_grad(const float* pts, float* sdf_out, float* grad_
               "iso_siren_sdf_grad: null pointer");
   ISO_REQUIRE(workspace_bytes >= stash_floats_any(hidden, n_hidden) * 4, ISO_ERR_WORKSPACE,
               "iso_siren_sdf_grad: workspace too small");
-  SirenArgs a;
+  SirenCodedArgs a;
   a.pts = const_cast<float*>(pts); a.normals = nullptr; a.mask = nullptr;
   a.sdf_out = sdf_out; a.grad_out = grad_out;
   a.idx_in = nullptr; a.count_in = nullptr; a.idx_out = nullptr; a.count_out = nullptr;
   a.packed = packed; a.stash = (float*)workspace; a.n = n; a.L = n_hidden;
   a.w0 = omega_first; a.wh = omega_hidden; a.tol = 0.f; a.do_move = 0; a.eval_only = 1;
   a.fwd_only = grad_out ? 0 : 1;       // value only: forward sweep only where the kernel has one
+  a.code_bias = code_bias; a.code_of = code_of;
   // a workspace of the projection's size (what the Python side allocates) has room for the two tile counters
   if (hidden == 256 && !a.fwd_only && siren_dynamic_tiles_enabled() &&
       workspace_bytes >= iso_project_siren_workspace_bytes(n, hidden, n_hidden)) {
@@ -529,4 +623,23 @@ extern "C" int iso_siren_sdf_grad(const float* pts, float* sdf_out, float* grad_
               "iso_siren_sdf_grad: unsupported hidden size %d", hidden);
   ISO_CHECK_LAUNCH("iso_siren_sdf_grad");
   return ISO_OK;
+}
+
+extern "C" int iso_siren_sdf_grad(const float* pts, float* sdf_out, float* grad_out,
+                                  int64_t n, const float* packed, int hidden,
+                                  int n_hidden, float omega_first, float omega_hidden,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  return siren_sdf_grad(pts, sdf_out, grad_out, n, packed, hidden, n_hidden, omega_first, omega_hidden, workspace,
+                        workspace_bytes, stream, nullptr, nullptr);
+}
+
+extern "C" int iso_siren_sdf_grad_coded(const float* pts, float* sdf_out, float* grad_out,
+                                        int64_t n, const float* packed, int hidden,
+                                        int n_hidden, float omega_first, float omega_hidden,
+                                        void* workspace, int64_t workspace_bytes, void* stream,
+                                        const float* code_bias, const int32_t* code_of, int64_t n_codes) {
+  ISO_REQUIRE(code_bias && n_codes >= 1 && (code_of || n_codes == 1), ISO_ERR_INVALID,
+              "iso_siren_sdf_grad_coded: needs a bias table of n_codes >= 1 rows (and code_of when n_codes > 1)");
+  return siren_sdf_grad(pts, sdf_out, grad_out, n, packed, hidden, n_hidden, omega_first, omega_hidden, workspace,
+                        workspace_bytes, stream, code_bias, code_of);
 }

@@ -47,6 +47,18 @@ struct SirenArgs {
   int ps_guard = 0;          // always 0 here; kept for the layout and for x3_step_body's machine code (siren_ps_takes)
 };
 
+// Argument block of the CODED step kernels (latent-conditioned SIREN, iso_*_siren_coded): SirenArgs with two fields at
+// its end.  Layer 0's bias comes from a per-code table (iso_siren_fold_codes, [n_codes][H] in natural feature order)
+// instead of the W0 image's bias slot; point i uses row code_of[i] (null: row 0 for every point).  The uncoded kernels
+// keep SirenArgs itself: a larger argument block moves the runtime's hidden arguments behind it, and with them the
+// machine code of those kernels.  The host side carries this type throughout (code_bias null: uncoded).
+struct SirenCodedArgs : SirenArgs {
+  const float* code_bias = nullptr;
+  const int32_t* code_of = nullptr;
+};
+template <bool CODED> struct SirenArgsOf { using type = SirenArgs; };
+template <> struct SirenArgsOf<true> { using type = SirenCodedArgs; };
+
 // Slots served by the 96-point-tile launch of a split list.  A round of the persistent grid is 256 tiles: 24 576
 // points in 71 us (96-point tiles) or 8 192 points in 25 us (32-point tiles); the remainder after the full rounds goes
 // to the small tiles when it fits two of their rounds, else it gets one more round of the large ones.
@@ -101,9 +113,9 @@ __host__ __device__ inline int64_t siren_packed_total(int H, int L) { return x16
 bool siren_x3_supported(int H, int L);
 int64_t siren_x3_stash_floats(int H, int L);
 void siren_x3_pack(const float* raw, float* packed, int H, int L, hipStream_t s);
-int siren_x3_launch(const SirenArgs& a, int H, int64_t n_upper, hipStream_t s);
-int siren_x3_tail_blocks();                                          // workgroups of the Newton-tail launch
-int siren_x3_launch_tail(const SirenArgs& a, int H, hipStream_t s);  // H = 256 only
+int siren_x3_launch(const SirenCodedArgs& a, int H, int64_t n_upper, hipStream_t s);
+int siren_x3_tail_blocks();                                               // workgroups of the Newton-tail launch
+int siren_x3_launch_tail(const SirenCodedArgs& a, int H, hipStream_t s);  // H = 256 only
 // ---- the point-stationary form of the H = 256 step (tools/experiments/siren_ps, not part of this library) -------
 // x3_step_body keeps its ps_guard check on this predicate (never true here: ps_guard is 0), because removing the check
 // changes that kernel's machine code.  Which lists the experiment served (decided on the device by both kernels from the

@@ -192,11 +192,25 @@ struct X3Shape {
   static_assert(NTO % NW == 0 && TW >= 1, "features must split evenly over the waves");
 };
 
+// the layer-0 biases of K-step s for lane half h (features x3_feat(s, 8h + e), e = 0..7: 16 s + 8 (e >> 2) + 4h + (e & 3))
+// from row `row` of the per-code table: two aligned 16-B loads
+template <int H>
+__device__ __forceinline__ void x3_code_bias8(const float* table, int row, int s, int h, float (&b)[8]) {
+  const f32x4* t = reinterpret_cast<const f32x4*>(table + (int64_t)row * H + 16 * s + 4 * h);
+  const f32x4 lo = t[0], hi = t[2];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { b[e] = lo[e]; b[4 + e] = hi[e]; }
+}
+
 // FWD: value only (iso_siren_sdf, sphere tracing) -- no stash, no reverse sweep, no w cos(w z)
 // bid / nblk: this workgroup's index among the nblk workgroups that share the list (the kernels below)
 // sid: index of the workgroup's stash region (= bid unless the caller runs private lists, see k_siren_tail_x3)
-template <int H, int NW, int NB, bool FWD>
-__device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, const int nblk, const int sid) {
+// CODED: layer 0's bias is row code_of[idx] of the per-code table a.code_bias (SirenCodedArgs, natural feature order) instead of
+// the .w slot of the W0 image, in the forward sweep and where reverse stage 0 forms z0 again; the expression is the same,
+// so a coded evaluation equals the uncoded one of the network whose b0 is that row, bit for bit
+template <int H, int NW, int NB, bool FWD, bool CODED>
+__device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::type& a, const int bid, const int nblk,
+                                             const int sid) {
   using S = X3Shape<H, NW, NB>;
   constexpr int NS = S::NS, NTO = S::NTO, TW = S::TW, SL = S::SL, NG = S::NG, P = S::P;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -271,6 +285,7 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
   __shared__ int s_next_tile, s_first_tile;
   int nidx[NB];
   float npx[NB], npy[NB], npz[NB];
+  int nrow[NB];                                          // CODED: the points' rows of the bias table
   auto fetch_idx = [&](int64_t t) {                      // list entries of tile t (-1: beyond the list)
     int j_e = j;
     asm volatile("" : "+v"(j_e));
@@ -285,9 +300,11 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
       npx[n] = npy[n] = npz[n] = 0.f;
+      if constexpr (CODED) nrow[n] = 0;
       if (nidx[n] >= 0) {
         const int64_t idx = nidx[n];
         npx[n] = a.pts[idx * 3]; npy[n] = a.pts[idx * 3 + 1]; npz[n] = a.pts[idx * 3 + 2];
+        if constexpr (CODED) nrow[n] = a.code_of ? a.code_of[idx] : 0;
       }
     }
   };
@@ -309,13 +326,19 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
   int64_t next_tile = 0;
   for (int64_t tile = first_tile; tile < n_tiles; tile = next_tile) {
     float px[NB], py[NB], pz[NB];
+    int row[NB];
     int j_e = j;
     asm volatile("" : "+v"(j_e));
 #pragma unroll
     for (int n = 0; n < NB; ++n) {
       px[n] = npx[n]; py[n] = npy[n]; pz[n] = npz[n];
+      if constexpr (CODED) row[n] = nrow[n];
       if constexpr (!FWD) {                // kept for the reverse sweep's layer 0 (visible after the barrier below)
-        if (w == 0 && h == 0) ptl[32 * n + j_e] = (f32x4){px[n], py[n], pz[n], 0.f};
+        if constexpr (CODED) {             // (the table row rides in the free 4th component)
+          if (w == 0 && h == 0) ptl[32 * n + j_e] = (f32x4){px[n], py[n], pz[n], __int_as_float(row[n])};
+        } else {
+          if (w == 0 && h == 0) ptl[32 * n + j_e] = (f32x4){px[n], py[n], pz[n], 0.f};
+        }
       }
     }
     // ---- layer 0 (3 -> H) on the VALU: this wave's H/NW features of all P points ------------
@@ -326,8 +349,15 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
 #pragma unroll
       for (int n = 0; n < NB; ++n) {
         float zz[8], hv[8], sv[8];
+        if constexpr (CODED) {
+          float bz[8];
+          x3_code_bias8<H>(a.code_bias, row[n], SL * w + sl, h, bz);
 #pragma unroll
-        for (int e = 0; e < 8; ++e) zz[e] = ((wv[e].x * px[n] + wv[e].y * py[n]) + wv[e].z * pz[n]) + wv[e].w;
+          for (int e = 0; e < 8; ++e) zz[e] = ((wv[e].x * px[n] + wv[e].y * py[n]) + wv[e].z * pz[n]) + bz[e];
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) zz[e] = ((wv[e].x * px[n] + wv[e].y * py[n]) + wv[e].z * pz[n]) + wv[e].w;
+        }
         x3_sin_wcos8(a.w0, a.w0, zz, hv, sv);
         const int k = sl * NB + n;
         {
@@ -555,8 +585,15 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
 #pragma unroll
           for (int n = 0; n < NB; ++n) {
             float zz[8], cv[8];
+            if constexpr (CODED) {
+              float bz[8];
+              x3_code_bias8<H>(a.code_bias, __float_as_int(q[n].w), SL * w + 2 * t + p, h, bz);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) zz[e] = ((wv[e].x * q[n].x + wv[e].y * q[n].y) + wv[e].z * q[n].z) + wv[e].w;
+              for (int e = 0; e < 8; ++e) zz[e] = ((wv[e].x * q[n].x + wv[e].y * q[n].y) + wv[e].z * q[n].z) + bz[e];
+            } else {
+#pragma unroll
+              for (int e = 0; e < 8; ++e) zz[e] = ((wv[e].x * q[n].x + wv[e].y * q[n].y) + wv[e].z * q[n].z) + wv[e].w;
+            }
             iso_wcos8(a.w0, a.w0, zz, cv);
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
@@ -633,9 +670,9 @@ __device__ __forceinline__ void x3_step_body(const SirenArgs& a, const int bid, 
   }
 }
 
-template <int H, int NW, int NB, int MINB, bool FWD>
-__global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3(SirenArgs a) {
-  x3_step_body<H, NW, NB, FWD>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
+template <int H, int NW, int NB, int MINB, bool FWD, bool CODED>
+__global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3(typename SirenArgsOf<CODED>::type a) {
+  x3_step_body<H, NW, NB, FWD, CODED>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
 }
 
 // Both tile shapes of a split list (SirenArgs::split) in ONE launch: workgroups [0, big_blocks) serve the slots below
@@ -643,14 +680,14 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3(SirenArgs a) {
 // behind the first group's).  The dispatcher places workgroups in index order, one per CU, so the small tiles start
 // on the CUs that finish their large ones first; a launch that finds nothing to do for one of the shapes costs nothing
 // (issued separately, the idle one of the two launches took ~4.4 us, 15 times per headline cycle).
-template <int H, int NW, int NB, int MINB>
-__global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(SirenArgs a) {
+template <int H, int NW, int NB, int MINB, bool CODED>
+__global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(typename SirenArgsOf<CODED>::type a) {
   const bool big = (int)blockIdx.x < a.big_blocks;
   const int small_blocks = (int)gridDim.x - a.big_blocks;
   if (big) {
-    SirenArgs b = a;
+    typename SirenArgsOf<CODED>::type b = a;
     b.split = 1;
-    x3_step_body<H, NW, NB, false>(b, (int)blockIdx.x, a.big_blocks, (int)blockIdx.x);
+    x3_step_body<H, NW, NB, false, CODED>(b, (int)blockIdx.x, a.big_blocks, (int)blockIdx.x);
   }
   // Drawn tiles (a.tile_ctr): a workgroup of the large shape that finds no large tile left goes on with the small ones
   // (its own stash region, participant small_blocks + blockIdx of small_blocks + big_blocks) -- the large workgroups end
@@ -659,7 +696,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(SirenArgs 
   // handed to the small ones on top: 13.26-13.28).
   if (!big || a.tile_ctr != nullptr) {
     if (big) __syncthreads();              // (the last large tile's epilogue reads LDS the other shape lays out differently)
-    SirenArgs b = a;
+    typename SirenArgsOf<CODED>::type b = a;
     b.split = 2;
     if (a.tile_ctr) b.tile_ctr = a.tile_ctr + 1;
     const bool joint = a.tile_ctr != nullptr;
@@ -668,7 +705,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(SirenArgs 
     const int nblk = joint ? small_blocks + a.big_blocks : small_blocks;
     if (big) b.stash = a.stash + (int64_t)blockIdx.x * X3Shape<H, NW, NB>::kStashPerWg(a.L);
     else b.stash = a.stash + (int64_t)a.big_blocks * X3Shape<H, NW, NB>::kStashPerWg(a.L);
-    x3_step_body<H, NW, 1, false>(b, bid, nblk, big ? 0 : bid);
+    x3_step_body<H, NW, 1, false, CODED>(b, bid, nblk, big ? 0 : bid);
   }
 }
 
@@ -679,17 +716,17 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(SirenArgs 
 // until none is left or iteration it_last (the evaluation without a move) is done.  A point's result does not depend
 // on the tile it sits in, so the results are those of the launch-per-iteration form, bit for bit.  Between two rounds
 // one workgroup barrier (the epilogue's atomics and list entries of the slower waves must have landed).
-template <int H, int NW, int MINB>
-__global__ __launch_bounds__(64 * NW, MINB) void k_siren_tail_x3(SirenArgs a) {
+template <int H, int NW, int MINB, bool CODED>
+__global__ __launch_bounds__(64 * NW, MINB) void k_siren_tail_x3(typename SirenArgsOf<CODED>::type a) {
   const int b = blockIdx.x, nblk = gridDim.x;
   int32_t* lists = a.tail_lists + (int64_t)b * 2 * a.tail_cap;
   int32_t* cnts = a.tail_counts + b * 2;
-  SirenArgs r = a;
+  typename SirenArgsOf<CODED>::type r = a;
   r.split = 0; r.small_tiles = 1; r.cnt_lo = -1; r.cnt_hi = INT64_MAX; r.tile_ctr = nullptr;
   // round 0: this workgroup's tiles of the global list
   r.idx_out = lists; r.count_out = cnts;
   r.do_move = a.it_first < a.it_last ? 1 : 0;
-  x3_step_body<H, NW, 1, false>(r, b, nblk, b);
+  x3_step_body<H, NW, 1, false, CODED>(r, b, nblk, b);
   int cur = 0;
   for (int it = a.it_first + 1; it <= a.it_last; ++it) {
     __syncthreads();
@@ -703,7 +740,7 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_tail_x3(SirenArgs a) {
     r.idx_in = lists + (int64_t)cur * a.tail_cap; r.count_in = cnts + cur;
     r.idx_out = lists + (int64_t)(cur ^ 1) * a.tail_cap; r.count_out = cnts + (cur ^ 1);
     r.do_move = it < a.it_last ? 1 : 0;
-    x3_step_body<H, NW, 1, false>(r, 0, 1, b);
+    x3_step_body<H, NW, 1, false, CODED>(r, 0, 1, b);
     cur ^= 1;
   }
   // leave the private counters at zero for the next launch on this workspace
@@ -711,30 +748,30 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_tail_x3(SirenArgs a) {
   if (threadIdx.x == 0) { cnts[0] = 0; cnts[1] = 0; }
 }
 
-template <int H, int NW, int NB, int MINB, bool FWD>
-int launch_x3(const SirenArgs& a, int64_t n_upper, hipStream_t s) {
+template <int H, int NW, int NB, int MINB, bool FWD, bool CODED>
+int launch_x3(const typename SirenArgsOf<CODED>::type& a, int64_t n_upper, hipStream_t s) {
   using S = X3Shape<H, NW, NB>;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step_x3<H, NW, NB, MINB, FWD>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::kLds);
     attr_done = true;
   }
   const int64_t tiles = (n_upper + S::P - 1) / S::P;
   const int64_t cap = 256 * MINB;
   const int blocks = (int)(tiles < cap ? (tiles < 1 ? 1 : tiles) : cap);
-  hipLaunchKernelGGL((k_siren_step_x3<H, NW, NB, MINB, FWD>), dim3(blocks), dim3(64 * NW), S::kLds, s, a);
+  hipLaunchKernelGGL((k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>), dim3(blocks), dim3(64 * NW), S::kLds, s, a);
   return 0;
 }
 
-template <int H, int NW, int NB, int MINB>
-int launch_x3_both(SirenArgs a, int64_t n_upper, hipStream_t s) {
+template <int H, int NW, int NB, int MINB, bool CODED>
+int launch_x3_both(typename SirenArgsOf<CODED>::type a, int64_t n_upper, hipStream_t s) {
   using SB = X3Shape<H, NW, NB>;
   using SS = X3Shape<H, NW, 1>;
   constexpr size_t lds = SB::kLds > SS::kLds ? SB::kLds : SS::kLds;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step_x3_both<H, NW, NB, MINB>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step_x3_both<H, NW, NB, MINB, CODED>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_done = true;
   }
@@ -742,7 +779,7 @@ int launch_x3_both(SirenArgs a, int64_t n_upper, hipStream_t s) {
   const int64_t tb = (n_upper + SB::P - 1) / SB::P, ts = (n_upper + SS::P - 1) / SS::P;
   a.big_blocks = (int)(tb < cap ? (tb < 1 ? 1 : tb) : cap);
   const int small_blocks = (int)(ts < cap ? (ts < 1 ? 1 : ts) : cap);
-  hipLaunchKernelGGL((k_siren_step_x3_both<H, NW, NB, MINB>), dim3(a.big_blocks + small_blocks), dim3(64 * NW), lds, s, a);
+  hipLaunchKernelGGL((k_siren_step_x3_both<H, NW, NB, MINB, CODED>), dim3(a.big_blocks + small_blocks), dim3(64 * NW), lds, s, a);
   return 0;
 }
 
@@ -775,26 +812,40 @@ void siren_x3_pack(const float* raw, float* packed, int H, int L, hipStream_t s)
 
 int siren_x3_tail_blocks() { return 256 * kMinB256; }
 
-int siren_x3_launch_tail(const SirenArgs& a, int H, hipStream_t s) {
-  if (H != 256) return -1;
+template <bool CODED>
+static int launch_tail(const typename SirenArgsOf<CODED>::type& a, hipStream_t s) {
   using SS = X3Shape<256, kNW256, 1>;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_tail_x3<256, kNW256, kMinB256>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_tail_x3<256, kNW256, kMinB256, CODED>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)SS::kLds);
     attr_done = true;
   }
-  hipLaunchKernelGGL((k_siren_tail_x3<256, kNW256, kMinB256>), dim3(siren_x3_tail_blocks()), dim3(64 * kNW256), SS::kLds, s, a);
+  hipLaunchKernelGGL((k_siren_tail_x3<256, kNW256, kMinB256, CODED>), dim3(siren_x3_tail_blocks()), dim3(64 * kNW256), SS::kLds, s, a);
   return 0;
 }
 
-int siren_x3_launch(const SirenArgs& a, int H, int64_t n_upper, hipStream_t s) {
-  if (a.split == 3 && H == 256 && !a.fwd_only) return launch_x3_both<256, kNW256, kNB256, kMinB256>(a, n_upper, s);
+int siren_x3_launch_tail(const SirenCodedArgs& a, int H, hipStream_t s) {
+  if (H != 256) return -1;
+  return a.code_bias ? launch_tail<true>(a, s) : launch_tail<false>(a, s);     // (false: the SirenArgs part)
+}
+
+template <bool CODED>
+static int launch_any(const typename SirenArgsOf<CODED>::type& a, int H, int64_t n_upper, hipStream_t s) {
+  if (a.split == 3 && H == 256 && !a.fwd_only) return launch_x3_both<256, kNW256, kNB256, kMinB256, CODED>(a, n_upper, s);
   if (a.fwd_only) {
-    if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, true>(a, n_upper, s);
-    if (H == 128) return launch_x3<128, 4, 3, kMinB128, true>(a, n_upper, s);
+    if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, true, CODED>(a, n_upper, s);
+    if (H == 128) return launch_x3<128, 4, 3, kMinB128, true, CODED>(a, n_upper, s);
   }
-  if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, false>(a, n_upper, s);
-  if (H == 128) return launch_x3<128, 4, 3, kMinB128, false>(a, n_upper, s);
+  // (the H = 256 gradient kernel of one tile shape: only run_step_split's callers reach it, and they take the split
+  // launch above; the coded form is not built)
+  if constexpr (!CODED) {
+    if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, false, false>(a, n_upper, s);
+  }
+  if (H == 128) return launch_x3<128, 4, 3, kMinB128, false, CODED>(a, n_upper, s);
   return -1;
+}
+
+int siren_x3_launch(const SirenCodedArgs& a, int H, int64_t n_upper, hipStream_t s) {
+  return a.code_bias ? launch_any<true>(a, H, n_upper, s) : launch_any<false>(a, H, n_upper, s);
 }

@@ -24,7 +24,8 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import frnn
-from .sdf_models import FusedSdf, PackedIdr, PackedSiren, idr_spec, siren_spec
+from .sdf_models import (CodeRows, FusedSdf, PackedIdr, PackedSiren, code_rows, coded_siren_spec, idr_spec,
+                         siren_spec)
 
 ProjectionResult = namedtuple("ProjectionResult", ("points", "normals", "mask"))
 
@@ -141,6 +142,31 @@ class LevelSetProjection(object):
 _GENERIC_WARNED = set()
 
 
+def _fused_code(model, forward_kwargs, counts):
+    """The fused route of a latent-conditioned SIREN (sdf_models.coded_siren_spec): CodeRows when the only forward kwarg
+    is a code `c` of a shape code_rows takes (counts: points of each batch row), else None (the generic route).  Such a
+    model called without a code raises, as the reference's forward does."""
+    spec = coded_siren_spec(model)
+    if spec is None:
+        return None
+    c = forward_kwargs.get("c")
+    if c is None or (torch.is_tensor(c) and c.numel() == 0):
+        raise ValueError("iso_points_amd: %s is conditioned on a latent code (c_dim = %d): pass c"
+                         % (type(model).__name__, spec[3]))
+    if set(forward_kwargs) != {"c"}:
+        return None
+    return code_rows(c, spec[3], counts)
+
+
+def _leading_rows(shape):
+    """(rows, entries per row) of an (N, *, 3) tensor -- a 2-D (M, 3) one is ONE row"""
+    n = 1
+    for d in shape[:-1]:
+        n *= int(d)
+    rows = int(shape[0]) if len(shape) > 2 else 1
+    return rows, (n // rows if rows else 0)
+
+
 def _warn_generic_route(model, has_kwargs):
     """Once per model class: this network has no fused SDF kernel (SIREN 3 -> H <= 256 x <= 8 sine layers -> 1 and
     IDR-style 128 / 256 / 512 do), so the projection runs the reference's torch loop (model.forward + autograd per
@@ -197,6 +223,13 @@ class UniformProjection(LevelSetProjection):
             from .sdf_models import siren_sdf_and_grad
             sdf, grad = siren_sdf_and_grad(model, points_packed)
             return sdf.view(shp[:-1]), grad.view(shp)
+        if points_packed.is_cuda and "c" in forward_kwargs:
+            rows, per = _leading_rows(shp)
+            code = _fused_code(model, forward_kwargs, [per] * rows)
+            if code is not None:                      # c (the only kwarg) is taken by the fused route
+                from .sdf_models import siren_sdf_and_grad
+                sdf, grad = siren_sdf_and_grad(model, points_packed, code=code)
+                return sdf.view(shp[:-1]), grad.view(shp)
         if idr_spec(model) is not None and points_packed.is_cuda and not forward_kwargs:
             from .sdf_models import idr_sdf_and_grad
             sdf, grad = idr_sdf_and_grad(model, points_packed)
@@ -232,10 +265,12 @@ class UniformProjection(LevelSetProjection):
                 return False
         return _Scope()
 
-    def _project_packed(self, model, pts, proj_max_iters, proj_tolerance, follow=None, **forward_kwargs):
+    def _project_packed(self, model, pts, proj_max_iters, proj_tolerance, follow=None, code_counts=None,
+                        **forward_kwargs):
         """pts (n,3) f32 contiguous on the GPU -> points, normals, mask(bool).  follow: bricks.Follow -- side work of
         the launch for the next stages of the cycle (iso_follow); returns False in `follow.done` when this model's route
-        cannot do it (the caller then runs the stand-alone passes)."""
+        cannot do it (the caller then runs the stand-alone passes).  code_counts: points of each cloud in `pts` (None: one
+        cloud), for the code `c` of a latent-conditioned SIREN (one per cloud, or one for all)."""
         n = pts.shape[0]
         dev = pts.device
         out = torch.empty_like(pts)
@@ -263,7 +298,9 @@ class UniformProjection(LevelSetProjection):
             return out, normals, mask
         if follow is not None:
             follow.done = False
-        if siren_spec(model) is not None and not forward_kwargs:
+        code = _fused_code(model, forward_kwargs, code_counts if code_counts is not None else [n]) \
+            if "c" in forward_kwargs or coded_siren_spec(model) is not None else None
+        if (siren_spec(model) is not None and not forward_kwargs) or code is not None:
             # the packed weight image is re-used on the caller's word (reuse_packed), or INSIDE one call of an operator
             # of this class (project_points / resample run several projections on weights that cannot change in between:
             # _pack_scope); never across calls on the strength of (storage, version) alone -- in-place updates through
@@ -275,9 +312,14 @@ class UniformProjection(LevelSetProjection):
             ps._scope = self._pack_scope if self._pack_depth > 0 else None
             self._packed_for = model
             ws = ps.workspace(n)
-            _lib.call("iso_project_siren", p(pts), p(out), p(normals), p(mask), n, p(ps.packed),
-                      ps.hidden, ps.n_hidden, ps.omega_first, ps.omega_hidden, int(proj_max_iters),
-                      float(proj_tolerance), p(ws), ws.numel(), _lib.stream())
+            args = [p(pts), p(out), p(normals), p(mask), n, p(ps.packed), ps.hidden, ps.n_hidden, ps.omega_first,
+                    ps.omega_hidden, int(proj_max_iters), float(proj_tolerance), p(ws), ws.numel(), _lib.stream()]
+            if code is None:
+                _lib.call("iso_project_siren", *args)
+            else:                    # layer 0's bias per code (the image is the network of the xyz columns)
+                table = ps.fold(code.codes)
+                _lib.call("iso_project_siren_coded", *args, p(table), p(code.code_of), table.shape[0])
+                ps._table = (table, code.code_of)     # alive until the stream has used them
             self._packed_cache = ps  # keep the workspace alive until the stream has used it
             return out, normals, mask
         if idr_spec(model) is not None and not forward_kwargs:
@@ -329,6 +371,8 @@ class UniformProjection(LevelSetProjection):
             raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
         lens = host_lengths(num_points)
         packed = padded_to_packed(points.detach().float(), lens).contiguous()
+        if "c" in forward_kwargs:                     # (a code per cloud: the lengths say which points are whose)
+            forward_kwargs = dict(forward_kwargs, code_counts=lens)
         with torch.no_grad():
             pts, normals, valid = self._project_packed(model, packed, proj_max_iters, proj_tolerance, follow=follow,
                                                        **forward_kwargs)
@@ -678,7 +722,7 @@ class SphereTracing(LevelSetProjection):
         self.radius = radius
         self.padding = padding
 
-    def _trace_packed(self, model, ray0, dirs):
+    def _trace_packed(self, model, ray0, dirs, code=None):
         n, dev = ray0.shape[0], ray0.device
         out = torch.empty_like(ray0)
         sdf = torch.zeros((n,), dtype=torch.float32, device=dev)
@@ -686,7 +730,16 @@ class SphereTracing(LevelSetProjection):
         p = _lib.ptr
         bound = float(self.padding + self.radius)
         T, tol, alpha = int(self.proj_max_iters), float(self.proj_tolerance), float(self.alpha)
-        if getattr(model, "iso_analytic", None) == "sphere":
+        if code is not None:                             # latent-conditioned SIREN: layer 0's bias per code
+            ps = PackedSiren(model, dev)
+            ws = ps.workspace(n)
+            table = ps.fold(code.codes)
+            _lib.call("iso_trace_siren_coded", p(ray0), p(dirs), p(out), p(sdf), p(mask), n, p(ps.packed), ps.hidden,
+                      ps.n_hidden, ps.omega_first, ps.omega_hidden, alpha, bound, T, tol, p(ws), ws.numel(),
+                      _lib.stream(), p(table), p(code.code_of), table.shape[0])
+            ps._table = (table, code.code_of)
+            self._packed_cache = ps
+        elif getattr(model, "iso_analytic", None) == "sphere":
             c = [float(x) for x in model.center.tolist()]
             _lib.call("iso_trace_sphere", p(ray0), p(dirs), p(out), p(sdf), p(mask), n, c[0], c[1], c[2],
                       float(model.radius), alpha, bound, T, tol, _lib.stream())
@@ -737,9 +790,18 @@ class SphereTracing(LevelSetProjection):
     def project_points(self, ray0, ray_direction, model, latent=None, **forward_kwargs):
         """ray0, ray_direction (N,*,3) -> dict(levelset_points, network_eval_on_levelset_points,
         levelset_points_Dx, mask); `levelset_points_Dx` is the point tensor itself, as in the
-        reference (:806)."""
+        reference (:806).  latent: the code of a latent-conditioned SIREN (implicit_modeling.py:305,313), one per
+        leading row of ray0 ((N, C) / (N, 1, C), as _convert_batched_to_packed_args, :26-57) or one for all ((C,) /
+        (1, C))."""
+        code = None
         if latent is not None and latent.nelement() > 0:
-            raise NotImplementedError("iso_points_amd: latent-conditioned networks are outside the hot path (c_dim=0)")
+            rows, per = _leading_rows(ray0.shape)
+            code = _fused_code(model, {"c": latent}, [per] * rows) if not forward_kwargs else None
+            if code is None:
+                raise NotImplementedError("iso_points_amd: a latent code is taken by latent-conditioned SIRENs only, "
+                                          "one per leading row of ray0 or one for all rays")
+        elif coded_siren_spec(model) is not None:
+            _fused_code(model, {}, [])                   # (raises: the model needs its code)
         if not ray0.is_cuda:
             raise RuntimeError("iso_points_amd: rays must be on the GPU; there is no CPU path")
         shp = ray0.shape
@@ -750,7 +812,7 @@ class SphereTracing(LevelSetProjection):
                 pts, val, mask = self._trace_packed_generic(
                     _KwModel(model, forward_kwargs), r0, rd)
             else:
-                pts, val, mask = self._trace_packed(model, r0, rd)
+                pts, val, mask = self._trace_packed(model, r0, rd, code=code)
         pts = pts.view(shp)
         return {"levelset_points": pts,
                 "network_eval_on_levelset_points": val.view(shp[:-1]),
@@ -827,6 +889,8 @@ def run_Secant_method(f_start, f_end, d_start, d_end, n_secant_steps, p0, ray_di
     """levelset_sampling.py:1331-1367.  `decoder` is an nn.Module (a FusedSdf is built for it) or
     a FusedSdf; every step is one value-only evaluation of the fused kernel."""
     sdf = decoder if isinstance(decoder, FusedSdf) else FusedSdf(decoder, p0.device)
+    if c is not None:                                   # the code of pair j (FusedSdf: one per row of p0, or CodeRows)
+        forward_kwargs = dict(forward_kwargs, c=c)
     d_pred = -f_start * (d_end - d_start) / (f_end - f_start) + d_start
     for _ in range(n_secant_steps):
         p_mid = p0 + d_pred.unsqueeze(-1) * ray_direction
@@ -846,9 +910,17 @@ def find_zero_crossing_between_point_pairs(p0, p1, network, n_secant_steps=8, n_
     (levelset_sampling.py:1210-1328).  p0, p1 (N,*,3) -> pt_pred (N,*,3), mask (N,*).
     The n_steps proposals per pair are evaluated by the value-only fused kernel in one call
     (`max_points` chunking is unnecessary); no host synchronisation before the secant loop:
-    it runs over all pairs and the mask is applied at the end (the per-pair arithmetic is the same)."""
+    it runs over all pairs and the mask is applied at the end (the per-pair arithmetic is the same).
+    c: the code of a latent-conditioned SIREN (implicit_modeling.py:318-319), one per leading row of p0 ((N, C) /
+    (N, 1, C), as _convert_batched_to_packed_args) or one for all; the n_steps proposals of pair j use j's code."""
+    pair_code = None
     if c is not None and c.nelement() > 0:
-        raise NotImplementedError("iso_points_amd: latent-conditioned networks are outside the hot path (c_dim=0)")
+        rows, per = _leading_rows(p0.shape)
+        model = network.model if isinstance(network, FusedSdf) else network
+        pair_code = _fused_code(model, {"c": c}, [per] * rows) if not forward_kwargs else None
+        if pair_code is None:
+            raise NotImplementedError("iso_points_amd: a latent code is taken by latent-conditioned SIRENs only, "
+                                      "one per leading row of p0 or one for all pairs")
     if not p0.is_cuda:
         raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
     sdf = network if isinstance(network, FusedSdf) else FusedSdf(network, p0.device)
@@ -860,7 +932,11 @@ def find_zero_crossing_between_point_pairs(p0, p1, network, n_secant_steps=8, n_
     d_proposal = torch.linspace(0, 1, steps=n_steps, device=device).view(1, n_steps) * \
         torch.norm(p1 - p0, p=2, dim=-1).unsqueeze(-1)
     p_proposal = p0.unsqueeze(-2) + ray_direction.unsqueeze(-2) * d_proposal.unsqueeze(-1)
+    if pair_code is not None:                           # proposal k of pair j: j's table row
+        step_rows = None if pair_code.code_of is None else pair_code.code_of.repeat_interleave(n_steps)
+        forward_kwargs = dict(forward_kwargs, c=CodeRows(pair_code.codes, step_rows))
     val = sdf(p_proposal.reshape(-1, 3), **forward_kwargs).view(n_pts, n_steps)
+    forward_kwargs.pop("c", None)
     compare = (lambda d: d < 0.0) if is_occupancy else (lambda d: d > 0.0)
     sign_matrix = torch.cat([torch.sign(val[..., :-1] * val[..., 1:]),
                              torch.ones(n_pts, 1, device=device)], dim=-1)
@@ -873,7 +949,7 @@ def find_zero_crossing_between_point_pairs(p0, p1, network, n_secant_steps=8, n_
     d_start, f_start = d_proposal[rows, indices], val[rows, indices]
     nxt = torch.clamp(indices + 1, max=n_steps - 1)
     d_end, f_end = d_proposal[rows, nxt], val[rows, nxt]
-    p_pred = run_Secant_method(f_start, f_end, d_start, d_end, n_secant_steps, p0, ray_direction, sdf, None,
+    p_pred = run_Secant_method(f_start, f_end, d_start, d_end, n_secant_steps, p0, ray_direction, sdf, pair_code,
                                **forward_kwargs)
     pt_pred = torch.where(mask.unsqueeze(-1), p_pred, torch.ones_like(p_pred))
     return pt_pred.view(shp), mask.view(shp[:-1])

@@ -18,6 +18,9 @@ from . import _lib
 
 _fields = ("sdf", "latent", "rgb", "occupancy")
 NetOutput = namedtuple("Result", _fields, defaults=(None,) * len(_fields))
+# the codes of one call of a latent-conditioned SIREN as the kernels take them (code_rows): codes (U, C) f32 and the
+# table row of every point, code_of (n,) int32 -- None when U = 1 (one code for every point)
+CodeRows = namedtuple("CodeRows", ("codes", "code_of"))
 
 
 class SphereSDF(nn.Module):
@@ -55,18 +58,19 @@ class SineLayer(nn.Module):
 
 
 class Siren(nn.Module):
-    """common.py:90-165 restricted to what the hot path uses: sdf output, linear head,
-    no latent code (c_dim=0 as in test_dtu_points.py:216-227)."""
+    """common.py:90-165 restricted to what the hot path uses: sdf output, linear head.  c_dim > 0 (the reference's
+    default, config.py:163-166) conditions it on a latent code: the first sine layer is dim + c_dim wide and forward
+    concatenates [c, coords] (:150-152); the fused kernels fold the code into layer 0's bias (PackedSiren.fold)."""
 
     def __init__(self, dim=3, hidden_size=256, n_layers=3, out_dims=None, outermost_linear=True,
                  c_dim=0, first_omega_0=30, hidden_omega_0=30.0, activation=None, **kwargs):
         super().__init__()
         out_dims = out_dims or OrderedDict(sdf=1)
-        if c_dim != 0 or not outermost_linear or activation is not None or sum(out_dims.values()) != 1:
-            raise NotImplementedError("iso_points_amd.Siren covers the sdf-only, c_dim=0, linear-head "
+        if c_dim < 0 or not outermost_linear or activation is not None or sum(out_dims.values()) != 1:
+            raise NotImplementedError("iso_points_amd.Siren covers the sdf-only, linear-head "
                                       "configuration of the reference's Siren")
         self.dim, self.c_dim = dim, c_dim
-        net = [SineLayer(dim, hidden_size, is_first=True, omega_0=first_omega_0)]
+        net = [SineLayer(dim + c_dim, hidden_size, is_first=True, omega_0=first_omega_0)]
         for _ in range(n_layers):
             net.append(SineLayer(hidden_size, hidden_size, is_first=False, omega_0=hidden_omega_0))
         final = nn.Linear(hidden_size, 1)
@@ -77,7 +81,71 @@ class Siren(nn.Module):
         self.net = nn.Sequential(*net)
 
     def forward(self, coords, c=None, **kwargs):
+        if c is not None and c.numel() > 0:                 # common.py:150-152
+            assert coords.ndim == c.ndim
+            coords = torch.cat([c, coords], dim=-1)
         return NetOutput(sdf=self.net(coords))
+
+
+def coded_siren_spec(model):
+    """(lins, omega_first, omega_hidden, c_dim) if `model` is a latent-conditioned SIREN the fused kernels can run (the
+    reference's Siren(c_dim = C > 0) or ours: `.net[i].linear`, layer 0 (3 + C) wide with the code columns FIRST, as
+    forward concatenates [c, x]), else None.  lins[0].weight[:, :c_dim] are the code columns, [:, c_dim:] the xyz
+    columns.  siren_spec() stays None for these models: only the callers that pass a code take them."""
+    C = getattr(model, "c_dim", 0)
+    if not isinstance(C, int) or C <= 0 or not (hasattr(model, "net") and isinstance(model.net, nn.Sequential)):
+        return None
+    mods = list(model.net)
+    if len(mods) < 2 or not isinstance(mods[-1], nn.Linear):
+        return None
+    if not all(hasattr(m, "linear") and hasattr(m, "omega_0") for m in mods[:-1]):
+        return None
+    lins = [m.linear for m in mods[:-1]] + [mods[-1]]
+    omegas = [float(m.omega_0) for m in mods[:-1]]
+    if lins[0].in_features != 3 + C or not _siren_shape_ok(lins, omegas):
+        return None
+    return lins, omegas[0], (omegas[1] if len(omegas) > 1 else omegas[0]), C
+
+
+def code_rows(c, c_dim, counts):
+    """The code shapes the reference's callers pass, as the fused kernels take them: (codes (U, c_dim) f32, code_of) or
+    None (the generic route).  counts: host list, number of points (rays, pairs) of each batch row, in packed order.
+      (C,) / (1, C) / (1, 1, C)  one code for every point: U = 1, code_of None
+      (N, C) / (N, 1, C)         one code per row, N = len(counts): code_of (sum(counts),) int32 on c's device, row b
+                                 repeated counts[b] times
+    Anything else (per-point codes, a row count that is not the batch's) is None."""
+    if not torch.is_tensor(c) or c.numel() == 0 or c.shape[-1] != c_dim or c.dtype not in (torch.float32, torch.float64,
+                                                                                          torch.float16, torch.bfloat16):
+        return None
+    if c.ndim == 1 or (c.ndim in (2, 3) and all(d == 1 for d in c.shape[:-1])):
+        return CodeRows(c.detach().reshape(1, c_dim).float().contiguous(), None)
+    if c.ndim == 3 and c.shape[1] != 1:
+        return None
+    if c.ndim not in (2, 3) or c.shape[0] != len(counts):
+        return None
+    codes = c.detach().reshape(-1, c_dim).float().contiguous()
+    return CodeRows(codes, rows_of(counts, c.device))
+
+
+def rows_of(counts, device):
+    """(sum(counts),) int32 on `device`: b repeated counts[b] times (host list in, no host read)"""
+    reps = torch.tensor([int(x) for x in counts], dtype=torch.int64, device=device)
+    return torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int32, device=device), reps,
+                                   output_size=int(sum(int(x) for x in counts)))
+
+
+def _siren_shape_ok(lins, omegas):
+    """3 (+ code columns) -> H -> H.. -> 1 with H <= 256, <= 8 hidden layers, biases, one hidden omega"""
+    H = lins[0].out_features
+    if lins[-1].out_features != 1 or lins[-1].in_features != H:
+        return False
+    if H < 1 or H > 256 or len(lins) - 2 > 8:
+        return False
+    if any(lin.in_features != H or lin.out_features != H for lin in lins[1:-1]):
+        return False
+    if any(lin.bias is None for lin in lins):
+        return False
+    return len(set(omegas[1:])) <= 1
 
 
 def siren_spec(model):
@@ -129,14 +197,18 @@ class PackedSiren(object):
     `current(model)` is necessary, not sufficient, for the image to be up to date (see weights_key)."""
 
     def current(self, model, device):
-        spec = siren_spec(model)
+        spec = siren_spec(model) or coded_siren_spec(model)
         return spec is not None and weights_key(spec[0], device) == self.key
 
     def __init__(self, model, device):
         spec = siren_spec(model)
-        if spec is None:
+        coded = coded_siren_spec(model) if spec is None else None
+        if spec is None and coded is None:
             raise ValueError("model is not a SIREN the fused kernel supports")
-        lins, self.omega_first, self.omega_hidden = spec
+        # a latent-conditioned SIREN (coded_siren_spec) is packed as the network of its xyz columns W0[:, C:]; the code
+        # columns and b0 stay on the device for fold(), which turns the codes of a call into layer 0's biases
+        self.c_dim = coded[3] if coded is not None else 0
+        lins, self.omega_first, self.omega_hidden = spec if spec is not None else coded[:3]
         self.key = weights_key(lins, device)
         self.model_hidden = lins[0].out_features
         # the fused kernels exist for H = 64 / 128 / 256: any other width runs as the next one up with ZERO rows and
@@ -148,6 +220,10 @@ class PackedSiren(object):
         for i, lin in enumerate(lins):
             w = lin.weight.detach().to(device=device, dtype=torch.float32)
             b = lin.bias.detach().to(device=device, dtype=torch.float32)
+            if i == 0 and self.c_dim:
+                self.w0_code = w[:, :self.c_dim].contiguous()            # (H_model, C)
+                self.b0 = b.contiguous()                                  # (H_model,)
+                w = w[:, self.c_dim:]
             rows = H if i < len(lins) - 1 else w.shape[0]
             cols = H if i > 0 else w.shape[1]
             if (rows, cols) != tuple(w.shape):
@@ -166,6 +242,17 @@ class PackedSiren(object):
                   self.n_hidden, _lib.stream())
         self._ws = None
 
+    def fold(self, codes):
+        """codes (U, c_dim) f32 on the device -> layer 0's bias of every code, (U, hidden) f32 (iso_siren_fold_codes: one
+        launch, no host read): b0 + W0[:, :C] c_u in natural feature order, padded features 0.  Separate from the
+        weight image, which is re-used across calls while the codes change every call."""
+        assert self.c_dim and codes.ndim == 2 and codes.shape[1] == self.c_dim
+        codes = codes.detach().to(device=self.packed.device, dtype=torch.float32).contiguous()
+        table = torch.empty((codes.shape[0], self.hidden), dtype=torch.float32, device=self.packed.device)
+        _lib.call("iso_siren_fold_codes", _lib.ptr(self.w0_code), _lib.ptr(self.b0), _lib.ptr(codes), _lib.ptr(table),
+                  self.model_hidden, self.hidden, self.c_dim, codes.shape[0], _lib.stream())
+        return table
+
     def workspace(self, n):
         need = _lib.load().iso_project_siren_workspace_bytes(int(n), self.hidden, self.n_hidden)
         if self._ws is None or self._ws.numel() < need:
@@ -173,20 +260,27 @@ class PackedSiren(object):
         return self._ws
 
 
-def siren_sdf_and_grad(model, points, need_grad=True, packed=None):
+def siren_sdf_and_grad(model, points, need_grad=True, packed=None, code=None):
     """One fused SDF + gradient evaluation (UniformProjection._compute_sdf_and_grad,
     levelset_sampling.py:142-170) for a SIREN.  points (...,3) -> sdf (...), grad (...,3).
-    need_grad=False: value only (forward sweep only), grad is None."""
+    need_grad=False: value only (forward sweep only), grad is None.
+    code: CodeRows of a latent-conditioned SIREN (code_rows); required for those, refused for the others."""
     shp = points.shape
     pts = points.detach().reshape(-1, 3).float().contiguous()
     ps = packed if packed is not None else PackedSiren(model, pts.device)
+    if bool(ps.c_dim) != (code is not None):
+        raise ValueError("a latent-conditioned SIREN needs its code, an unconditioned one takes none")
     n = pts.shape[0]
     sdf = torch.empty((n,), dtype=torch.float32, device=pts.device)
     grad = torch.empty((n, 3), dtype=torch.float32, device=pts.device) if need_grad else None
     ws = ps.workspace(n)
-    _lib.call("iso_siren_sdf_grad", _lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(grad), n,
-              _lib.ptr(ps.packed), ps.hidden, ps.n_hidden, ps.omega_first, ps.omega_hidden,
-              _lib.ptr(ws), ws.numel(), _lib.stream())
+    args = [_lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(grad), n, _lib.ptr(ps.packed), ps.hidden, ps.n_hidden, ps.omega_first,
+            ps.omega_hidden, _lib.ptr(ws), ws.numel(), _lib.stream()]
+    if code is None:
+        _lib.call("iso_siren_sdf_grad", *args)
+    else:
+        table, code_of = ps.fold(code.codes), code.code_of
+        _lib.call("iso_siren_sdf_grad_coded", *args, _lib.ptr(table), _lib.ptr(code_of), table.shape[0])
     return sdf.view(shp[:-1]), (grad.view(shp) if need_grad else None)
 
 
@@ -301,12 +395,26 @@ class FusedSdf(object):
             self.kind, self.packed = "siren", PackedSiren(model, device)
         elif idr_spec(model) is not None:
             self.kind, self.packed = "idr", PackedIdr(model, device)
+        elif coded_siren_spec(model) is not None:
+            self.kind, self.packed = "coded_siren", PackedSiren(model, device)
 
     def __call__(self, points, **forward_kwargs):
-        """points (...,3) -> sdf (...)"""
+        """points (...,3) -> sdf (...).  A latent-conditioned SIREN takes its code as c=: one for all points ((C,) /
+        (1, C)), one per leading row of `points` ((N, C) / (N, 1, C)), or CodeRows; other shapes, and any other
+        forward kwarg, go to model.forward."""
         if not points.is_cuda:
             raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
-        if forward_kwargs or self.kind == "generic":
+        if self.kind == "coded_siren" and set(forward_kwargs) <= {"c"}:
+            c = forward_kwargs.get("c")
+            if c is None or (torch.is_tensor(c) and c.numel() == 0):
+                raise ValueError("iso_points_amd: this SIREN is conditioned on a latent code (c_dim = %d): pass c"
+                                 % self.packed.c_dim)
+            rows = points.shape[0] if points.ndim > 1 else 1
+            code = c if isinstance(c, CodeRows) else \
+                code_rows(c, self.packed.c_dim, [points.numel() // 3 // max(rows, 1)] * rows)
+            if code is not None:
+                return siren_sdf_and_grad(self.model, points, need_grad=False, packed=self.packed, code=code)[0]
+        if forward_kwargs or self.kind in ("generic", "coded_siren"):
             with torch.no_grad():
                 return self.model.forward(points.reshape(-1, 3), **forward_kwargs).sdf.reshape(points.shape[:-1])
         if self.kind == "siren":
