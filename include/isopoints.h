@@ -429,6 +429,21 @@ int iso_farthest_point_sampling(const float* points, const int64_t* lengths,
                                 int64_t p_stride, int64_t out_stride, float* work,
                                 int64_t* out_idx, void* stream);
 
+/* Local frames of a K-nearest neighbourhood = estimate_pointcloud_local_coord_frames
+ * (DSS/utils/mathHelper.py:43-119): per valid row (b, i < lengths[b]) with neighbours
+ * x_j = points[b, idx[b,i,j]] (idx (N,P,K) int64 from knn_points, the point itself included):
+ * m = mean x_j, C = (1/K) sum (x_j - m)(x_j - m)^T, eigenpairs by cyclic Jacobi in f32,
+ * eigenvalues clamped at >= 0 and ascending -> curvature_out (N,P,3); frames_out (N,P,3,3)
+ * holds eigenvector c in column c (frames[..., :, 0] = the normal).  disambiguate != 0 applies
+ * the reference's sign rule (:73-74, :105-113): with d_j = x_j - (p_i - mu_b), mu_b the mean of
+ * cloud b's first lengths[b] rows, a column flips when #{<v, d_j> > 0} < K/2 (columns 0 and 2),
+ * and column 1 = col0 x col2.  Rows i >= lengths[b] are zeroed; lengths NULL = max_points.
+ * work: iso_pca_frames_work_bytes(N) of scratch (only read when disambiguate).  No atomics. */
+int64_t iso_pca_frames_work_bytes(int n_clouds);
+int iso_pca_frames(const float* points, const int64_t* lengths, const int64_t* idx, int n_clouds,
+                   int64_t max_points, int K, int disambiguate, void* work, float* curvature_out,
+                   float* frames_out, void* stream);
+
 /* ------------------------------------------------------------------------
  * D. EWA surface splatting
  *    replaces SurfaceSplatting (DSS/core/rasterizer.py:103-661), the pybind module

@@ -6,6 +6,7 @@
   farthest_sampling   point_processing.py:473-499   (torch_cluster.fps)
   knn_points          pytorch3d.ops.knn_points as upsample uses it (:315,:358)
   denoise_normals     point_processing.py:241-278   bilateral normal filter on the FRNN neighbourhood
+  remove_outliers     point_processing.py:16-31     drop points whose neighbourhood is not flat (math_helper)
 
 Inputs are padded tensors (N,P,3) + lengths (pytorch3d's Pointclouds container is out of scope;
 objects exposing points_padded()/num_points_per_cloud() are accepted).  Neighbour search, the
@@ -234,3 +235,26 @@ def denoise_normals(points, normals, sharpness_sigma=30, knn_result=None, neighb
         torch.exp(-(((1 - (nbr_n * unit[:, :, None, :]).sum(dim=-1)) / sharpness_sigma) ** 2))
     mean = (nbr_n * w[..., None]).sum(dim=-2) / eps_denom(w.sum(dim=-1, keepdim=True))
     return torch.nn.functional.normalize(mean, dim=-1).view_as(normals)
+
+
+def remove_outliers(pointclouds, neighborhood_size=16, tolerance=0.05):
+    """Keep the points whose K-neighbourhood is flat: lambda0 / (lambda0 + lambda1 + lambda2) < tolerance over the
+    ascending covariance eigenvalues of math_helper.estimate_pointcloud_local_coord_frames, and that lie inside their
+    cloud's length (point_processing.py:16-31).  Returns the kept points compacted per cloud, in order, as
+    (points_padded (N, max kept, 3), num_points (N,)), the way upsample / wlop return.  The ratio is the reference's plain
+    division: in a neighbourhood of exact duplicates it is 0 / 0 = NaN and the point is dropped, as in the reference.
+    Same limits as the estimator: neighborhood_size <= 32, no backward."""
+    from .math_helper import estimate_pointcloud_local_coord_frames
+    points, num_points = convert_pointclouds_to_tensor(pointclouds)
+    # only the eigenvalues are read: the sign rule does not change them
+    variance, _ = estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size=neighborhood_size,
+                                                         disambiguate_directions=False)
+    N, P = points.shape[0], points.shape[1]
+    inside = torch.arange(P, device=points.device)[None, :] < num_points.to(points.device)[:, None]
+    mask = (variance[..., 0] / torch.sum(variance, dim=-1) < tolerance) & inside
+    kept = [int(x) for x in mask.sum(dim=1).tolist()]
+    out = points.new_zeros((N, max(kept) if kept else 0, 3))
+    for b in range(N):
+        out[b, : kept[b]] = points[b][mask[b]]
+    return out, with_host_lengths(torch.tensor(kept, dtype=torch.int64, device=points.device), kept)
+
