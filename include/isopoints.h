@@ -482,6 +482,48 @@ int iso_splat_setup(const float* points, const float* normals, const float* h,
                     float sigma, float cutoff, float* ndc_out, float* ellipse_out,
                     float* cutoff_out, float* radii_out, float* scaler_out, void* stream);
 
+/* _compute_global_Vrk (rasterizer.py:293-342), Vrk_invariant: ONE h per cloud.  dists (N,p_stride,7)
+ * from the K=7 self query -> h[first_idx[n] + i] = clamp(mean, 5e-5, 1e-3) for every row of cloud n,
+ * where mean is the reference's h_k.mean(dim=1) over the PADDED tensor of all clouds of ITS call:
+ * sum over i < padded_len of 0.5*max_{6 nn} d2, with -0.5 for the rows past num_pts[n] (FRNN pads
+ * distances with -1) and 0.5e-3 for every row of a cloud of fewer than 7 points, divided by
+ * padded_len.  padded_len = the largest cloud's length over everything the reference would have
+ * batched (>= p_stride; the caller may hand the clouds over in several calls with the same value).
+ * num_pts[n] must be <= p_stride: rows of `dists` that do not exist count as padding.  Two launches:
+ * per-slice sums in double (fixed order, no atomics), then finish + broadcast.
+ * work: iso_splat_vrk_h_global_work_bytes(N) of scratch.                                   */
+int64_t iso_splat_vrk_h_global_work_bytes(int n_clouds);
+int iso_splat_vrk_h_global(const float* dists, const int64_t* first_idx, const int64_t* num_pts,
+                           float* h, int n_clouds, int64_t p_stride, int64_t padded_len, void* work,
+                           void* stream);
+/* The tangent frame the isotropic set-up (iso_splat_setup / iso_splat_front) derives from a normal:
+ * u = normalize(n x (n + e)), v = normalize(n x u), e = the axis least aligned with n.  n rows of
+ * normals -> u_out, v_out (n,3).  For tests and tools: iso_splat_setup_vrk fed (n, u, v) and
+ * curvature (., h, h) gives iso_splat_setup's bits.                                         */
+int iso_splat_tangent_frame(const float* normals, int64_t n, float* u_out, float* v_out, void* stream);
+/* _get_per_point_info with an explicit local frame (_compute_anisotropic_Vrk, rasterizer.py:257-291
+ * + :417-424): as iso_splat_setup, but the splat's plane and variances come from frames (P,3,3)
+ * packed (eigenvector c in column c) and curvature (P,3) packed, ascending, as iso_pca_frames
+ * writes them: u = column 1, v = column 2, Vrk = curvature[1] u u^T + curvature[2] v v^T (no clamp).
+ * Every output is invariant under a sign flip of u or v.  A row with curvature[1] == curvature[2]
+ * takes iso_splat_setup's factored arithmetic.                                             */
+int iso_splat_setup_vrk(const float* points, const float* frames, const float* curvature,
+                        const int64_t* first_idx, const int64_t* num_pts, const float* views,
+                        const float* projs, int n_views, int64_t max_pts, int image_size,
+                        float sigma, float cutoff, float* ndc_out, float* ellipse_out,
+                        float* cutoff_out, float* radii_out, float* scaler_out, void* stream);
+/* The same, fused with estimate_pointcloud_local_coord_frames(neighborhood_size=8,
+ * disambiguate_directions=False) (mathHelper.py:43-119): knn_idx (n_views,p_stride,8) int64 holds,
+ * for row i of view cloud n, the 8 nearest rows of THAT cloud (the row itself included, indices
+ * local to the cloud: knn_points on the padded view clouds); the frame is solved in registers by
+ * the device code of iso_pca_frames and never written.  Bit-identical to iso_pca_frames(K=8,
+ * disambiguate=0) + iso_splat_setup_vrk.  Every cloud must hold more than 8 points.          */
+int iso_splat_setup_aniso(const float* points, const int64_t* knn_idx, int64_t p_stride,
+                          const int64_t* first_idx, const int64_t* num_pts, const float* views,
+                          const float* projs, int n_views, int image_size, float sigma,
+                          float cutoff, float* ndc_out, float* ellipse_out, float* cutoff_out,
+                          float* radii_out, float* scaler_out, void* stream);
+
 /* Forward rasterisation = _C.splat_points (rasterize_points.h:461-525).
  * Two calls around one caller-side read of the pair count:
  *   iso_splat_bin_count : tile_cnt (n_clouds*T*T, zero on entry) += splats per

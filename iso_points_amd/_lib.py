@@ -80,6 +80,11 @@ SIGNATURES = {
     "iso_compact_rows": (_I, [_P, _P, _P, _P, _L, _L, _I, _P]),
     "iso_splat_vrk_h": (_I, [_P, _P, _P, _P, _P, _I, _L, _P]),
     "iso_splat_setup": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "iso_splat_vrk_h_global_work_bytes": (_L, [_I]),
+    "iso_splat_vrk_h_global": (_I, [_P, _P, _P, _P, _I, _L, _L, _P, _P]),
+    "iso_splat_tangent_frame": (_I, [_P, _L, _P, _P, _P]),
+    "iso_splat_setup_vrk": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
+    "iso_splat_setup_aniso": (_I, [_P, _P, _L, _P, _P, _P, _P, _I, _I, _F, _F, _P, _P, _P, _P, _P, _P]),
     "iso_splat_tiles_per_side": (_I, [_I]),
     "iso_splat_bin_count": (_I, [_P, _P, _P, _P, _I, _L, _I, _I, _I, _I, _P, _P]),
     "iso_splat_tile_offsets": (_I, [_P, _P, _P, _L, _P]),

@@ -32,6 +32,7 @@
 #include <float.h>
 #include "iso_common.h"
 #include "splat_frame.h"
+#include "pca_eig.h"
 
 #pragma clang fp contract(off)
 
@@ -184,6 +185,117 @@ __device__ __forceinline__ SetupRes splat_setup_point(float x, float y, float z,
   return o;
 }
 
+// The tangent frame of splat_setup_point, statement for statement, for iso_splat_tangent_frame (the export through which a
+// test hands the isotropic kernel's own frame to iso_splat_setup_vrk).  A copy and not a call from splat_setup_point:
+// calling it there changed the instruction schedule of k_splat_setup.
+__device__ __forceinline__ void splat_tangent_frame(float nx, float ny, float nz, float& ux, float& uy, float& uz,
+                                                    float& vx, float& vy, float& vz) {
+  // tangent frame: u0 = normalize(n x (n + e)), u1 = normalize(n x u0), e = axis least
+  // aligned with n (a deterministic instance of rasterizer.py:395-397)
+  float ex = 0.f, ey = 0.f, ez = 0.f;
+  const float ax = fabsf(nx), ay = fabsf(ny), az = fabsf(nz);
+  if (ax <= ay && ax <= az) ex = 1.f; else if (ay <= az) ey = 1.f; else ez = 1.f;
+  const float mx = nx + ex, my = ny + ey, mz = nz + ez;
+  ux = ny * mz - nz * my;
+  uy = nz * mx - nx * mz;
+  uz = nx * my - ny * mx;
+  float un = sqrtf((ux * ux + uy * uy) + uz * uz);
+  un = un > 1e-12f ? un : 1e-12f;
+  ux /= un; uy /= un; uz /= un;
+  vx = ny * uz - nz * uy;
+  vy = nz * ux - nx * uz;
+  vz = nx * uy - ny * ux;
+  float vn = sqrtf((vx * vx + vy * vy) + vz * vz);
+  vn = vn > 1e-12f ? vn : 1e-12f;
+  vx /= vn; vy /= vn; vz /= vn;
+}
+
+__global__ void k_tangent_frame(const float* __restrict__ nrm, int64_t n, float* __restrict__ u, float* __restrict__ v) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float ux, uy, uz, vx, vy, vz;
+    splat_tangent_frame(nrm[i * 3], nrm[i * 3 + 1], nrm[i * 3 + 2], ux, uy, uz, vx, vy, vz);
+    u[i * 3] = ux; u[i * 3 + 1] = uy; u[i * 3 + 2] = uz;
+    v[i * 3] = vx; v[i * 3 + 1] = vy; v[i * 3 + 2] = vz;
+  }
+}
+
+// World -> NDC of the point and WJk (3x2), the Jacobian of screen xy with respect to world xyz (_compute_WJk, :441-492):
+// the part of the set-up that comes before the local frame (the first lines of splat_setup_point).
+struct SetupProj { float xv, yv, t, zv, w0[3], w1[3]; };
+
+__device__ __forceinline__ SetupProj splat_setup_project(float x, float y, float z, const float* __restrict__ V,
+                                                         const float* __restrict__ M) {
+  SetupProj pj;
+  // [p,1] @ M columns 0,1,3 and view depth
+  pj.xv = ((x * M[0] + y * M[4]) + z * M[8]) + M[12];
+  pj.yv = ((x * M[1] + y * M[5]) + z * M[9]) + M[13];
+  pj.t = ((x * M[3] + y * M[7]) + z * M[11]) + M[15];
+  pj.zv = ((x * V[2] + y * V[6]) + z * V[10]) + V[14];
+  const float t2 = iso_eps_denom(pj.t * pj.t, 1e-17f);
+  const float td = iso_eps_denom(pj.t, 1e-17f);
+  const float j00 = 1.0f / td;
+  const float j30 = -1.0f / t2 * pj.xv, j31 = -1.0f / t2 * pj.yv;
+  // WJk = M[:3,:] @ Jk  (3x2)
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    pj.w0[r] = M[r * 4 + 0] * j00 + M[r * 4 + 3] * j30;
+    pj.w1[r] = M[r * 4 + 1] * j00 + M[r * 4 + 3] * j31;
+  }
+  return pj;
+}
+
+// The part after the frame for an explicit frame and two variances: Sk = [u; v] (2x3) spans the splat's plane, Vrk = c1 u u^T + c2 v v^T
+// is its source-space variance.  Mk = Sk @ WJk, G = Mk^T diag(c1, c2) Mk + lp I; ellipse, radii and scaler follow from G and
+// |det Mk| (:499-563), the general form of _compute_anisotropic_Vrk (:257-291).  splat_setup_point above is the instance
+// c1 == c2 = h with the frame derived from the normal and G = h Mk^T Mk + lp I factored; it is kept as it was (splitting it
+// changed the instruction schedule of the isotropic kernels), and this sibling falls back to the factored form by select
+// where the two variances of a row are equal, so an isotropic row gives the same bits through either entry.  Every output
+// is even in u and in v: the eigensolver's arbitrary signs do not matter.
+__device__ __forceinline__ SetupRes splat_setup_frame(const SetupProj& pj, float ux, float uy, float uz, float vx, float vy,
+                                                      float vz, float c1, float c2, int S, float sigma, float cutoffC) {
+  const float* w0 = pj.w0;
+  const float* w1 = pj.w1;
+  // Mk = Sk @ WJk (2x2)
+  const float m00 = (ux * w0[0] + uy * w0[1]) + uz * w0[2];
+  const float m01 = (ux * w1[0] + uy * w1[1]) + uz * w1[2];
+  const float m10 = (vx * w0[0] + vy * w0[1]) + vz * w0[2];
+  const float m11 = (vx * w1[0] + vy * w1[1]) + vz * w1[2];
+  const float ps = 2.0f / (float)S;
+  const float lp = sigma * (ps * ps);
+  const float hk = c1;
+  // Vk = h * Mk^T Mk
+  float g00 = hk * (m00 * m00 + m10 * m10) + lp;
+  float g01 = hk * (m00 * m01 + m10 * m11);
+  float g11 = hk * (m01 * m01 + m11 * m11) + lp;
+  const float detM = m00 * m11 - m01 * m10;
+  // det(h M^T M + lp I) = h^2 det(M)^2 + lp h |M|_F^2 + lp^2: all terms positive, so no
+  // cancellation (the textbook g00*g11 - g01^2 loses ~cond(G) digits on grazing splats)
+  const float fro = (m00 * m00 + m10 * m10) + (m01 * m01 + m11 * m11);
+  float detG = (hk * hk) * (detM * detM) + (lp * hk * fro + lp * lp);
+  {
+    // det(G) = c1 c2 det(Mk)^2 + lp (c1 |row0(Mk)|^2 + c2 |row1(Mk)|^2) + lp^2: the same expansion, all terms non-negative
+    const bool same = c1 == c2;
+    const float a00 = (c1 * (m00 * m00) + c2 * (m10 * m10)) + lp;
+    const float a01 = c1 * (m00 * m01) + c2 * (m10 * m11);
+    const float a11 = (c1 * (m01 * m01) + c2 * (m11 * m11)) + lp;
+    const float adet = (c1 * c2) * (detM * detM) +
+                       (lp * (c1 * (m00 * m00 + m01 * m01) + c2 * (m10 * m10 + m11 * m11)) + lp * lp);
+    g00 = same ? g00 : a00;
+    g01 = same ? g01 : a01;
+    g11 = same ? g11 : a11;
+    detG = same ? detG : adet;
+  }
+  const float a = g11 / detG, c = g00 / detG, b = (-g01 / detG) + (-g01 / detG);
+  const float den = iso_eps_denom(4.0f * a * c - b * b, 1e-17f);
+  SetupRes o;
+  o.rad[1] = sqrtf(esqrt_arg(4.0f * a * cutoffC / den));
+  o.rad[0] = sqrtf(esqrt_arg(4.0f * c * cutoffC / den));
+  o.scaler = fabsf(detM) / iso_eps_denom(sqrtf(esqrt_arg(detG * 4.0f * 3.14159265358979323846f * 3.14159265358979323846f)), 1e-17f);
+  o.ndc[0] = pj.xv / pj.t; o.ndc[1] = pj.yv / pj.t; o.ndc[2] = pj.zv;
+  o.el[0] = a; o.el[1] = b; o.el[2] = c;
+  return o;
+}
+
 __global__ void k_splat_setup(const float* __restrict__ pts, const float* __restrict__ nrm,
                               const float* __restrict__ h, const int64_t* __restrict__ first,
                               const int64_t* __restrict__ num, const float* __restrict__ views,
@@ -204,6 +316,120 @@ __global__ void k_splat_setup(const float* __restrict__ pts, const float* __rest
     o.radii[p * 2] = r.rad[0]; o.radii[p * 2 + 1] = r.rad[1];
     o.scaler[p] = r.scaler;
   }
+}
+
+// The set-up for an explicit local frame: frames (P,3,3) packed, eigenvector c in column c, curvature (P,3) ascending
+// (what iso_pca_frames writes); the two larger eigenpairs span the splat (rasterizer.py:281-290).
+__global__ void k_splat_setup_vrk(const float* __restrict__ pts, const float* __restrict__ frames,
+                                  const float* __restrict__ curv, const int64_t* __restrict__ first,
+                                  const int64_t* __restrict__ num, const float* __restrict__ views,
+                                  const float* __restrict__ projs, int S, float sigma, float cutoffC, SetupOut o) {
+  const int n = blockIdx.y;
+  const float* V = views + n * 16;
+  const float* M = projs + n * 16;
+  const int64_t len = num[n], base = first[n];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = base + i;
+    const float* f = frames + p * 9;
+    const SetupProj pj = splat_setup_project(pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2], V, M);
+    const SetupRes r = splat_setup_frame(pj, f[1], f[4], f[7], f[2], f[5], f[8], curv[p * 3 + 1], curv[p * 3 + 2], S, sigma,
+                                         cutoffC);
+    o.ndc[p * 3] = r.ndc[0]; o.ndc[p * 3 + 1] = r.ndc[1]; o.ndc[p * 3 + 2] = r.ndc[2];
+    o.ellipse[p * 3] = r.el[0]; o.ellipse[p * 3 + 1] = r.el[1]; o.ellipse[p * 3 + 2] = r.el[2];
+    o.cutoff[p] = cutoffC;
+    o.radii[p * 2] = r.rad[0]; o.radii[p * 2 + 1] = r.rad[1];
+    o.scaler[p] = r.scaler;
+  }
+}
+
+// Anisotropic set-up, fused: one lane per packed row gathers its 8 neighbours of the SAME view cloud through the kNN
+// index (N, p_stride, 8; indices local to the cloud), solves the neighbourhood covariance with the device code of
+// k_pca_frames (pca_eig.h) and goes straight into the set-up; the frame never reaches memory.
+constexpr int kVrkK = 8;       // neighborhood_size of _compute_anisotropic_Vrk (rasterizer.py:275)
+__global__ void __launch_bounds__(256) k_splat_setup_aniso(const float* __restrict__ pts, const int64_t* __restrict__ idx,
+                                                           int64_t p_stride, const int64_t* __restrict__ first,
+                                                           const int64_t* __restrict__ num,
+                                                           const float* __restrict__ views,
+                                                           const float* __restrict__ projs, int S, float sigma,
+                                                           float cutoffC, SetupOut o) {
+  const int n = blockIdx.y;
+  const float* V = views + n * 16;
+  const float* M = projs + n * 16;
+  const int64_t base = first[n];
+  const int64_t len = min(num[n], p_stride);
+  const float* cloud = pts + base * 3;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t p = base + i;
+    float l[3], v[3][3];
+    pca_neighbourhood_eig(cloud, idx + ((int64_t)n * p_stride + i) * kVrkK, kVrkK, len, l, v);
+    const SetupProj pj = splat_setup_project(pts[p * 3], pts[p * 3 + 1], pts[p * 3 + 2], V, M);
+    const SetupRes r = splat_setup_frame(pj, v[0][1], v[1][1], v[2][1], v[0][2], v[1][2], v[2][2], l[1], l[2], S, sigma,
+                                         cutoffC);
+    o.ndc[p * 3] = r.ndc[0]; o.ndc[p * 3 + 1] = r.ndc[1]; o.ndc[p * 3 + 2] = r.ndc[2];
+    o.ellipse[p * 3] = r.el[0]; o.ellipse[p * 3 + 1] = r.el[1]; o.ellipse[p * 3 + 2] = r.el[2];
+    o.cutoff[p] = cutoffC;
+    o.radii[p * 2] = r.rad[0]; o.radii[p * 2 + 1] = r.rad[1];
+    o.scaler[p] = r.scaler;
+  }
+}
+
+// Invariant mode (_compute_global_Vrk, rasterizer.py:293-342): ONE h per cloud = clamp(mean_i 0.5 * max_{6 nn} d2, 5e-5,
+// 1e-3).  The reference's mean runs over the PADDED (N, padded_len, 6) tensor of ALL clouds of its call (padded_len = the
+// largest one's length, given by the caller, who may hand the clouds over in several calls): it divides by padded_len,
+// and a row past a shorter cloud's length contributes what the neighbour search padded it with (-1 from FRNN: -0.5); a
+// cloud of fewer than 7 points has every row, padded ones included, set to 1e-3.  Deterministic: workgroup (s, n) adds
+// slice s of cloud n in double and a fixed-shape tree in LDS, the finish adds the slices in order.
+constexpr int kHSlices = 64;
+constexpr int kHBlock = 256;
+__global__ void __launch_bounds__(kHBlock) k_vrk_h_partial(const float* __restrict__ dists /*(N,p_stride,7)*/,
+                                                           const int64_t* __restrict__ num, int64_t p_stride, int64_t pmax,
+                                                           double* __restrict__ part) {
+  __shared__ double s_sum[kHBlock];
+  const int n = blockIdx.y, s = blockIdx.x;
+  const int64_t clen = num[n];
+  const int64_t len = min(max(clen, (int64_t)0), p_stride);    // rows of `dists` that exist for this cloud
+  const int64_t chunk = (pmax + kHSlices - 1) / kHSlices;
+  const int64_t lo = s * chunk, hi = min(lo + chunk, pmax);
+  double acc = 0.0;
+  for (int64_t i = lo + threadIdx.x; i < hi; i += kHBlock) {
+    float m = -1.0f;                                           // a padded row: FRNN's fill
+    if (clen < 7) {
+      m = 1e-3f;
+    } else if (i < len) {
+      const float* d = dists + ((int64_t)n * p_stride + i) * 7;
+      m = -FLT_MAX;
+#pragma unroll
+      for (int k = 1; k < 7; ++k) m = fmaxf(m, d[k]);
+    }
+    acc += (double)(0.5f * m);
+  }
+  s_sum[threadIdx.x] = acc;
+  __syncthreads();
+  for (int w = kHBlock / 2; w > 0; w >>= 1) {
+    if (threadIdx.x < w) s_sum[threadIdx.x] += s_sum[threadIdx.x + w];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[(int64_t)n * kHSlices + s] = s_sum[0];
+}
+
+__global__ void __launch_bounds__(256) k_vrk_h_finish(const double* __restrict__ part, const int64_t* __restrict__ first,
+                                                      const int64_t* __restrict__ num, int64_t pmax,
+                                                      float* __restrict__ h) {
+  __shared__ float s_h;
+  const int n = blockIdx.y;
+  if (threadIdx.x == 0) {
+    double acc = 0.0;
+    for (int s = 0; s < kHSlices; ++s) acc += part[(int64_t)n * kHSlices + s];
+    const float mean = (float)(acc / (double)(pmax > 0 ? pmax : 1));
+    s_h = fminf(fmaxf(mean, 5e-5f), 1e-3f);
+  }
+  __syncthreads();
+  const float hv = s_h;
+  const int64_t len = num[n], base = first[n];
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (int64_t)gridDim.x * blockDim.x)
+    h[base + i] = hv;
 }
 
 // ---------------------------------------------------------------- fused filter + compaction + set-up
@@ -1933,6 +2159,71 @@ extern "C" int iso_splat_setup(const float* points, const float* normals, const 
   hipLaunchKernelGGL(k_splat_setup, dim3(gx, n_views), dim3(256), 0, (hipStream_t)stream, points,
                      normals, h, first_idx, num_pts, views, projs, image_size, sigma, cutoff, o);
   ISO_CHECK_LAUNCH("iso_splat_setup");
+  return ISO_OK;
+}
+
+extern "C" int64_t iso_splat_vrk_h_global_work_bytes(int n_clouds) {
+  return n_clouds > 0 ? (int64_t)n_clouds * kHSlices * (int64_t)sizeof(double) : 0;
+}
+
+extern "C" int iso_splat_vrk_h_global(const float* dists, const int64_t* first_idx, const int64_t* num_pts, float* h,
+                                      int n_clouds, int64_t p_stride, int64_t padded_len, void* work, void* stream) {
+  ISO_REQUIRE(n_clouds >= 0 && p_stride >= 0 && padded_len >= p_stride, ISO_ERR_INVALID,
+              "iso_splat_vrk_h_global: bad sizes (padded_len must be >= p_stride)");
+  if (n_clouds == 0 || p_stride == 0) return ISO_OK;
+  ISO_REQUIRE(dists && first_idx && num_pts && h && work, ISO_ERR_INVALID, "iso_splat_vrk_h_global: null pointer");
+  hipLaunchKernelGGL(k_vrk_h_partial, dim3(kHSlices, n_clouds), dim3(kHBlock), 0, (hipStream_t)stream, dists, num_pts,
+                     p_stride, padded_len, (double*)work);
+  ISO_CHECK_LAUNCH("iso_splat_vrk_h_global (partial sums)");
+  int gx = iso_div_up(p_stride, 256); if (gx > 4096) gx = 4096;
+  hipLaunchKernelGGL(k_vrk_h_finish, dim3(gx, n_clouds), dim3(256), 0, (hipStream_t)stream, (const double*)work, first_idx,
+                     num_pts, padded_len, h);
+  ISO_CHECK_LAUNCH("iso_splat_vrk_h_global");
+  return ISO_OK;
+}
+
+extern "C" int iso_splat_tangent_frame(const float* normals, int64_t n, float* u_out, float* v_out, void* stream) {
+  ISO_REQUIRE(n >= 0, ISO_ERR_INVALID, "iso_splat_tangent_frame: bad sizes");
+  if (n == 0) return ISO_OK;
+  ISO_REQUIRE(normals && u_out && v_out, ISO_ERR_INVALID, "iso_splat_tangent_frame: null pointer");
+  hipLaunchKernelGGL(k_tangent_frame, dim3(iso_stream_grid(n, 256)), dim3(256), 0, (hipStream_t)stream, normals, n, u_out,
+                     v_out);
+  ISO_CHECK_LAUNCH("iso_splat_tangent_frame");
+  return ISO_OK;
+}
+
+extern "C" int iso_splat_setup_vrk(const float* points, const float* frames, const float* curvature,
+                                   const int64_t* first_idx, const int64_t* num_pts, const float* views, const float* projs,
+                                   int n_views, int64_t max_pts, int image_size, float sigma, float cutoff, float* ndc_out,
+                                   float* ellipse_out, float* cutoff_out, float* radii_out, float* scaler_out, void* stream) {
+  ISO_REQUIRE(n_views >= 0 && max_pts >= 0 && image_size > 0, ISO_ERR_INVALID, "iso_splat_setup_vrk: bad sizes");
+  if (n_views == 0 || max_pts == 0) return ISO_OK;
+  ISO_REQUIRE(points && frames && curvature && first_idx && num_pts && views && projs && ndc_out && ellipse_out &&
+                  cutoff_out && radii_out && scaler_out,
+              ISO_ERR_INVALID, "iso_splat_setup_vrk: null pointer");
+  SetupOut o{ndc_out, ellipse_out, cutoff_out, radii_out, scaler_out};
+  int gx = iso_div_up(max_pts, 256); if (gx > 4096) gx = 4096;
+  hipLaunchKernelGGL(k_splat_setup_vrk, dim3(gx, n_views), dim3(256), 0, (hipStream_t)stream, points, frames, curvature,
+                     first_idx, num_pts, views, projs, image_size, sigma, cutoff, o);
+  ISO_CHECK_LAUNCH("iso_splat_setup_vrk");
+  return ISO_OK;
+}
+
+extern "C" int iso_splat_setup_aniso(const float* points, const int64_t* knn_idx, int64_t p_stride,
+                                     const int64_t* first_idx, const int64_t* num_pts, const float* views,
+                                     const float* projs, int n_views, int image_size, float sigma, float cutoff,
+                                     float* ndc_out, float* ellipse_out, float* cutoff_out, float* radii_out,
+                                     float* scaler_out, void* stream) {
+  ISO_REQUIRE(n_views >= 0 && p_stride >= 0 && image_size > 0, ISO_ERR_INVALID, "iso_splat_setup_aniso: bad sizes");
+  if (n_views == 0 || p_stride == 0) return ISO_OK;
+  ISO_REQUIRE(points && knn_idx && first_idx && num_pts && views && projs && ndc_out && ellipse_out && cutoff_out &&
+                  radii_out && scaler_out,
+              ISO_ERR_INVALID, "iso_splat_setup_aniso: null pointer");
+  SetupOut o{ndc_out, ellipse_out, cutoff_out, radii_out, scaler_out};
+  int gx = iso_div_up(p_stride, 256); if (gx > 4096) gx = 4096;
+  hipLaunchKernelGGL(k_splat_setup_aniso, dim3(gx, n_views), dim3(256), 0, (hipStream_t)stream, points, knn_idx, p_stride,
+                     first_idx, num_pts, views, projs, image_size, sigma, cutoff, o);
+  ISO_CHECK_LAUNCH("iso_splat_setup_aniso");
   return ISO_OK;
 }
 

@@ -170,6 +170,9 @@ class IsoCycle(object):
 
     def __init__(self, model, points0, views, projs, raster_settings=None, knn_k=8, comm=None, target=None,
                  world=None, rank=None):
+        if raster_settings is not None and (raster_settings.Vrk_invariant or not raster_settings.Vrk_isotropic):
+            raise NotImplementedError("IsoCycle: the non-default Vrk modes (Vrk_invariant / Vrk_isotropic=False) are out of "
+                                      "scope for the sharded cycle; SurfaceSplatting.forward serves them on one GPU")
         self.comm = comm or _Single()
         self.world = self.comm.world if world is None else int(world)
         self.rank = self.comm.rank if rank is None else int(rank)

@@ -543,34 +543,127 @@ class SurfaceSplatting(object):
                   flags.numel() - 1, U, _lib.stream())
         return out
 
-    def per_point_info(self, points_f, normals_f, first, num, views, projs):
-        """_get_per_point_info + transform for already filtered packed clouds."""
+    @staticmethod
+    def vrk_mode(rs):
+        """'isotropic' (the default), 'invariant' or 'anisotropic', in the reference's order of precedence
+        (rasterizer.py:417-424: Vrk_invariant wins over Vrk_isotropic)."""
+        if rs.Vrk_invariant:
+            return "invariant"
+        return "isotropic" if rs.Vrk_isotropic else "anisotropic"
+
+    def per_point_info(self, points_f, normals_f, first, num, views, projs, padded_len=None, debug=None):
+        """_get_per_point_info + transform for already filtered packed clouds, in the three Vrk modes of the reference
+        (rasterizer.py:417-424); every output is detached, as there (:556-563).
+
+        isotropic (default): h_i = clamp(0.5 * max of the 6 nearest squared distances, 5e-5, 0.01) per row (:367-386).
+
+        invariant (Vrk_invariant=True, :293-342): ONE h per view cloud, clamp(mean_i h_i, 5e-5, 1e-3), the same K = 7 FRNN
+        self query and the normal-derived frame.  Two quirks of the reference are reproduced: its mean is h_k.mean(dim=1)
+        over the PADDED tensor, so it divides by the LARGEST view cloud's length and every row past a shorter cloud's
+        length contributes -0.5 (FRNN pads distances with -1) -- a shorter cloud's h comes out smaller, often at the lower
+        clamp; and its refresh=False branch is dead (it raises NameError), so h is recomputed on every call: _Vrk_h holds
+        the rows' h of the last call for inspection and is never read back as a cache.
+
+        anisotropic (Vrk_isotropic=False, :257-291): per row, the two larger eigenpairs (c1, u), (c2, v) of the covariance of
+        its 8 nearest rows IN THE SAME VIEW CLOUD (estimate_pointcloud_local_coord_frames, K = 8, no disambiguation) give
+        Vrk = c1 u u^T + c2 v v^T; the normals are not used.  The eigenvalues are of the order of the squared point spacing
+        and are not clamped (the reference's behaviour): on a very dense cloud only the low-pass term
+        antialiasing_sigma * (2 / S)^2 keeps the splats visible.  A view cloud of 8 points or fewer raises the reference's
+        ValueError (mathHelper.py:66-70).  _Vrk_h is None afterwards.
+
+        padded_len (invariant mode): the length of the padded tensor the mean runs over, when the clouds of one reference
+        call are handed over in several calls here (forward() does: one call per cloud of a batch, or per run of 8 views);
+        default: the largest cloud of this call.  debug: a dict that receives "knn_idx" (N, max rows, 8), the anisotropic
+        mode's neighbour index (tests, tools); nothing is kept on the object."""
         rs = self.raster_settings
-        if rs.Vrk_invariant or not rs.Vrk_isotropic:
-            raise NotImplementedError("only the default isotropic Vrk is built (SURVEY 2.1 #3)")
+        mode = self.vrk_mode(rs)
         dev = points_f.device
         lens = host_lengths(num)
+        if mode == "anisotropic" and any(l <= 8 for l in lens):
+            raise ValueError("The neighborhood_size argument has to be >= size of each of the point clouds.")
         N, mx, tot = len(lens), (max(lens) if lens else 0), points_f.shape[0]
         p = _lib.ptr
         s = _lib.stream()
-        # h: K=7 self query per filtered view cloud (rasterizer.py:367-386)
         padded = torch.zeros((N, max(mx, 1), 3), dtype=torch.float32, device=dev)
         firsts = host_lengths(first)
         for i in range(N):
             padded[i, :lens[i]] = points_f[firsts[i]:firsts[i] + lens[i]]
-        dists, _, _, _ = frnn.frnn_grid_points(padded, padded, num, num, K=7, r=self.frnn_radius)
-        h = torch.empty((tot,), dtype=torch.float32, device=dev)
-        _lib.call("iso_splat_vrk_h", p(dists), p(first), p(num), None, p(h), N, dists.shape[1], s)
-        self._Vrk_h = h
         ndc = torch.empty((tot, 3), dtype=torch.float32, device=dev)
         ellipse = torch.empty((tot, 3), dtype=torch.float32, device=dev)
         cutoff = torch.empty((tot,), dtype=torch.float32, device=dev)
         radii = torch.empty((tot, 2), dtype=torch.float32, device=dev)
         scaler = torch.empty((tot,), dtype=torch.float32, device=dev)
+        out = ndc, {"radii": radii, "ellipse_params": ellipse, "cutoff_threshold": cutoff, "scaler": scaler}
+        size = (min(image_hw(rs.image_size)), float(rs.antialiasing_sigma), float(rs.cutoff_threshold))
+        if mode == "anisotropic":
+            from .point_processing import knn_points
+            idx = knn_points(padded, padded, num, num, K=8).idx.to(torch.int64).contiguous()       # (N, mx, 8), local indices
+            self._Vrk_h = None
+            if debug is not None:
+                debug["knn_idx"] = idx
+            _lib.call("iso_splat_setup_aniso", p(points_f), p(idx), idx.shape[1], p(first), p(num), p(_f32c(views)),
+                      p(_f32c(projs)), N, *size, p(ndc), p(ellipse), p(cutoff), p(radii), p(scaler), s)
+            return out
+        # h: K=7 self query per filtered view cloud (rasterizer.py:367-386, :306-320)
+        dists, _, _, _ = frnn.frnn_grid_points(padded, padded, num, num, K=7, r=self.frnn_radius)
+        h = torch.empty((tot,), dtype=torch.float32, device=dev)
+        if mode == "invariant":
+            work = torch.empty((max(_lib.load().iso_splat_vrk_h_global_work_bytes(N), 1),), dtype=torch.uint8, device=dev)
+            plen = dists.shape[1] if padded_len is None else int(padded_len)
+            if plen < dists.shape[1]:
+                raise ValueError("per_point_info: padded_len %d is shorter than a cloud of this call (%d)" % (plen, mx))
+            _lib.call("iso_splat_vrk_h_global", p(dists), p(first), p(num), p(h), N, dists.shape[1], plen, p(work), s)
+        else:
+            _lib.call("iso_splat_vrk_h", p(dists), p(first), p(num), None, p(h), N, dists.shape[1], s)
+        self._Vrk_h = h
         _lib.call("iso_splat_setup", p(points_f), p(normals_f), p(h), p(first), p(num), p(_f32c(views)),
-                  p(_f32c(projs)), N, mx, min(image_hw(rs.image_size)), float(rs.antialiasing_sigma),
-                  float(rs.cutoff_threshold), p(ndc), p(ellipse), p(cutoff), p(radii), p(scaler), s)
-        return ndc, {"radii": radii, "ellipse_params": ellipse, "cutoff_threshold": cutoff, "scaler": scaler}
+                  p(_f32c(projs)), N, mx, *size, p(ndc), p(ellipse), p(cutoff), p(radii), p(scaler), s)
+        return out
+
+    def filter_job(self, points, normals, views):
+        """First half of the filtered route: filter_renderable + the packed layout of one cloud seen by N cameras.  One host
+        read (the view lengths)."""
+        P, N = points.shape[0], views.shape[0]
+        dev = points.device
+        flags, off, lens = self.filter_renderable(points, normals, views)
+        fl = [sum(lens[:i]) for i in range(N)]
+        num = with_host_lengths(torch.tensor(lens, dtype=torch.int64, device=dev), lens)
+        first = with_host_lengths(torch.tensor(fl, dtype=torch.int64, device=dev), fl)
+        fv = flags[:N * P].view(N, P)
+        mask = (fv << torch.arange(N, device=dev, dtype=torch.int32)[:, None]).sum(0).to(torch.int32)
+        view_total = torch.zeros((8,), dtype=torch.int32, device=dev)
+        view_total[:N] = num.to(torch.int32)
+        return {"flags": flags, "off": off, "lens": lens, "first_idx": first, "num_points": num, "mask": mask,
+                "view_total": view_total}
+
+    def front_filtered(self, points, normals, views, projs, features=None, job=None, padded_len=None):
+        """The route of the non-default Vrk modes through forward(): filter_renderable -> compact -> per_point_info, i.e. the
+        neighbours of a row are the points RENDERABLE IN ITS VIEW, as in the reference.  Returns the keys of front() that
+        forward() reads (exact-sized arrays; h_rows = the rows' h or None).  job: what filter_job returned for these
+        inputs; padded_len: see per_point_info (forward() passes the largest view cloud of ALL its jobs, so that the
+        invariant mean is the reference's, which batches them).  Two host reads: the view lengths in filter_job, the raster's
+        pair count in forward()."""
+        P, N = points.shape[0], views.shape[0]
+        dev = points.device
+        job = job if job is not None else self.filter_job(points, normals, views)
+        flags, off, lens, first, num = job["flags"], job["off"], job["lens"], job["first_idx"], job["num_points"]
+        tot = sum(lens)
+        common = {"first_idx": first, "num_points": num, "view_total": job["view_total"], "mask": job["mask"]}
+        if tot == 0:
+            if self.vrk_mode(self.raster_settings) == "anisotropic":
+                raise ValueError("The neighborhood_size argument has to be >= size of each of the point clouds.")
+            z = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)        # noqa: E731
+            return {"ndc": z(0, 3), "ellipse_params": z(0, 3), "cutoff_threshold": z(0), "radii": z(0, 2), "scaler": z(0),
+                    "features": None, "src": torch.empty((0,), dtype=torch.int32, device=dev), "h_rows": None, "capacity": 0,
+                    **common}
+        pts_f = self.compact(points, flags, off, P, tot)
+        nrm_f = self.compact(normals, flags, off, P, tot)
+        feat = self.compact(features, flags, off, P, tot) if features is not None else None
+        # original point of every packed row: the int32 point numbers go through the row compaction as raw 32-bit words
+        ids = torch.arange(P, dtype=torch.int32, device=dev).view(torch.float32)[:, None]
+        src = self.compact(ids, flags, off, P, tot).flatten().view(torch.int32)
+        ndc, info = self.per_point_info(pts_f, nrm_f, first, num, views, projs, padded_len=padded_len)
+        return {"ndc": ndc, **info, "features": feat, "src": src, "h_rows": self._Vrk_h_value, "capacity": tot, **common}
 
     # -- fused front end (section E of the C ABI): no filtered copies, no host read ---------------------
     def front(self, points, normals, views, projs, features=None, features_from_normals=False, grid=None,
@@ -582,8 +675,9 @@ class SurfaceSplatting(object):
         buffer to write ndc / ellipse / radii / scaler / features into (the multi-GPU wire layout)."""
         from . import bricks
         rs = self.raster_settings
-        if rs.Vrk_invariant or not rs.Vrk_isotropic:
-            raise NotImplementedError("only the default isotropic Vrk is built (SURVEY 2.1 #3)")
+        if self.vrk_mode(rs) != "isotropic":
+            raise NotImplementedError("front: the fused front end serves the default isotropic Vrk only; the invariant and the "
+                                      "anisotropic mode take the filtered route (front_filtered; DESIGN.md 3.4b)")
         P, N = points.shape[0], views.shape[0]
         if N > 8:
             raise NotImplementedError("front: at most 8 views per pass (SurfaceSplatting.forward runs it in chunks)")
@@ -731,16 +825,28 @@ class SurfaceSplatting(object):
         else:
             jobs = [(clouds[b], b, b + 1) for b in range(B)]
         parts = []
-        for (pp, nn, ff), v0, v1 in jobs:
+        fused = self.vrk_mode(rs) == "isotropic"           # the other modes: filter -> compact -> per_point_info per job
+        filtered, padded_len = None, None
+        if not fused:
+            # the reference runs _get_per_point_info ONCE on all filtered clouds (:603-610): the invariant mean's padded
+            # length is the largest view cloud of the whole call, not of a job
+            with torch.no_grad():
+                filtered = [self.filter_job(_f32c(pp.detach()), _f32c(nn.detach()), views[v0:v1]) for (pp, nn, _), v0, v1 in jobs]
+            padded_len = max(1, max(n for f in filtered for n in f["lens"]))
+        for j, ((pp, nn, ff), v0, v1) in enumerate(jobs):
             pts, nrm = _f32c(pp.detach()), _f32c(nn.detach())
             wide = ff is not None and ff.shape[1] > 8        # wider than the front end packs: gathered afterwards
             with torch.no_grad():
-                fr = self.front(pts, nrm, views[v0:v1], projs[v0:v1], features=None if wide else ff)
+                if fused:
+                    fr = self.front(pts, nrm, views[v0:v1], projs[v0:v1], features=None if wide else ff)
+                else:
+                    fr = self.front_filtered(pts, nrm, views[v0:v1], projs[v0:v1], features=None if wide else ff,
+                                             job=filtered[j], padded_len=padded_len)
             parts.append((fr, pts, nrm, pp, ff if wide else None))
         # exact-size results: ONE host read of every job's row counts
         one = len(parts) == 1
         binned = None
-        if one and min(S, W) > 0:
+        if one and fused and min(S, W) > 0:
             # one job: the raster's count pass + tile offsets run on the front end's capacity-sized arrays BEFORE the host
             # read below, which then also brings the pair total (no second stop of the queue inside splat_points)
             fr0 = parts[0][0]
@@ -772,6 +878,8 @@ class SurfaceSplatting(object):
                                        rs.image_size)
                     total_pairs = int(binned[0][-1].item())
             self._pair_cap = max(cap_pairs, int(1.25 * total_pairs) + 4096)
+        elif not fused:
+            counts = [n for fr, _, _, _, _ in parts for n in host_lengths(fr["num_points"])]      # (read by filter_renderable)
         else:
             counts = (parts[0][0]["num_points"] if one else torch.cat([fr["num_points"] for fr, _, _, _, _ in parts])).tolist()
         lens = [int(x) for x in counts]
@@ -847,6 +955,9 @@ class SurfaceSplatting(object):
             # the bandwidth of every packed row: view v's rows are a slice (lengths known on the host), gathered view by
             # view (torch.repeat_interleave over 2 M rows was 0.2 ms of the operator-API cycle)
             out = []
+            if not fused:                                    # the filtered route holds the rows' h itself (None: anisotropic)
+                rows = [fr["h_rows"] for fr, _, _, _, _ in parts]
+                return None if any(r is None for r in rows) else (torch.cat(rows, dim=0) if len(rows) > 1 else rows[0])
             for j, (fr, _, _, _, _) in enumerate(parts):
                 v_at, nv, jt = spans[j]
                 jl = lens[v_at:v_at + nv]
