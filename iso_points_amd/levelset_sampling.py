@@ -60,8 +60,14 @@ def true_counts(mask):
     if h is None or getattr(mask, "_iso_true_version", None) != mask._version:
         B = mask.shape[0]
         h = [int(x) for x in torch.count_nonzero(mask.reshape(B, -1), dim=1).tolist()]
-        mask._iso_true, mask._iso_true_version = h, mask._version
+        remember_true_counts(mask, h)
     return h
+
+
+def remember_true_counts(mask, counts):
+    """Hand true_counts a per-cloud count the caller has already read back (the only writer of its cache)."""
+    mask._iso_true, mask._iso_true_version = [int(x) for x in counts], mask._version
+    return mask
 
 
 def full_lengths(points):
@@ -563,8 +569,8 @@ class UniformProjection(LevelSetProjection):
                                            sample_iters=sample_iters or self.sample_iters, **forward_kwargs)
                 c2 = torch.count_nonzero(optimistic.mask.reshape(1, -1), dim=1)
                 both = torch.stack([c1, c2]).tolist()                   # ONE host read for both masks
-                res.mask._iso_true, res.mask._iso_true_version = [int(both[0][0])], res.mask._version
-                optimistic.mask._iso_true, optimistic.mask._iso_true_version = [int(both[1][0])], optimistic.mask._version
+                remember_true_counts(res.mask, both[0])
+                remember_true_counts(optimistic.mask, both[1])
             # (the optimistic order only after a call on this object that saw every point converge: on a partly fitted
             # network it would resample -- and rebuild the grid on -- unconverged points every call for nothing: ADVICE r5)
             self._all_converged_last = true_counts(res.mask) == host_lengths(lengths)

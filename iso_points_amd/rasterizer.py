@@ -99,6 +99,100 @@ def _max_pts(num_points):
     return max(h) if h else 0
 
 
+class TileBins(NamedTuple):
+    """What bin_tiles computed of N packed clouds on an S x W image, for ONE raster_tiles call (the fill advances the
+    cursors).  rows: the packed arrays' length (SurfaceSplatting.forward bins on capacity-sized ones and narrows this once
+    the host has the count: the kernels go by first / num alone).  tile_off[t]: first pair of tile t, [-1] the pair total;
+    cursor[-1]: the fill's overflow flag.  total: the pair list's capacity (>= the pair total), None while unknown."""
+    S: int
+    W: int
+    band: tuple
+    N: int
+    rows: int
+    tile_off: torch.Tensor
+    cursor: torch.Tensor
+    total: Optional[int] = None
+
+
+def _tile_grid(S, W):          # -> (tile rows, tile columns)
+    lib = _lib.load()
+    return (lib.iso_splat_tiles_per_side(S) if S > 0 else 0), (lib.iso_splat_tiles_per_side(W) if W > 0 else 0)
+
+
+def _packed_args(points, ellipse_params, cutoff_thres, radii, first, num):
+    """The arrays of a raster call as the kernels read them (f32 / int64, contiguous), the lengths' host copy kept."""
+    args = _f32c(points), _f32c(ellipse_params), _f32c(cutoff_thres), _f32c(radii), _i64c(first), _i64c(num)
+    if hasattr(num, "_iso_host") and args[5] is not num:
+        with_host_lengths(args[5], host_lengths(num))
+    return args
+
+
+def _fragment_buffers(N, S, W, K, dev, whole):
+    """idx, zbuf, qvalue, occupancy: unset where the raster writes every pixel (whole), else the empty image (-1 / 0)."""
+    def make(shape, dtype, fill):
+        return torch.empty(shape, dtype=dtype, device=dev) if whole else torch.full(shape, fill, dtype=dtype, device=dev)
+    return (make((N, S, W, K), torch.int32, -1), make((N, S, W, K), torch.float32, -1.0),
+            make((N, S, W, K), torch.float32, -1.0), make((N, S, W), torch.float32, 0.0))
+
+
+def bin_tiles(points, radii, first, num, max_pts, image_size, band=None, tile_cnt_ws=None):
+    """The raster's count pass + tile offsets -> TileBins (total=None).  points (rows,3) / radii (rows,2) f32, first / num
+    (N,) int64, contiguous; only the device need know the row counts (max_pts >= every cloud's).  band: (begin, end)
+    tile rows, default all.  tile_cnt_ws: the caller's own zero-on-entry buffer of >= 4 (ntiles + 1) bytes -- owners
+    that capture graphs keep theirs; default: one kept per device and stream."""
+    S, W = image_hw(image_size)
+    dev, N = points.device, num.shape[0]
+    T, TW = _tile_grid(S, W)
+    band = (0, T) if band is None else (int(band[0]), int(band[1]))
+    ntiles = N * T * TW
+    p, s = _lib.ptr, _lib.stream()
+    own_cnt = tile_cnt_ws is not None
+    tile_cnt = (tile_cnt_ws[:4 * (ntiles + 1)] if own_cnt else _zeroed_workspace("tile_cnt", dev, 4 * (ntiles + 1))).view(torch.int32)
+    tile_off = torch.empty((ntiles + 1,), dtype=torch.int32, device=dev)
+    cursor = torch.empty((ntiles + 1,), dtype=torch.int32, device=dev)   # [ntiles] = overflow flag
+    try:
+        # counts -> offsets + cleared cursors in one launch; the counter array is cleared by the pass that reads it
+        _lib.call("iso_splat_bin_count", p(points), p(radii), p(first), p(num), N, int(max_pts), S, W, band[0], band[1], p(tile_cnt), s)
+        _lib.call("iso_splat_tile_offsets", p(tile_cnt), p(tile_off), p(cursor), ntiles + 1, s)
+    except Exception:
+        if not own_cnt:                                   # it may hold counts: never reuse it
+            for k in [k for k, v in _ZEROED.items() if v.data_ptr() == tile_cnt.data_ptr()]:
+                _ZEROED.pop(k, None)
+        raise
+    return TileBins(S, W, band, N, int(points.shape[0]), tile_off, cursor)
+
+
+def raster_tiles(bins, pts, el, cu, ra, first, num, max_pts, depth_merging_thres, K, out=None, split_heavy_tiles=True,
+                 composite_with=None, image_out=None, mark_visible=None, overflow_out=None):
+    """Pair fill + raster of binned clouds (bins.total set; arrays as _packed_args returns them) -> (idx, zbuf, qvalue,
+    occupancy[, image]).  The keywords are splat_points'."""
+    S, W, band, N, dev = bins.S, bins.W, bins.band, bins.N, pts.device
+    assert bins.total is not None and N == num.shape[0] and bins.rows == pts.shape[0], "raster_tiles: not these clouds' bins"
+    T, TW = _tile_grid(S, W)
+    ntiles = bins.tile_off.numel() - 1
+    idx, zbuf, qv, occ = out if out is not None else _fragment_buffers(N, S, W, K, dev, band == (0, T))
+    assert idx.shape == (N, S, W, K), "raster_tiles: the fragments are not of the bins' image"
+    pairs = torch.empty((max(bins.total, 1),), dtype=torch.int32, device=dev)
+    if overflow_out is not None:
+        overflow_out.append(bins.cursor[ntiles:])
+    rws_b = _lib.load().iso_splat_forward_workspace_bytes(N * TW * (band[1] - band[0]), K) if split_heavy_tiles else 0
+    rws = torch.empty((rws_b,), dtype=torch.uint8, device=dev) if rws_b else None
+    p = _lib.ptr
+    common = (p(pts), p(el), p(cu), p(ra), p(first), p(num), N, int(max_pts), float(depth_merging_thres), S, W, K,
+              band[0], band[1], p(bins.cursor), p(bins.tile_off), p(pairs), int(bins.total),
+              _lib.ctypes.c_void_p(bins.cursor.data_ptr() + 4 * ntiles), p(idx), p(zbuf), p(qv), p(occ), p(rws), rws_b)
+    if composite_with is None:
+        _lib.call("iso_splat_forward", *common, _lib.stream())
+        return idx, zbuf, qv, occ
+    sc_, ft_, norm_, eps_ = composite_with
+    C = ft_.shape[1]
+    img = image_out if image_out is not None else (
+        (torch.empty if band == (0, T) else torch.zeros)((N, S, W, C + 1), dtype=torch.float32, device=dev))
+    _lib.call("iso_splat_render_visible", *common, p(_f32c(sc_)), p(_f32c(ft_)), C, int(bool(norm_)), float(eps_), p(img),
+              p(mark_visible), _lib.stream())
+    return idx, zbuf, qv, occ, img
+
+
 class _CNamespace(object):
     """Drop-in for `from DSS import _C` (ext.cpp:5-18)."""
 
@@ -119,7 +213,7 @@ class _CNamespace(object):
         bin_size / max_points_per_bin are accepted and ignored: binning is internal (16x16 tiles,
         exact-size pair list), so the reference's num_bins<22 / max_points_per_bin limits do not
         exist here.  tile_rows=(begin, end) (extension, used by the sharded path) rasterises
-        only that band of 16-pixel tile rows (NDC pixel order) into `out` (or fresh -1/0 tensors)."""
+        only that band of 16-pixel tile rows (NDC pixel order) into `out` (or fresh -1/0 tensors).  tile_cnt_ws: bin_tiles."""
         if not points.is_cuda:
             raise RuntimeError("iso_points_amd._C.splat_points: tensors must be on the GPU; there is no CPU path")
         K = int(points_per_pixel)
@@ -128,113 +222,19 @@ class _CNamespace(object):
             raise RuntimeError("Must have 1 <= points_per_pixel <= %d" % kMaxPointsPerPixel)
         if points.ndim != 2 or points.shape[1] != 3:
             raise RuntimeError("points must have shape (P, 3)")
-        P = points.shape[0]
+        P, N = points.shape[0], num_points_per_cloud.shape[0]
         if ellipse_params.shape != (P, 3) or radii.shape != (P, 2) or cutoff_thres.shape != (P,):
             raise RuntimeError("ellipse_params (P,3), radii (P,2), cutoff_thres (P,) expected")
-        dev = points.device
-        N = num_points_per_cloud.shape[0]
-        done = getattr(num_points_per_cloud, "_iso_done", None)          # SurfaceSplatting.forward: rasterised already
-        if done is not None:
-            del num_points_per_cloud._iso_done
-            if done[0] == (S, W, N, K, P) and tile_rows is None and out is None and composite_with is None:
-                return done[1]
-        pts, el, cu, ra = _f32c(points), _f32c(ellipse_params), _f32c(cutoff_thres), _f32c(radii)
-        first, num = _i64c(cloud_to_packed_first_idx), _i64c(num_points_per_cloud)
-        if hasattr(num_points_per_cloud, "_iso_host") and num is not num_points_per_cloud:
-            with_host_lengths(num, host_lengths(num_points_per_cloud))
-        lib = _lib.load()
-        T = lib.iso_splat_tiles_per_side(S) if S > 0 else 0           # tile rows
-        TW = lib.iso_splat_tiles_per_side(W) if W > 0 else 0          # tile columns
-        band = (0, T) if tile_rows is None else (int(tile_rows[0]), int(tile_rows[1]))
-        if out is not None:
-            idx, zbuf, qv, occ = out
-        elif band == (0, T):
-            idx = torch.empty((N, S, W, K), dtype=torch.int32, device=dev)
-            zbuf = torch.empty((N, S, W, K), dtype=torch.float32, device=dev)
-            qv = torch.empty((N, S, W, K), dtype=torch.float32, device=dev)
-            occ = torch.empty((N, S, W), dtype=torch.float32, device=dev)
-        else:
-            idx = torch.full((N, S, W, K), -1, dtype=torch.int32, device=dev)
-            zbuf = torch.full((N, S, W, K), -1.0, dtype=torch.float32, device=dev)
-            qv = torch.full((N, S, W, K), -1.0, dtype=torch.float32, device=dev)
-            occ = torch.zeros((N, S, W), dtype=torch.float32, device=dev)
+        pts, el, cu, ra, first, num = _packed_args(points, ellipse_params, cutoff_thres, radii, cloud_to_packed_first_idx,
+                                                   num_points_per_cloud)
         if N == 0 or S == 0 or W == 0:
-            return idx, zbuf, qv, occ
-        ntiles = N * T * TW
+            return tuple(out) if out is not None else _fragment_buffers(N, S, W, K, points.device, True)
         maxp = int(max_pts) if max_pts is not None else _max_pts(num)
-        p, s = _lib.ptr, _lib.stream()
-        # counts -> offsets + cleared cursors in one launch; the counter array is cleared by the pass that reads it
-        # (tile_cnt_ws: the caller's own zero-on-entry buffer of >= 4 (ntiles + 1) bytes -- owners that capture graphs keep
-        #  theirs; default: one kept per device and stream)
-        own_cnt = tile_cnt_ws is not None
-        tile_cnt = (tile_cnt_ws[:4 * (ntiles + 1)] if own_cnt else _zeroed_workspace("tile_cnt", dev, 4 * (ntiles + 1))).view(torch.int32)
-        tile_off = torch.empty((ntiles + 1,), dtype=torch.int32, device=dev)
-        cursor = torch.empty((ntiles + 1,), dtype=torch.int32, device=dev)   # [ntiles] = overflow flag
-        binned = getattr(num_points_per_cloud, "_iso_binned", None)      # SurfaceSplatting.forward: see prebin()
-        if binned is not None and binned[0] == (S, W, band, N, P):
-            tile_off, cursor, total = binned[1]
-            del num_points_per_cloud._iso_binned
-        else:
-            try:
-                _lib.call("iso_splat_bin_count", p(pts), p(ra), p(first), p(num), N, maxp, S, W, band[0], band[1],
-                          p(tile_cnt), s)
-                _lib.call("iso_splat_tile_offsets", p(tile_cnt), p(tile_off), p(cursor), ntiles + 1, s)
-            except Exception:
-                if not own_cnt:                                   # it may hold counts: never reuse it
-                    for k in [k for k, v in _ZEROED.items() if v.data_ptr() == tile_cnt.data_ptr()]:
-                        _ZEROED.pop(k, None)
-                raise
-            if pair_capacity is None:
-                total = int(tile_off[ntiles].item())      # the one host read of the forward pass
-            else:
-                total = int(pair_capacity)
-        pairs = torch.empty((max(total, 1),), dtype=torch.int32, device=dev)
-        if overflow_out is not None:
-            overflow_out.append(cursor[ntiles:])
-        rws_b = lib.iso_splat_forward_workspace_bytes(N * TW * (band[1] - band[0]), K) if split_heavy_tiles else 0
-        rws = torch.empty((rws_b,), dtype=torch.uint8, device=dev) if rws_b else None
-        if composite_with is not None:
-            sc_, ft_, norm_, eps_ = composite_with
-            C = ft_.shape[1]
-            img = image_out if image_out is not None else (
-                torch.empty((N, S, W, C + 1), dtype=torch.float32, device=dev) if band == (0, T)
-                else torch.zeros((N, S, W, C + 1), dtype=torch.float32, device=dev))
-            # mark_visible: (P,) uint8, zero over the clouds' rows -- the lists' points are marked while they are written
-            _lib.call("iso_splat_render_visible", p(pts), p(el), p(cu), p(ra), p(first), p(num), N, maxp,
-                      float(depth_merging_thres), S, W, K, band[0], band[1], p(cursor), p(tile_off), p(pairs), total,
-                      _lib.ctypes.c_void_p(cursor.data_ptr() + 4 * ntiles), p(idx), p(zbuf), p(qv), p(occ), p(rws), rws_b,
-                      p(_f32c(sc_)), p(_f32c(ft_)), C, int(bool(norm_)), float(eps_), p(img), p(mark_visible), s)
-            return idx, zbuf, qv, occ, img
-        _lib.call("iso_splat_forward", p(pts), p(el), p(cu), p(ra), p(first), p(num), N, maxp,
-                  float(depth_merging_thres), S, W, K, band[0], band[1], p(cursor), p(tile_off), p(pairs), total,
-                  _lib.ctypes.c_void_p(cursor.data_ptr() + 4 * ntiles), p(idx), p(zbuf), p(qv), p(occ), p(rws), rws_b, s)
-        return idx, zbuf, qv, occ
-
-    @staticmethod
-    def prebin(points, radii, first, num, max_pts, image_size):
-        """The count pass and the tile offsets of splat_points on arrays whose row counts only the device knows yet
-        (first / num (N,) int64 device tensors, max_pts >= every cloud's rows): SurfaceSplatting.forward issues them before
-        its one host read, which then brings back the row counts AND the pair total (tile_off[-1]) -- splat_points no
-        longer stops the queue between the offsets and the fill.  Returns (tile_off, cursor); attach
-        ((S, W, band, N, rows), (tile_off, cursor, total)) to the num tensor splat_points will be given as `_iso_binned`."""
-        S, W = image_hw(image_size)
-        dev = points.device
-        N = num.shape[0]
-        lib = _lib.load()
-        T, TW = lib.iso_splat_tiles_per_side(S), lib.iso_splat_tiles_per_side(W)
-        ntiles = N * T * TW
-        p, s = _lib.ptr, _lib.stream()
-        tile_cnt = _zeroed_workspace("tile_cnt", dev, 4 * (ntiles + 1)).view(torch.int32)
-        tile_off = torch.empty((ntiles + 1,), dtype=torch.int32, device=dev)
-        cursor = torch.empty((ntiles + 1,), dtype=torch.int32, device=dev)
-        try:
-            _lib.call("iso_splat_bin_count", p(points), p(radii), p(first), p(num), N, int(max_pts), S, W, 0, T, p(tile_cnt), s)
-            _lib.call("iso_splat_tile_offsets", p(tile_cnt), p(tile_off), p(cursor), ntiles + 1, s)
-        except Exception:
-            for k in [k for k, v in _ZEROED.items() if v.data_ptr() == tile_cnt.data_ptr()]:
-                _ZEROED.pop(k, None)
-            raise
-        return tile_off, cursor, (S, W, (0, T), N)
+        bins = bin_tiles(pts, ra, first, num, maxp, image_size, band=tile_rows, tile_cnt_ws=tile_cnt_ws)
+        total = int(pair_capacity if pair_capacity is not None else bins.tile_off[-1].item())      # (the one host read)
+        return raster_tiles(bins._replace(total=total), pts, el, cu, ra, first, num, maxp, depth_merging_thres, K, out=out,
+                            split_heavy_tiles=split_heavy_tiles, composite_with=composite_with, image_out=image_out,
+                            mark_visible=mark_visible, overflow_out=overflow_out)
 
     @staticmethod
     def _splat_points_naive(points, ellipse_params, cutoff_thres, radii, cloud_to_packed_first_idx,
@@ -347,11 +347,7 @@ class _CNamespace(object):
         if ellipse_params.shape != (P, 3) or radii.shape != (P, 2) or cutoff_thres.shape != (P,):
             raise RuntimeError("ellipse_params (P,3), radii (P,2), cutoff_thres (P,) expected")
         N, M = bin_points.shape[0], bin_points.shape[3]
-        dev = points.device
-        idx = torch.empty((N, S, S, K), dtype=torch.int32, device=dev)
-        zbuf = torch.empty((N, S, S, K), dtype=torch.float32, device=dev)
-        qv = torch.empty((N, S, S, K), dtype=torch.float32, device=dev)
-        occ = torch.empty((N, S, S), dtype=torch.float32, device=dev)
+        idx, zbuf, qv, occ = _fragment_buffers(N, S, S, K, points.device, True)
         p = _lib.ptr
         _lib.call("iso_rasterize_fine", p(_f32c(points)), p(_f32c(ellipse_params)), p(_f32c(cutoff_thres)), p(_f32c(radii)),
                   P, p(bin_points.to(torch.int32).contiguous()), N, M, float(depth_merging_thres), S, bs, K, p(idx), p(zbuf),
@@ -389,7 +385,8 @@ def _zeroed_workspace(tag, dev, nbytes):
     have read instead of starting with a clearing pass): cleared once, when it is first made, and kept per device AND
     STREAM -- two calls on different streams would otherwise share counters in flight.  Never made while the stream is
     capturing (the buffer would live in the graph's private pool and be handed to eager code later): a caller that
-    captures passes its own workspace (`ws=` of median_radius; IsoCycle does)."""
+    captures passes its own workspace (IsoCycle does).  Callers: bin_tiles (tag "tile_cnt", own: `tile_cnt_ws=`) and
+    median_radius (own: `ws=`); each evicts the buffer from _ZEROED when its launch fails, as it may be dirty then."""
     stream = torch.cuda.current_stream(dev).cuda_stream
     key = (tag, dev.index, int(nbytes), int(stream))
     ws = _ZEROED.get(key)
@@ -437,11 +434,19 @@ class EllipticalRasterizer(autograd.Function):
     @staticmethod
     def forward(ctx, pts_screen, ellipse_param, cutoff_threshold, radii, cloud_to_packed_first_idx,
                 num_points_per_cloud, depth_merging_threshold, image_size, points_per_pixel,
-                bin_size=0, max_points_per_bin=0, radii_backward_scaler=10.0):
-        idx, zbuf, qvalue_map, occ_map = _C.splat_points(
+                bin_size=0, max_points_per_bin=0, radii_backward_scaler=10.0, prepared=None):
+        """prepared (extension, no tensor): what the caller has computed of this call already, from these very inputs -- a
+        TileBins with its total (no binning here) or the finished (idx, zbuf, qvalue, occupancy) (only the context is set up)."""
+        N, K, hw = num_points_per_cloud.shape[0], int(points_per_pixel), image_hw(image_size)
+        if isinstance(prepared, TileBins):
+            assert prepared[:5] == (*hw, (0, _tile_grid(*hw)[0]), N, pts_screen.shape[0]), "not this call's binning"
+            args = _packed_args(pts_screen, ellipse_param, cutoff_threshold, radii, cloud_to_packed_first_idx, num_points_per_cloud)
+            prepared = raster_tiles(prepared, *args, _max_pts(args[5]), depth_merging_threshold, K)
+        idx, zbuf, qvalue_map, occ_map = prepared if prepared is not None else _C.splat_points(
             pts_screen, ellipse_param, cutoff_threshold, radii, cloud_to_packed_first_idx,
             num_points_per_cloud, depth_merging_threshold, image_size, points_per_pixel, bin_size,
             max_points_per_bin)
+        assert idx.shape == (N, *hw, K), "not this call's fragments"
         ctx.radii_backward_scaler = radii_backward_scaler
         ctx.depth_merging_threshold = depth_merging_threshold
         ctx.host = (host_lengths(cloud_to_packed_first_idx), host_lengths(num_points_per_cloud))
@@ -468,15 +473,15 @@ class EllipticalRasterizer(autograd.Function):
         covered = sum(nl) == pts_screen.shape[0] and all(fl[i] == sum(nl[:i]) for i in range(len(nl)))
         grads = _C._backward(pts_screen, radii, occ_grad, first_idx, num_points, visible=vis, rs=rs,
                              idx=idx, grad_zbuf=zbuf_grad, rows_covered=covered)
-        return (grads, None, None, None, None, None, None, None, None, None, None, None)
+        return (grads, None, None, None, None, None, None, None, None, None, None, None, None)
 
 
 def rasterize_elliptical_points(pcls_screen, ellipse_params, cutoff_threshold, radii,
                                 depth_merging_threshold: float = 0.05, image_size: int = 512,
                                 points_per_pixel: int = 5, bin_size: Optional[int] = None,
                                 max_points_per_bin: Optional[int] = None,
-                                radii_backward_scaler: float = 10.0, clip_pts_grad: float = -1.0):
-    """rasterizer.py:678-740."""
+                                radii_backward_scaler: float = 10.0, clip_pts_grad: float = -1.0, prepared=None):
+    """rasterizer.py:678-740.  prepared: see EllipticalRasterizer.forward."""
     points_packed = pcls_screen.points_packed()
     first = pcls_screen.cloud_to_packed_first_idx()
     num = pcls_screen.num_points_per_cloud()
@@ -488,7 +493,7 @@ def rasterize_elliptical_points(pcls_screen, ellipse_params, cutoff_threshold, r
         points_packed.register_hook(_clip)
     return EllipticalRasterizer.apply(points_packed, ellipse_params, cutoff_threshold, radii, first, num,
                                       depth_merging_threshold, image_size, points_per_pixel, bin_size or 0,
-                                      max_points_per_bin or 0, radii_backward_scaler)
+                                      max_points_per_bin or 0, radii_backward_scaler, prepared)
 
 
 # ----------------------------------------------------------------------------- SurfaceSplatting
@@ -808,24 +813,29 @@ class SurfaceSplatting(object):
         feature width.  Returns (PointFragments, filtered dict): the packed rows are view-major / cloud-major in
         ascending point order -- the reference's packed layout."""
         clouds = self._clouds_of(points, normals, features)
-        views, projs = self._camera_matrices(cameras if cameras is not None else self.cameras)
-        views, projs = _f32c(views), _f32c(projs)
-        rs = self.raster_settings
-        N, B = views.shape[0], len(clouds)
+        views, projs = (_f32c(m) for m in self._camera_matrices(cameras if cameras is not None else self.cameras))
+        jobs = self._plan_jobs(clouds, views.shape[0])
+        fused = self.vrk_mode(self.raster_settings) == "isotropic"
+        parts = self._run_front_ends(jobs, views, projs, fused)
+        ahead = len(parts) == 1 and fused and min(image_hw(self.raster_settings.image_size)) > 0
+        issued = self._issue_before_read(parts[0][0], parts[0][1].shape[0]) if ahead else (None, None, [])
+        lens, prepared = self._read_row_counts(parts, fused, *issued)
+        return self._assemble(len(clouds), jobs, parts, lens, prepared, views, projs, fused)
+
+    @staticmethod
+    def _plan_jobs(clouds, N):
+        """[(cloud, first view, end view)]: one cloud + a run of at most 8 cameras each (iso_splat_front's pass width)."""
+        B = len(clouds)
         if B != 1 and B != N:
             raise ValueError("SurfaceSplatting.forward: %d clouds need %d cameras (or one cloud for any number), got %d"
                              % (B, B, N))
-        dev = views.device
-        (S, W), K = image_hw(rs.image_size), int(rs.points_per_pixel)
-        # jobs: one cloud + a run of at most 8 cameras each (iso_splat_front's pass width)
-        jobs = []
         if B == 1:
-            for v0 in range(0, N, 8):
-                jobs.append((clouds[0], v0, min(v0 + 8, N)))
-        else:
-            jobs = [(clouds[b], b, b + 1) for b in range(B)]
-        parts = []
-        fused = self.vrk_mode(rs) == "isotropic"           # the other modes: filter -> compact -> per_point_info per job
+            return [(clouds[0], v0, min(v0 + 8, N)) for v0 in range(0, N, 8)]
+        return [(clouds[b], b, b + 1) for b in range(B)]
+
+    def _run_front_ends(self, jobs, views, projs, fused):
+        """The front end of every job (fused: front(); the other Vrk modes: filter -> compact -> per_point_info) ->
+        [(front dict, points, normals, the caller's points, features wider than the front end packs or None)]."""
         filtered, padded_len = None, None
         if not fused:
             # the reference runs _get_per_point_info ONCE on all filtered clouds (:603-610): the invariant mean's padded
@@ -833,6 +843,7 @@ class SurfaceSplatting(object):
             with torch.no_grad():
                 filtered = [self.filter_job(_f32c(pp.detach()), _f32c(nn.detach()), views[v0:v1]) for (pp, nn, _), v0, v1 in jobs]
             padded_len = max(1, max(n for f in filtered for n in f["lens"]))
+        parts = []
         for j, ((pp, nn, ff), v0, v1) in enumerate(jobs):
             pts, nrm = _f32c(pp.detach()), _f32c(nn.detach())
             wide = ff is not None and ff.shape[1] > 8        # wider than the front end packs: gathered afterwards
@@ -843,60 +854,52 @@ class SurfaceSplatting(object):
                     fr = self.front_filtered(pts, nrm, views[v0:v1], projs[v0:v1], features=None if wide else ff,
                                              job=filtered[j], padded_len=padded_len)
             parts.append((fr, pts, nrm, pp, ff if wide else None))
-        # exact-size results: ONE host read of every job's row counts
-        one = len(parts) == 1
-        binned = None
-        if one and fused and min(S, W) > 0:
-            # one job: the raster's count pass + tile offsets run on the front end's capacity-sized arrays BEFORE the host
-            # read below, which then also brings the pair total (no second stop of the queue inside splat_points)
-            fr0 = parts[0][0]
-            with torch.no_grad():
-                binned = _C.prebin(fr0["ndc"], fr0["radii"], fr0["first_idx"], fr0["num_points"], parts[0][1].shape[0],
-                                   rs.image_size)
-        early, ovf = None, []
-        cap_pairs = int(getattr(self, "_pair_cap", 0))
-        if binned is not None and cap_pairs > 0 and not os.environ.get("ISO_OPAPI_SYNC"):      # (the variable: A/B of the two orders)
-            # ... and with a pair capacity known from earlier calls (1.25 x the largest total seen) the fill and the raster
-            # themselves are ISSUED before the read, on the capacity-sized arrays (the kernels take the row counts from the
-            # device): the host reads row counts, pair total and overflow flag while the GPU rasterises.  An overflow
-            # (a frame with > 1.25 x the pairs of every earlier one) discards the result and takes the exact path.
-            fr0 = parts[0][0]
-            with torch.no_grad():
-                fr0["num_points"]._iso_binned = (binned[2] + (int(fr0["ndc"].shape[0]),), (binned[0], binned[1], cap_pairs))
-                early = _C.splat_points(fr0["ndc"], fr0["ellipse_params"], fr0["cutoff_threshold"], fr0["radii"],
-                                        fr0["first_idx"], fr0["num_points"], rs.depth_merging_threshold, rs.image_size, K,
-                                        max_pts=parts[0][1].shape[0], overflow_out=ovf)
-        if one and binned is not None:
-            extra = [binned[0][-1:].long()] + ([ovf[0].reshape(1).long()] if early is not None else [])
-            both = torch.cat([parts[0][0]["num_points"]] + extra).tolist()          # ONE host read
-            counts, total_pairs = both[:N], int(both[N])
-            if early is not None and (int(both[N + 1]) != 0 or total_pairs > cap_pairs):
-                early = None                                                        # pair list overflowed: exact path below
-                with torch.no_grad():                                               # (the counters were consumed: count again)
-                    fr0 = parts[0][0]
-                    binned = _C.prebin(fr0["ndc"], fr0["radii"], fr0["first_idx"], fr0["num_points"], parts[0][1].shape[0],
-                                       rs.image_size)
-                    total_pairs = int(binned[0][-1].item())
-            self._pair_cap = max(cap_pairs, int(1.25 * total_pairs) + 4096)
-        elif not fused:
-            counts = [n for fr, _, _, _, _ in parts for n in host_lengths(fr["num_points"])]      # (read by filter_renderable)
-        else:
-            counts = (parts[0][0]["num_points"] if one else torch.cat([fr["num_points"] for fr, _, _, _, _ in parts])).tolist()
-        lens = [int(x) for x in counts]
-        tot = sum(lens)
-        if binned is not None:
-            binned = (binned[2] + (tot,), (binned[0], binned[1], total_pairs))
-        fl = [sum(lens[:i]) for i in range(N)]
-        if one:                # the front end's own device-side layout (no host -> device copies of what the device has)
-            num = with_host_lengths(parts[0][0]["num_points"], lens)
-            first = with_host_lengths(parts[0][0]["first_idx"], fl)
-            if early is not None and tot > 0:
-                num._iso_done = ((S, W, N, K, tot), early)
-            elif binned is not None and tot > 0:
-                num._iso_binned = binned
-        else:
-            num = with_host_lengths(torch.tensor(lens, dtype=torch.int64, device=dev), lens)
-            first = with_host_lengths(torch.tensor(fl, dtype=torch.int64, device=dev), fl)
+        return parts
+
+    def _bin_front(self, fr, max_pts):
+        return bin_tiles(fr["ndc"], fr["radii"], fr["first_idx"], fr["num_points"], max_pts, self.raster_settings.image_size)
+
+    def _issue_before_read(self, fr, max_pts):
+        """One fused job: what of the raster is queued on the front end's capacity-sized arrays while only the device knows
+        the row counts -> (TileBins, early fragments or None, the (1,) int64 tensors the host read must bring along).
+        Always the binning: the read then brings the pair total too, and the raster call does not stop the queue again.
+        With _pair_cap (1.25 x the largest total of earlier calls) also the fill and the raster: the host reads counts,
+        total and overflow flag while the GPU rasterises.  (ISO_OPAPI_SYNC: A/B of the two orders.)"""
+        rs, cap_pairs = self.raster_settings, int(getattr(self, "_pair_cap", 0))
+        bins, early, ovf = self._bin_front(fr, max_pts), None, []
+        if cap_pairs > 0 and not os.environ.get("ISO_OPAPI_SYNC"):
+            early = raster_tiles(bins._replace(total=cap_pairs), fr["ndc"], fr["ellipse_params"], fr["cutoff_threshold"],
+                                 fr["radii"], fr["first_idx"], fr["num_points"], max_pts, rs.depth_merging_threshold,
+                                 int(rs.points_per_pixel), overflow_out=ovf)
+        return bins, early, [bins.tile_off[-1:].long()] + [o.reshape(1).long() for o in ovf]
+
+    def _read_row_counts(self, parts, fused, bins, early, extra):
+        """The ONE host read of forward(): every job's row counts, with them what _issue_before_read asked for -> (rows per
+        view, the raster call's `prepared`: early fragments, TileBins with their total, or None).  An early raster whose
+        pair list overflowed (a frame with > 1.25 x the pairs of every earlier one) is dropped here for the exact path."""
+        if not fused:                                         # (read by filter_renderable)
+            return [n for fr, _, _, _, _ in parts for n in host_lengths(fr["num_points"])], None
+        nums = [fr["num_points"] for fr, _, _, _, _ in parts] + extra
+        both = [int(x) for x in (nums[0] if len(nums) == 1 else torch.cat(nums)).tolist()]
+        if bins is None:
+            return both, None
+        N, cap_pairs = len(both) - len(extra), int(getattr(self, "_pair_cap", 0))
+        total_pairs = both[N]
+        if early is not None and (both[N + 1] != 0 or total_pairs > cap_pairs):
+            early = None
+            bins = self._bin_front(parts[0][0], parts[0][1].shape[0])          # (the fill consumed the cursors: count again)
+            total_pairs = int(bins.tile_off[-1].item())
+        self._pair_cap = max(cap_pairs, int(1.25 * total_pairs) + 4096)
+        return both[:N], early if early is not None else bins._replace(rows=sum(both[:N]), total=total_pairs)
+
+    def _assemble(self, B, jobs, parts, lens, prepared, views, projs, fused):
+        """Packed layout, columns, the raster call and the lazy `filtered` dictionary -> forward()'s result."""
+        rs, N, dev = self.raster_settings, views.shape[0], views.device
+        (S, W), K = image_hw(rs.image_size), int(rs.points_per_pixel)
+        tot, fl = sum(lens), [sum(lens[:i]) for i in range(N)]
+        one = len(parts) == 1      # one job: the front end's own device-side layout (no host -> device copy of what the device has)
+        num = with_host_lengths(parts[0][0]["num_points"] if one else torch.tensor(lens, dtype=torch.int64, device=dev), lens)
+        first = with_host_lengths(parts[0][0]["first_idx"] if one else torch.tensor(fl, dtype=torch.int64, device=dev), fl)
 
         def make_flags():
             flags_jobs = [((fr["mask"][None] >> torch.arange(v1 - v0, device=dev)[:, None]) & 1).to(torch.int32)
@@ -910,12 +913,9 @@ class SurfaceSplatting(object):
             return flags
 
         if tot == 0:
-            flags = make_flags()
-            idx = torch.full((N, S, W, K), -1, dtype=torch.int32, device=dev)
-            neg = torch.full((N, S, W, K), -1.0, dtype=torch.float32, device=dev)
-            occ = torch.zeros((N, S, W), dtype=torch.float32, device=dev)
-            return PointFragments(idx, neg, neg.clone(), neg.clone(), occ), {"num_points": num, "first_idx": first,
-                                                                             "flags": flags}
+            idx, zbuf, qv, occ = _fragment_buffers(N, S, W, K, dev, False)
+            return PointFragments(idx, zbuf, qv, qv.clone(), occ), {"num_points": num, "first_idx": first,
+                                                                     "flags": make_flags()}
         # Columns of the packed rows.  What the raster needs is built now; the rest of the reference's `filtered` dictionary
         # (gathered points / normals / wide features, int64 src, flags, visibility, the rows' bandwidths) on first access.
         cols = {k: [] for k in ("radii", "ellipse_params", "cutoff_threshold", "scaler", "ndc", "features")}
@@ -923,8 +923,7 @@ class SurfaceSplatting(object):
         v_at = 0
         for (fr, pts, nrm, pp, wide_ff), (_, v0, v1) in zip(parts, jobs):
             nv = v1 - v0
-            jl = lens[v_at:v_at + nv]
-            jt = sum(jl)
+            jt = sum(lens[v_at:v_at + nv])
             spans.append((v_at, nv, jt))
             for k in ("radii", "ellipse_params", "cutoff_threshold", "scaler"):
                 cols[k].append(fr[k][:jt])
@@ -974,7 +973,7 @@ class SurfaceSplatting(object):
             PackedClouds(ndc, first, num), info["ellipse_params"], info["cutoff_threshold"], info["radii"],
             depth_merging_threshold=rs.depth_merging_threshold, image_size=rs.image_size, points_per_pixel=K,
             bin_size=rs.bin_size, max_points_per_bin=rs.max_points_per_bin,
-            radii_backward_scaler=rs.radii_backward_scaler, clip_pts_grad=rs.clip_pts_grad)
+            radii_backward_scaler=rs.radii_backward_scaler, clip_pts_grad=rs.clip_pts_grad, prepared=prepared)
         frag_scaler = gather_with_neg_idx(info["scaler"], idx)
         frags = PointFragments(idx, zbuf, qv, frag_scaler, occ)
 

@@ -362,6 +362,49 @@ def test_heavy_tiles_in_slices_equal_whole_tiles(dev, P, S, K):
         assert torch.equal(r[4], composite(PointFragments(a[0], a[1], a[2], None, a[3]), scal, feat, norm_weighted=norm))
 
 
+def test_forward_hands_its_binning_on_explicitly(dev):
+    """SurfaceSplatting.forward issues the raster's binning (and, from its second call on, the raster itself) before its
+    host read and hands the result to the raster call as an argument.  Nothing of it rides on the lengths tensors it
+    returns: rasterising ANOTHER cloud of the same row count with those very tensors equals doing so with fresh copies.
+    And rasterize_elliptical_points(prepared=TileBins of its inputs) equals the call without."""
+    from iso_points_amd.levelset_sampling import host_lengths
+    from iso_points_amd.rasterizer import (PackedClouds, PointsRasterizationSettings, SurfaceSplatting, _C, bin_tiles,
+                                           rasterize_elliptical_points)
+    SO = _SO()
+    N, S, K = 2, 96, 6
+    views = torch.stack([SO.look_at_view(3.0, 20.0, 180.0 * i) for i in range(N)]).to(dev)
+    projs = views @ SO.perspective(30.0).to(dev)
+    rs = PointsRasterizationSettings(image_size=S, points_per_pixel=K)
+    a = torch.nn.functional.normalize(torch.randn(20000, 3, generator=torch.Generator().manual_seed(5)), dim=-1).to(dev)
+    ss = SurfaceSplatting(raster_settings=rs)
+    ss.forward(a, a.clone(), cameras=(views, projs))                     # exact path; learns a pair capacity
+    assert ss._pair_cap > 0
+    frags, filt = ss.forward(a, a.clone(), cameras=(views, projs))       # early path
+    first, num = filt["first_idx"], filt["num_points"]
+    # cloud b: a's rows mirrored in x (same row count, other pixels)
+    ndc_b = (filt["ndc"] * torch.tensor([-1.0, 1.0, 1.0], device=dev)).contiguous()
+    el, cu, ra = filt["ellipse_params"], filt["cutoff_threshold"], filt["radii"]
+    thres = rs.depth_merging_threshold
+    got = _C.splat_points(ndc_b, el, cu, ra, first, num, thres, S, K, 0, 0)
+    ref = _C.splat_points(ndc_b, el, cu, ra, first.clone(), num.clone(), thres, S, K, 0, 0)
+    for g, r in zip(got, ref):
+        assert torch.equal(g, r)
+    assert not torch.equal(got[0], frags.idx) and (got[0] >= 0).float().mean() > 0.2
+
+    def raster(prepared):
+        return rasterize_elliptical_points(PackedClouds(ndc_b, first, num), el, cu, ra, depth_merging_threshold=thres,
+                                           image_size=S, points_per_pixel=K, prepared=prepared)
+    bins = bin_tiles(ndc_b, ra, first, num, max(host_lengths(num)), S)
+    assert (bins.S, bins.W, bins.N, bins.rows, bins.total) == (S, S, N, ndc_b.shape[0], None)
+    with_bins = raster(bins._replace(total=int(bins.tile_off[-1].item())))
+    for g, r in zip(with_bins, raster(None)):
+        assert torch.equal(g, r)
+    for g, r in zip(with_bins, ref):
+        assert torch.equal(g, r)
+    for g, r in zip(raster(tuple(ref)), ref):                            # finished fragments: handed through
+        assert torch.equal(g, r)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("H,W", [(96, 160), (160, 96), (100, 130)])
 def test_non_square_image_against_the_square_sub_case(dev, H, W):
