@@ -915,6 +915,52 @@ int iso_splat_median_pass(int pass, const float* radii, const uint8_t* visible, 
                           int64_t workspace_bytes, void* stream);
 int iso_splat_median_final(void* workspace, int n_clouds, float radii_s, float* search_radius_out, void* stream);
 
+/* ----------------------------------------------------------------------
+ * G. Chamfer distance between point clouds (csrc/chamfer.hip)
+ *    replaces pytorch3d.loss.chamfer_distance (CUDA-only, not vendored) where the reference calls it:
+ *      evaluation.py:119-122, :169-172     chamfer_p / chamfer_n of the extracted iso-points
+ *      DSS/training/trainer.py:256         the validation metric train_mvr.py:196 selects checkpoints by
+ *    Both entries enqueue on `stream` and do not synchronise; no float atomics: two runs give the same bits.
+ *
+ * iso_chamfer_nearest: for every valid row i of x (N,P1,3) the exact nearest point of cloud y (N,P2,3), whose grid
+ * (sorted_y, sorted_idx_y, off, grid_params) comes from the build calls of section B at an infinite radius:
+ *   d2_out (N,P1) f32 = (dx*dx + dy*dy) + dz*dz (f32, no FMA contraction), ties -> the lower index of y;
+ *   d2_out and nterm_out may be NULL (the loss needs the indices and the sums only);
+ *   idx_out (N,P1) i32; with normals (both or neither; (N,P,3), any length) nterm_out (N,P1) =
+ *   1 - |cos(x_normals[i], y_normals[idx[i]])|, cos = dot / (max(|a|, 1e-6) max(|b|, 1e-6)).
+ * Rows i >= x_lengths[n], rows with a NaN coordinate and every row of a cloud whose y is empty get d2 = 0, idx = -1,
+ * nterm = 0.  sums_out (N,2) = {sum d2, sum nterm} per cloud: per-workgroup partial sums, added in a fixed order
+ * (64 contiguous chunks, each in index order, then the chunks in order).
+ * workspace: iso_chamfer_nearest_workspace_bytes(N, P1, P2), 16-B aligned.                                          */
+int64_t iso_chamfer_nearest_workspace_bytes(int n_clouds, int64_t p1, int64_t p2);
+int iso_chamfer_nearest(const float* x, const int64_t* x_lengths, const float* sorted_y,
+                        const int32_t* sorted_idx_y, const int64_t* y_lengths, const int32_t* off,
+                        const float* grid_params, const float* x_normals, const float* y_normals,
+                        float* d2_out, int32_t* idx_out, float* nterm_out, float* sums_out, int n_clouds,
+                        int64_t p1, int64_t p2, int64_t g_stride, void* workspace, int64_t workspace_bytes,
+                        void* stream);
+
+/* iso_chamfer_backward: gradient of
+ *   sum_n g_dx[n] sum_i d2(x_i, y[idx_x[i]]) + g_dy[n] sum_j d2(y_j, x[idx_y[j]])
+ * (and of the same two sums of the normal terms, scaled by g_nx / g_ny) w.r.t. both clouds and both normal tensors, in
+ * one call: both sides share every launch (zero, count, three scan phases, fill, two gradient kernels).  Indices are
+ * constants, so the normal terms have no gradient w.r.t. positions.  idx_x (N,P1), idx_y (N,P2): the i32 results of
+ * iso_chamfer_nearest in the two directions (-1 = no term); g_* (N) f32 carry weights, the length and batch
+ * normalisation and the upstream gradient.
+ *   grad_x[i] = 2 g_dx (x_i - y[idx_x[i]]) + 2 g_dy sum_{j: idx_y[j] = i} (x_i - y_j)        (grad_y likewise)
+ * The second part is a gather: the other cloud's indices are counting-sorted by target (integer atomics,
+ * iso_prefix_sum) and each target's list is summed in ascending j by its own lane (up to 8 entries) or by one wave
+ * (sorted up to 1024 entries, beyond that a strided scan of the index row): a fixed order.  Rows beyond a cloud's length
+ * get 0.  grad_x or grad_y may be NULL: that side is skipped; grad_*_normals may be NULL (a normal gradient needs its
+ * cloud's position gradient buffer).  workspace: iso_chamfer_backward_workspace_bytes(N, P1, P2), 16-B aligned.        */
+int64_t iso_chamfer_backward_workspace_bytes(int n_clouds, int64_t p1, int64_t p2);
+int iso_chamfer_backward(const float* x, const float* y, const int64_t* x_lengths, const int64_t* y_lengths,
+                         const int32_t* idx_x, const int32_t* idx_y, const float* g_dx, const float* g_dy,
+                         const float* x_normals, const float* y_normals, const float* g_nx, const float* g_ny,
+                         float* grad_x, float* grad_y, float* grad_x_normals, float* grad_y_normals,
+                         int n_clouds, int64_t p1, int64_t p2, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -145,6 +145,10 @@ SIGNATURES = {
                                   _P, _P, _P, _L, _P, _P]),
     "iso_splat_front": (_I, [_P, _P, _P, _I, _I, _P, _P, _L, _P, _P, _I, _I, _F, _F, _P, _L, _P, _P, _P, _P, _P, _P,
                              _P, _P, _P, _P, _P]),
+    "iso_chamfer_nearest_workspace_bytes": (_L, [_I, _L, _L]),
+    "iso_chamfer_nearest": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _L, _P, _L, _P]),
+    "iso_chamfer_backward_workspace_bytes": (_L, [_I, _L, _L]),
+    "iso_chamfer_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _P, _L, _P]),
 }
 
 class Follow(ctypes.Structure):

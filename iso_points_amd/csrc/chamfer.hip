@@ -1,0 +1,567 @@
+// Chamfer distance between two point clouds on the cell grid of frnn.hip, written for gfx950.
+// Stands in for pytorch3d.loss.chamfer_distance as the reference calls it (include/isopoints.h
+// section G for the call sites).
+//
+//   k_cham_pack     : (x, y, z, original index) record per sorted target point, one 16-B load per candidate
+//   k_cham_nearest  : one lane per query walks the 3x3x3 cell block and at most two more Chebyshev rings
+//                     around its cell (the exact K = 1 search of k_query, same d2 expression, same
+//                     (d2, index) order); a query still open after that is finished by its whole WAVE in
+//                     the same launch, the lanes splitting each further shell's cell columns.  The lane
+//                     then forms the normal term and the workgroup reduces both sums in a fixed order.
+//   k_cham_finish   : adds the workgroups' partial sums of a cloud in a fixed order (64 chunks in index order)
+//   backward        : k_cham_count / iso_prefix_sum / k_cham_fill sort the other cloud's nearest indices by
+//                     target (integer atomics only); k_cham_grad sums each target's list in ascending query
+//                     order, k_cham_grad_heavy serves the long lists with one wave each.  Both clouds' gradients
+//                     run in the same launches (blockIdx.z = the side).  No float atomics: two runs give the
+//                     same bits.
+#include <float.h>
+#include "iso_common.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kRingCap = 2;          // rings a lane walks alone beyond its first (k_query's value)
+constexpr int kNearBlock = 256;
+constexpr int kMaxPartials = 4096;   // workgroups per cloud of k_cham_nearest = partial sums k_cham_finish adds
+constexpr int kLightList = 8;        // targets chosen by at most this many queries are summed by their own lane
+constexpr int kSortList = 1024;      // longer lists are not sorted: the wave scans the whole index row instead
+constexpr float kNormEps = 1e-6f;    // torch.nn.functional.cosine_similarity's eps
+
+__device__ __forceinline__ bool pair_lt(float d1, int i1, float d2, int i2) {
+  return d1 < d2 || (d1 == d2 && i1 < i2);
+}
+
+__global__ void k_cham_pack(const float* __restrict__ sorted, const int32_t* __restrict__ sorted_idx,
+                            const int64_t* __restrict__ lengths, int64_t p_stride, float4* __restrict__ out) {
+  const int n = blockIdx.y;
+  const int64_t len = lengths ? lengths[n] : p_stride;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (int64_t)gridDim.x * blockDim.x) {
+    const float* q = sorted + ((int64_t)n * p_stride + i) * 3;
+    out[(int64_t)n * p_stride + i] = make_float4(q[0], q[1], q[2], __int_as_float(sorted_idx[(int64_t)n * p_stride + i]));
+  }
+}
+
+struct Grid3 {
+  float mnx, mny, mnz, delta, cell;
+  int rx, ry, rz, total;
+};
+
+__device__ __forceinline__ void scan_run(const float4* __restrict__ s4, int64_t i0, int64_t i1, float qx, float qy,
+                                         float qz, float& bd, int& bi) {
+  // two candidates per trip: two independent 16-B loads in flight per lane
+  for (int64_t i = i0; i < i1; i += 2) {
+    const bool two = i + 1 < i1;
+    const float4 ca = s4[i];
+    const float4 cb = s4[two ? i + 1 : i];
+    {
+      const float dx = qx - ca.x, dy = qy - ca.y, dz = qz - ca.z;
+      const float d2 = (dx * dx + dy * dy) + dz * dz;
+      const int oi = __float_as_int(ca.w);
+      if (pair_lt(d2, oi, bd, bi)) { bd = d2; bi = oi; }
+    }
+    if (two) {
+      const float dx = qx - cb.x, dy = qy - cb.y, dz = qz - cb.z;
+      const float d2 = (dx * dx + dy * dy) + dz * dz;
+      const int oi = __float_as_int(cb.w);
+      if (pair_lt(d2, oi, bd, bi)) { bd = d2; bi = oi; }
+    }
+  }
+}
+
+// the cells of column (x, y) that belong to shell rho around (cx, cy, cz): an edge column is one z-run, an
+// interior column its two cap cells
+__device__ __forceinline__ void scan_column(const float4* __restrict__ s4, const int32_t* __restrict__ offn,
+                                            const Grid3& g, int64_t len2, int x, int y, int cx, int cy, int cz, int rho,
+                                            float qx, float qy, float qz, float& bd, int& bi) {
+  const bool edge = (x == cx - rho) || (x == cx + rho) || (y == cy - rho) || (y == cy + rho);
+  const int nseg = (edge || rho == 0) ? 1 : 2;
+  for (int sgm = 0; sgm < nseg; ++sgm) {
+    int za, zb;
+    if (edge) { za = cz - rho; zb = cz + rho; }
+    else if (sgm == 0) { za = cz - rho; zb = cz - rho; }
+    else { za = cz + rho; zb = cz + rho; }
+    za = max(za, 0); zb = min(zb, g.rz - 1);
+    if (za > zb) continue;
+    const int c0 = (x * g.ry + y) * g.rz + za, c1 = (x * g.ry + y) * g.rz + zb;
+    scan_run(s4, offn[c0], (c1 + 1 < g.total) ? (int64_t)offn[c1 + 1] : len2, qx, qy, qz, bd, bi);
+  }
+}
+
+// 1 - |cos(a, b)|, cos = a.b / (max(|a|, eps) max(|b|, eps))
+__device__ __forceinline__ float normal_term(const float* __restrict__ a, const float* __restrict__ b) {
+  const float ax = a[0], ay = a[1], az = a[2], bx = b[0], by = b[1], bz = b[2];
+  const float la = sqrtf((ax * ax + ay * ay) + az * az), lb = sqrtf((bx * bx + by * by) + bz * bz);
+  const float dot = (ax * bx + ay * by) + az * bz;
+  return 1.0f - fabsf(dot / (fmaxf(la, kNormEps) * fmaxf(lb, kNormEps)));
+}
+
+template <bool NORMALS>
+__global__ __launch_bounds__(kNearBlock) void k_cham_nearest(
+    const float* __restrict__ x, const int64_t* __restrict__ x_len, const float4* __restrict__ xyzi,
+    const int64_t* __restrict__ y_len, const int32_t* __restrict__ off, const float* __restrict__ params,
+    const float* __restrict__ x_normals, const float* __restrict__ y_normals, float* __restrict__ d2_out,
+    int32_t* __restrict__ idx_out, float* __restrict__ nterm_out, float* __restrict__ partials, int64_t p1,
+    int64_t p2, int64_t g_stride) {
+  __shared__ float s_sum[kNearBlock / 64][2];
+  const int n = blockIdx.y;
+  const int lane = threadIdx.x & 63;
+  const float4* s4 = xyzi + (int64_t)n * p2;
+  const int64_t len2 = y_len ? y_len[n] : p2;
+  const int64_t len1 = x_len ? x_len[n] : p1;
+  const float* gp = params + n * ISO_GRID3_PARAMS;
+  Grid3 g;
+  g.mnx = gp[0]; g.mny = gp[1]; g.mnz = gp[2]; g.delta = gp[3];
+  g.rx = (int)gp[4]; g.ry = (int)gp[5]; g.rz = (int)gp[6]; g.total = (int)gp[7];
+  g.cell = 1.0f / g.delta;
+  const int32_t* offn = off + (int64_t)n * g_stride;
+  float acc_d = 0.f, acc_n = 0.f;
+
+  // the loop bound is the same in every lane of a wave: the lanes of a wave finish its open queries together
+  for (int64_t t0 = (int64_t)blockIdx.x * kNearBlock; t0 < p1; t0 += (int64_t)gridDim.x * kNearBlock) {
+    const int64_t t = t0 + threadIdx.x;
+    const bool row = t < p1;
+    float qx = 0.f, qy = 0.f, qz = 0.f;
+    float bd = FLT_MAX;
+    int bi = 0x7fffffff;
+    int cx = 0, cy = 0, cz = 0, rho_next = 0, rho_max = -1;
+    bool open = false;
+    if (row && t < len1 && len2 > 0) {
+      const float* q = x + ((int64_t)n * p1 + t) * 3;
+      qx = q[0]; qy = q[1]; qz = q[2];
+    }
+    if (row && t < len1 && len2 > 0 && qx == qx && qy == qy && qz == qz) {
+      // unclamped integer cell of the query (may lie outside the grid)
+      const float lim = 1.0e6f;
+      cx = (int)fminf(fmaxf(floorf((qx - g.mnx) * g.delta), -lim), lim);
+      cy = (int)fminf(fmaxf(floorf((qy - g.mny) * g.delta), -lim), lim);
+      cz = (int)fminf(fmaxf(floorf((qz - g.mnz) * g.delta), -lim), lim);
+      // rings below the distance (in cells) from the query's cell to the grid box are empty
+      const int gapx = cx < 0 ? -cx : (cx >= g.rx ? cx - g.rx + 1 : 0);
+      const int gapy = cy < 0 ? -cy : (cy >= g.ry ? cy - g.ry + 1 : 0);
+      const int gapz = cz < 0 ? -cz : (cz >= g.rz ? cz - g.rz + 1 : 0);
+      const int rho0 = max(gapx, max(gapy, gapz));
+      rho_max = max(g.rx, max(g.ry, g.rz)) + rho0;   // beyond this no cell exists
+      const int rho_stop = min(rho_max, rho0 + kRingCap);
+      open = true;
+      int rho = rho0;
+      if (rho0 == 0 && rho_stop >= 1) {
+        // rings 0 and 1 together: nine z-runs, each one contiguous range of the sorted array
+        const int za = max(cz - 1, 0), zb = min(cz + 1, g.rz - 1);
+        for (int xx = max(cx - 1, 0); xx <= min(cx + 1, g.rx - 1); ++xx)
+          for (int yy = max(cy - 1, 0); yy <= min(cy + 1, g.ry - 1); ++yy) {
+            const int c0 = (xx * g.ry + yy) * g.rz + za, c1 = (xx * g.ry + yy) * g.rz + zb;
+            scan_run(s4, offn[c0], (c1 + 1 < g.total) ? (int64_t)offn[c1 + 1] : len2, qx, qy, qz, bd, bi);
+          }
+        const float gg = g.cell * 0.999f;
+        if (bd < FLT_MAX && bd <= gg * gg) open = false;
+        rho = 2;
+      }
+      for (; rho <= rho_stop && open; ++rho) {
+        for (int xx = max(cx - rho, 0); xx <= min(cx + rho, g.rx - 1); ++xx)
+          for (int yy = max(cy - rho, 0); yy <= min(cy + rho, g.ry - 1); ++yy)
+            scan_column(s4, offn, g, len2, xx, yy, cx, cy, cz, rho, qx, qy, qz, bd, bi);
+        if (rho >= 1) {
+          const float gg = (float)rho * g.cell * 0.999f;
+          if (bd < FLT_MAX && bd <= gg * gg) open = false;
+        }
+      }
+      rho_next = rho;
+      if (rho_next > rho_max) open = false;
+    }
+    // the wave finishes its open queries one after the other (an isolated point, a query far from the cloud): one
+    // slow lane would otherwise hold its wave for thousands of dependent loads
+    unsigned long long todo = __ballot(open);
+    while (todo) {
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1;
+      const float wx = __shfl(qx, src), wy = __shfl(qy, src), wz = __shfl(qz, src);
+      const int wcx = __shfl(cx, src), wcy = __shfl(cy, src), wcz = __shfl(cz, src);
+      const int w_first = __shfl(rho_next, src), w_max = __shfl(rho_max, src);
+      float wd = __shfl(bd, src);
+      int wi = __shfl(bi, src);
+      for (int rho = w_first; rho <= w_max; ++rho) {
+        const int x0 = max(wcx - rho, 0), x1 = min(wcx + rho, g.rx - 1);
+        const int y0 = max(wcy - rho, 0), y1 = min(wcy + rho, g.ry - 1);
+        if (x0 <= x1 && y0 <= y1) {
+          const int ny = y1 - y0 + 1;
+          const int ncols = (x1 - x0 + 1) * ny;
+          for (int col = lane; col < ncols; col += 64)
+            scan_column(s4, offn, g, len2, x0 + col / ny, y0 + col % ny, wcx, wcy, wcz, rho, wx, wy, wz, wd, wi);
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+          const float od = __shfl_xor(wd, o);
+          const int oi = __shfl_xor(wi, o);
+          if (pair_lt(od, oi, wd, wi)) { wd = od; wi = oi; }
+        }
+        const float gg = (float)rho * g.cell * 0.999f;
+        if (rho >= 1 && wd < FLT_MAX && wd <= gg * gg) break;
+      }
+      if (lane == src) { bd = wd; bi = wi; }
+    }
+    if (row) {
+      const bool found = bd < FLT_MAX;
+      const float d2 = found ? bd : 0.f;
+      float nt = 0.f;
+      if (NORMALS && found)
+        nt = normal_term(x_normals + ((int64_t)n * p1 + t) * 3, y_normals + ((int64_t)n * p2 + bi) * 3);
+      if (d2_out) d2_out[(int64_t)n * p1 + t] = d2;
+      idx_out[(int64_t)n * p1 + t] = found ? bi : -1;
+      if (NORMALS && nterm_out) nterm_out[(int64_t)n * p1 + t] = nt;
+      acc_d += d2;
+      acc_n += nt;
+    }
+  }
+  acc_d = iso_wave_sum(acc_d);
+  acc_n = iso_wave_sum(acc_n);
+  if (lane == 0) { s_sum[threadIdx.x >> 6][0] = acc_d; s_sum[threadIdx.x >> 6][1] = acc_n; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    float s = s_sum[0][threadIdx.x];
+#pragma unroll
+    for (int w = 1; w < kNearBlock / 64; ++w) s += s_sum[w][threadIdx.x];
+    partials[((int64_t)n * gridDim.x + blockIdx.x) * 2 + threadIdx.x] = s;
+  }
+}
+
+// sums_out[n] = {sum d2, sum normal term}: the partials of cloud n in 64 contiguous chunks, each added in index order by
+// one lane, then the 64 chunk sums added in order
+__global__ __launch_bounds__(128) void k_cham_finish(const float* __restrict__ partials, int n_part,
+                                                     float* __restrict__ sums_out) {
+  __shared__ float s_p[kMaxPartials * 2];
+  __shared__ float s_c[2][64];
+  const int n = blockIdx.x;
+  for (int i = threadIdx.x; i < n_part * 2; i += 128) s_p[i] = partials[(int64_t)n * n_part * 2 + i];
+  __syncthreads();
+  const int q = threadIdx.x >> 6, l = threadIdx.x & 63;
+  const int chunk = (n_part + 63) / 64;
+  float s = 0.f;
+  for (int k = 0; k < chunk; ++k) {
+    const int i = l * chunk + k;
+    if (i < n_part) s += s_p[i * 2 + q];
+  }
+  s_c[q][l] = s;
+  __syncthreads();
+  if (l == 0) {
+    float t = 0.f;
+    for (int k = 0; k < 64; ++k) t += s_c[q][k];
+    sums_out[n * 2 + q] = t;
+  }
+}
+
+// ---- backward ---------------------------------------------------------------------------------------------------
+// One side of the backward pass: cloud A (p1 rows, the gradient's owner) and cloud B (p2 rows).  idx_b[j] = the row of A
+// that row j of B chose.  Both sides (x as A, y as A) run in the same launches, blockIdx.z picks the side.  Count and
+// offset rows have the common stride pm = max(P1, P2), so that one batched prefix sum serves both sides.
+struct Side {
+  const float* a;        // (N,p1,3)
+  const float* b;        // (N,p2,3)
+  const float* an;       // normals of A or null
+  const float* bn;
+  const int64_t* a_len;
+  const int32_t* idx_a;  // (N,p1): row of B chosen by row i of A
+  const int32_t* idx_b;  // (N,p2)
+  const float* g_own;    // (N) scale of A's own terms
+  const float* g_other;  // (N) scale of the terms of B's rows
+  const float* gn_own;
+  const float* gn_other;
+  float* grad_a;
+  float* grad_an;        // null: the normals' gradient is not wanted
+  int64_t p1, p2, pm;
+  int32_t* cnt;          // (N,pm)
+  int32_t* off;          // (N,pm)
+  int32_t* slot;         // (N,p2)
+  int32_t* list;         // (N,p2)
+  int32_t* heavy;        // (N*p1)
+  int32_t* heavy_count;
+};
+struct Sides { Side d[2]; };
+
+__global__ void k_cham_count(Sides both) {
+  const Side s = blockIdx.z ? both.d[1] : both.d[0];
+  const int n = blockIdx.y;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < s.p2; j += (int64_t)gridDim.x * blockDim.x) {
+    const int i = s.idx_b[(int64_t)n * s.p2 + j];
+    if (i >= 0) s.slot[(int64_t)n * s.p2 + j] = atomicAdd(&s.cnt[(int64_t)n * s.pm + i], 1);
+  }
+}
+
+__global__ void k_cham_fill(Sides both) {
+  const Side s = blockIdx.z ? both.d[1] : both.d[0];
+  const int n = blockIdx.y;
+  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < s.p2; j += (int64_t)gridDim.x * blockDim.x) {
+    const int i = s.idx_b[(int64_t)n * s.p2 + j];
+    if (i >= 0) s.list[(int64_t)n * s.p2 + s.off[(int64_t)n * s.pm + i] + s.slot[(int64_t)n * s.p2 + j]] = (int32_t)j;
+  }
+}
+
+// d(1 - |cos(a, b)|) / da
+__device__ __forceinline__ void normal_term_grad(const float (&a)[3], const float* __restrict__ b, float (&out)[3]) {
+  const float bx = b[0], by = b[1], bz = b[2];
+  const float la = sqrtf((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]), lb = sqrtf((bx * bx + by * by) + bz * bz);
+  const float ca = fmaxf(la, kNormEps), cb = fmaxf(lb, kNormEps);
+  const float c = ((a[0] * bx + a[1] * by) + a[2] * bz) / (ca * cb);
+  const float sgn = c > 0.f ? -1.f : (c < 0.f ? 1.f : 0.f);       // -sign(cos)
+  const float k1 = sgn / (ca * cb);
+  const float k2 = (la >= kNormEps) ? sgn * c / (la * ca) : 0.f;  // the clamped norm is a constant
+  out[0] = k1 * bx - k2 * a[0];
+  out[1] = k1 * by - k2 * a[1];
+  out[2] = k1 * bz - k2 * a[2];
+}
+
+// what row j of B adds to row i of A: (a_i - b_j) to pos, d(1 - |cos(an_i, bn_j)|)/d an_i to nrm
+template <bool NORMALS>
+__device__ __forceinline__ void add_pair(const Side& s, int n, const float (&ai)[3], const float (&ani)[3], int64_t j,
+                                         float (&pos)[3], float (&nrm)[3]) {
+  const float* bj = s.b + ((int64_t)n * s.p2 + j) * 3;
+  pos[0] += ai[0] - bj[0]; pos[1] += ai[1] - bj[1]; pos[2] += ai[2] - bj[2];
+  if (NORMALS) {
+    float gn[3];
+    normal_term_grad(ani, s.bn + ((int64_t)n * s.p2 + j) * 3, gn);
+    nrm[0] += gn[0]; nrm[1] += gn[1]; nrm[2] += gn[2];
+  }
+}
+
+// grad_a[i] = 2 g_own (a_i - b[idx_a[i]]) + 2 g_other sum_{j: idx_b[j] = i} (a_i - b_j), and the same two parts for the
+// normals.  One lane per row of A; a list longer than kLightList is left to k_cham_grad_heavy (this kernel writes the row's
+// own part, that one adds the list's).
+template <bool NORMALS>
+__global__ __launch_bounds__(256) void k_cham_grad(Sides both) {
+  const Side s = blockIdx.z ? both.d[1] : both.d[0];
+  const int n = blockIdx.y;
+  const int64_t len = s.a_len ? s.a_len[n] : s.p1;
+  const float go = 2.0f * s.g_own[n], gt = 2.0f * s.g_other[n];
+  const float no = NORMALS ? s.gn_own[n] : 0.f, nt = NORMALS ? s.gn_other[n] : 0.f;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < s.p1; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t r = (int64_t)n * s.p1 + i;
+    const int64_t c_row = (int64_t)n * s.pm + i;
+    float gp[3] = {0.f, 0.f, 0.f}, gq[3] = {0.f, 0.f, 0.f};
+    if (i < len) {
+      float ai[3], ani[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+      for (int c = 0; c < 3; ++c) ai[c] = s.a[r * 3 + c];
+      if (NORMALS) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) ani[c] = s.an[r * 3 + c];
+      }
+      const int own = s.idx_a[r];
+      if (own >= 0) {
+        float pos[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f};
+        add_pair<NORMALS>(s, n, ai, ani, own, pos, nrm);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { gp[c] = go * pos[c]; gq[c] = no * nrm[c]; }
+      }
+      const int L = s.cnt[c_row];
+      if (L > kLightList) {
+        s.heavy[atomicAdd(s.heavy_count, 1)] = (int32_t)r;  // the order of this list decides nothing: one wave per entry
+      } else if (L > 0) {
+        // ascending query order: take the smallest index above the last one taken, L times
+        const int32_t* li = s.list + (int64_t)n * s.p2 + s.off[c_row];
+        float pos[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f};
+        int last = -1;
+        for (int k = 0; k < L; ++k) {
+          int nxt = 0x7fffffff;
+          for (int m = 0; m < L; ++m) { const int v = li[m]; if (v > last && v < nxt) nxt = v; }
+          add_pair<NORMALS>(s, n, ai, ani, nxt, pos, nrm);
+          last = nxt;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { gp[c] += gt * pos[c]; gq[c] += nt * nrm[c]; }
+      }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) s.grad_a[r * 3 + c] = gp[c];
+    if (NORMALS && s.grad_an) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s.grad_an[r * 3 + c] = gq[c];
+    }
+  }
+}
+
+// One wave per long list.  Up to kSortList entries: the list is rank-sorted into LDS and lane l sums entries l, l + 64, ...
+// of the sorted list; beyond that: lane l visits rows l, l + 64, ... of B and takes those that chose this target.  Either
+// way every lane's sum runs in ascending query order and the 64 sums are added by the same butterfly: a fixed order.
+template <bool NORMALS>
+__global__ __launch_bounds__(64) void k_cham_grad_heavy(Sides both) {
+  __shared__ int32_t s_raw[kSortList], s_sorted[kSortList];
+  const Side s = blockIdx.z ? both.d[1] : both.d[0];
+  const int lane = threadIdx.x;
+  const int count = *s.heavy_count;
+  for (int w = blockIdx.x; w < count; w += gridDim.x) {
+    const int64_t r = s.heavy[w];
+    const int n = (int)(r / s.p1);
+    const int i = (int)(r - (int64_t)n * s.p1);
+    const int64_t c_row = (int64_t)n * s.pm + i;
+    const int L = s.cnt[c_row];
+    float ai[3], ani[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ai[c] = s.a[r * 3 + c];
+    if (NORMALS) {
+#pragma unroll
+      for (int c = 0; c < 3; ++c) ani[c] = s.an[r * 3 + c];
+    }
+    float pos[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f};
+    if (L <= kSortList) {
+      const int32_t* li = s.list + (int64_t)n * s.p2 + s.off[c_row];
+      __syncthreads();                                   // the previous entry's readers of the LDS lists are done
+      for (int m = lane; m < L; m += 64) s_raw[m] = li[m];
+      __syncthreads();
+      for (int m = lane; m < L; m += 64) {
+        const int v = s_raw[m];
+        int rank = 0;
+        for (int q = 0; q < L; ++q) rank += (s_raw[q] < v) ? 1 : 0;   // query indices are distinct
+        s_sorted[rank] = v;
+      }
+      __syncthreads();
+      for (int m = lane; m < L; m += 64) add_pair<NORMALS>(s, n, ai, ani, s_sorted[m], pos, nrm);
+    } else {
+      const int32_t* ib = s.idx_b + (int64_t)n * s.p2;
+      for (int64_t j = lane; j < s.p2; j += 64)
+        if (ib[j] == i) add_pair<NORMALS>(s, n, ai, ani, j, pos, nrm);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { pos[c] = iso_wave_sum(pos[c]); nrm[c] = iso_wave_sum(nrm[c]); }
+    if (lane == 0) {
+      const float gt = 2.0f * s.g_other[n];
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s.grad_a[r * 3 + c] += gt * pos[c];
+      if (NORMALS && s.grad_an) {
+        const float nt = s.gn_other[n];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s.grad_an[r * 3 + c] += nt * nrm[c];
+      }
+    }
+  }
+}
+
+int near_grid(int64_t p1) {
+  int gx = iso_div_up(p1, kNearBlock);
+  if (gx > kMaxPartials) gx = kMaxPartials;
+  return gx < 1 ? 1 : gx;
+}
+
+int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
+
+}  // namespace
+
+// workspace of iso_chamfer_nearest: [candidate records: N*P2 float4][partials: N * grid * 2 floats]
+extern "C" int64_t iso_chamfer_nearest_workspace_bytes(int n_clouds, int64_t p1, int64_t p2) {
+  if (n_clouds < 0) n_clouds = 0;
+  if (p1 < 0) p1 = 0;
+  if (p2 < 0) p2 = 0;
+  return 16 * (int64_t)n_clouds * p2 + align16((int64_t)n_clouds * near_grid(p1) * 2 * 4) + 16;
+}
+
+extern "C" int iso_chamfer_nearest(const float* x, const int64_t* x_lengths, const float* sorted_y,
+                                   const int32_t* sorted_idx_y, const int64_t* y_lengths, const int32_t* off,
+                                   const float* grid_params, const float* x_normals, const float* y_normals,
+                                   float* d2_out, int32_t* idx_out, float* nterm_out, float* sums_out, int n_clouds,
+                                   int64_t p1, int64_t p2, int64_t g_stride, void* workspace, int64_t workspace_bytes,
+                                   void* stream) {
+  ISO_REQUIRE(n_clouds >= 0 && p1 >= 0 && p2 >= 0 && g_stride >= 0, ISO_ERR_INVALID, "iso_chamfer_nearest: bad sizes");
+  ISO_REQUIRE(p1 < 0x7fffffff && p2 < 0x7fffffff, ISO_ERR_UNSUPPORTED, "iso_chamfer_nearest: 32-bit point indices");
+  if (n_clouds == 0) return ISO_OK;
+  ISO_REQUIRE(sums_out, ISO_ERR_INVALID, "iso_chamfer_nearest: null pointer");
+  ISO_REQUIRE((x && idx_out) || p1 == 0, ISO_ERR_INVALID, "iso_chamfer_nearest: null pointer");
+  ISO_REQUIRE((sorted_y && sorted_idx_y) || p2 == 0, ISO_ERR_INVALID, "iso_chamfer_nearest: null pointer");
+  ISO_REQUIRE(off && grid_params, ISO_ERR_INVALID, "iso_chamfer_nearest: null pointer");
+  ISO_REQUIRE((x_normals == nullptr) == (y_normals == nullptr), ISO_ERR_INVALID,
+              "iso_chamfer_nearest: normals for both clouds or for neither");
+  ISO_REQUIRE(workspace && workspace_bytes >= iso_chamfer_nearest_workspace_bytes(n_clouds, p1, p2), ISO_ERR_WORKSPACE,
+              "iso_chamfer_nearest: workspace too small");
+  ISO_REQUIRE(((uintptr_t)workspace & 15) == 0, ISO_ERR_INVALID, "iso_chamfer_nearest: workspace must be 16-B aligned");
+  hipStream_t s = (hipStream_t)stream;
+  float4* xyzi = reinterpret_cast<float4*>(workspace);
+  float* partials = reinterpret_cast<float*>((char*)workspace + 16 * (int64_t)n_clouds * p2);
+  const int gx = near_grid(p1);
+  if (p2 > 0) {
+    int gp = iso_div_up(p2, 256);
+    if (gp > 4096) gp = 4096;
+    hipLaunchKernelGGL(k_cham_pack, dim3(gp, n_clouds), dim3(256), 0, s, sorted_y, sorted_idx_y, y_lengths, p2, xyzi);
+  }
+  if (x_normals)
+    hipLaunchKernelGGL(k_cham_nearest<true>, dim3(gx, n_clouds), dim3(kNearBlock), 0, s, x, x_lengths, xyzi, y_lengths, off,
+                       grid_params, x_normals, y_normals, d2_out, idx_out, nterm_out, partials, p1, p2, g_stride);
+  else
+    hipLaunchKernelGGL(k_cham_nearest<false>, dim3(gx, n_clouds), dim3(kNearBlock), 0, s, x, x_lengths, xyzi, y_lengths, off,
+                       grid_params, x_normals, y_normals, d2_out, idx_out, nterm_out, partials, p1, p2, g_stride);
+  hipLaunchKernelGGL(k_cham_finish, dim3(n_clouds), dim3(128), 0, s, partials, gx, sums_out);
+  ISO_CHECK_LAUNCH("iso_chamfer_nearest");
+  return ISO_OK;
+}
+
+// workspace of iso_chamfer_backward: cnt, off (N*P1 ints each), slot, list (N*P2 each), heavy (N*P1), heavy_count (4 ints),
+// then the prefix sum's own
+// workspace of iso_chamfer_backward, R = N * max(P1, P2) ints per array and side: cnt (2R) + heavy counters (4), off (2R),
+// heavy (2R), slot (2R), list (2R), then the prefix sum's own
+static int64_t backward_ints(int n_clouds, int64_t pm) { return 10 * (int64_t)n_clouds * pm + 4; }
+
+extern "C" int64_t iso_chamfer_backward_workspace_bytes(int n_clouds, int64_t p1, int64_t p2) {
+  if (n_clouds < 0) n_clouds = 0;
+  const int64_t pm = p1 > p2 ? (p1 > 0 ? p1 : 0) : (p2 > 0 ? p2 : 0);
+  return align16(4 * backward_ints(n_clouds, pm)) + iso_prefix_sum_workspace_bytes(pm, 2 * n_clouds) + 16;
+}
+
+extern "C" int iso_chamfer_backward(const float* x, const float* y, const int64_t* x_lengths, const int64_t* y_lengths,
+                                    const int32_t* idx_x, const int32_t* idx_y, const float* g_dx, const float* g_dy,
+                                    const float* x_normals, const float* y_normals, const float* g_nx, const float* g_ny,
+                                    float* grad_x, float* grad_y, float* grad_x_normals, float* grad_y_normals,
+                                    int n_clouds, int64_t p1, int64_t p2, void* workspace, int64_t workspace_bytes,
+                                    void* stream) {
+  ISO_REQUIRE(n_clouds >= 0 && p1 >= 0 && p2 >= 0, ISO_ERR_INVALID, "iso_chamfer_backward: bad sizes");
+  const int64_t pm = p1 > p2 ? p1 : p2;
+  ISO_REQUIRE((int64_t)n_clouds * pm < 0x7fffffff, ISO_ERR_UNSUPPORTED, "iso_chamfer_backward: 32-bit row indices");
+  if (n_clouds == 0 || pm == 0 || (!grad_x && !grad_y)) return ISO_OK;
+  ISO_REQUIRE(g_dx && g_dy && (p1 == 0 || (x && idx_x)) && (p2 == 0 || (y && idx_y)), ISO_ERR_INVALID,
+              "iso_chamfer_backward: null pointer");
+  ISO_REQUIRE((x_normals == nullptr) == (y_normals == nullptr), ISO_ERR_INVALID,
+              "iso_chamfer_backward: normals for both clouds or for neither");
+  ISO_REQUIRE((!grad_x_normals || grad_x) && (!grad_y_normals || grad_y), ISO_ERR_INVALID,
+              "iso_chamfer_backward: a normal gradient needs its cloud's position gradient buffer");
+  const bool normals = grad_x_normals || grad_y_normals;
+  ISO_REQUIRE(!normals || (x_normals && g_nx && g_ny), ISO_ERR_INVALID, "iso_chamfer_backward: null pointer");
+  ISO_REQUIRE(workspace && workspace_bytes >= iso_chamfer_backward_workspace_bytes(n_clouds, p1, p2), ISO_ERR_WORKSPACE,
+              "iso_chamfer_backward: workspace too small");
+  ISO_REQUIRE(((uintptr_t)workspace & 15) == 0, ISO_ERR_INVALID, "iso_chamfer_backward: workspace must be 16-B aligned");
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t R = (int64_t)n_clouds * pm;
+  int32_t* cnt = (int32_t*)workspace;       // [2][N][pm]
+  int32_t* heavy_count = cnt + 2 * R;       // zeroed together with cnt
+  int32_t* offp = heavy_count + 4;
+  int32_t* heavy = offp + 2 * R;
+  int32_t* slot = heavy + 2 * R;
+  int32_t* list = slot + 2 * R;
+  void* scan_ws = (char*)workspace + align16(4 * backward_ints(n_clouds, pm));
+  Sides both;
+  int ns = 0;
+  if (grad_x && p1 > 0) {
+    both.d[ns] = Side{x, y, x_normals, y_normals, x_lengths, idx_x, idx_y, g_dx, g_dy, g_nx, g_ny, grad_x, grad_x_normals,
+                      p1, p2, pm, cnt + ns * R, offp + ns * R, slot + ns * R, list + ns * R, heavy + ns * R, heavy_count + ns};
+    ++ns;
+  }
+  if (grad_y && p2 > 0) {
+    both.d[ns] = Side{y, x, y_normals, x_normals, y_lengths, idx_y, idx_x, g_dy, g_dx, g_ny, g_nx, grad_y, grad_y_normals,
+                      p2, p1, pm, cnt + ns * R, offp + ns * R, slot + ns * R, list + ns * R, heavy + ns * R, heavy_count + ns};
+    ++ns;
+  }
+  if (ns == 0) return ISO_OK;
+  if (ns == 1) both.d[1] = both.d[0];
+  iso_zero_words(cnt, 2 * R + 4, s);
+  int gm = iso_div_up(pm, 256);
+  if (gm > 4096) gm = 4096;
+  hipLaunchKernelGGL(k_cham_count, dim3(gm, n_clouds, ns), dim3(256), 0, s, both);
+  int rc = iso_prefix_sum(cnt, offp, pm, ns * n_clouds, pm, scan_ws, iso_prefix_sum_workspace_bytes(pm, 2 * n_clouds), stream);
+  if (rc != ISO_OK) return rc;
+  hipLaunchKernelGGL(k_cham_fill, dim3(gm, n_clouds, ns), dim3(256), 0, s, both);
+  const int gh = (int)(R < 2048 ? R : 2048);
+  if (normals) {
+    hipLaunchKernelGGL(k_cham_grad<true>, dim3(gm, n_clouds, ns), dim3(256), 0, s, both);
+    hipLaunchKernelGGL(k_cham_grad_heavy<true>, dim3(gh, 1, ns), dim3(64), 0, s, both);
+  } else {
+    hipLaunchKernelGGL(k_cham_grad<false>, dim3(gm, n_clouds, ns), dim3(256), 0, s, both);
+    hipLaunchKernelGGL(k_cham_grad_heavy<false>, dim3(gh, 1, ns), dim3(64), 0, s, both);
+  }
+  ISO_CHECK_LAUNCH("iso_chamfer_backward");
+  return ISO_OK;
+}
