@@ -99,15 +99,6 @@ struct BrickParams {
 };
 
 #ifdef __HIPCC__
-__device__ __forceinline__ unsigned bk_f2key(float f) {
-  const unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float bk_key2f(unsigned k) {
-  const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
-
 // Per-thread bounding box, joined over the workgroup and added to the pending box (all threads of the workgroup call
 // commit(); s_box: one row of 6 floats per wave).
 struct BkBox {
@@ -149,7 +140,7 @@ struct BkBox {
       for (int k = 1; k < (int)(blockDim.x >> 6); ++k) v = a < 3 ? fminf(v, s_box[k][a]) : fmaxf(v, s_box[k][a]);
       unsigned* acc = reinterpret_cast<unsigned*>(counters) + kBoxAt + kBoxStride * (blockIdx.x % kBoxCopies);
       const bool any = a < 3 ? v < FLT_MAX : v > -FLT_MAX;      // (a workgroup without a point: nothing)
-      const unsigned key = a < 3 ? ~bk_f2key(v) : bk_f2key(v);
+      const unsigned key = a < 3 ? ~iso_f2key(v) : iso_f2key(v);
       if (any && key > seen) atomicMax(&acc[a], key);
     }
   }
@@ -183,8 +174,8 @@ __device__ __forceinline__ void bk_box_read(const int32_t* __restrict__ counters
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const unsigned l = s_red[a], u = s_red[3 + a];
-    mn[a] = l ? bk_key2f(~l) : 0.f;
-    mx[a] = u ? bk_key2f(u) : 0.f;
+    mn[a] = l ? iso_key2f(~l) : 0.f;
+    mx[a] = u ? iso_key2f(u) : 0.f;
   }
 }
 // lanes 0..kBoxCopies-1 of ONE workgroup, in a launch after every reader of the pending box

@@ -52,16 +52,6 @@ BrickWs bricks_carve(void* ws, int64_t n_max) {
 
 namespace {
 
-__device__ __forceinline__ int wave_incl_scan_i(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 // ---- header ------------------------------------------------------------------------------------
 // bbox: [min xyz, 0, max xyz, 0] (iso_points_bbox layout; for N ranks the caller reduces it first)
 __global__ void k_bricks_params(const float* __restrict__ bbox, int n_boxes, BrickParams q, BrickHdr* __restrict__ h,
@@ -320,19 +310,6 @@ __global__ __launch_bounds__(256) void k_brick_scatter_recs(const float4* __rest
 constexpr int BS_ITEMS = 4, BS_CHUNK = 256 * BS_ITEMS;
 static_assert(BK_CPB == 8, "a brick's counters are two 16-byte words");
 
-__device__ __forceinline__ int block_excl_scan_256(int v, int& total, int* lds /*>= 4*/) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int inc = wave_incl_scan_i(v);
-  if (lane == 63) lds[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { const int t = lds[i]; if (i < w) base += t; tot += t; }
-  total = tot;
-  __syncthreads();
-  return base + inc - v;
-}
-
 // a thread's BS_ITEMS bricks of chunk `chunk`: their counters (zeroed behind the read when ZERO) and the brick totals
 template <bool ZERO>
 __device__ __forceinline__ int brick_counters_load(int32_t* __restrict__ cnt, int chunk, int nb, int (&c)[BS_ITEMS][BK_CPB],
@@ -396,7 +373,7 @@ __global__ __launch_bounds__(256) void k_brick_sums(const BrickHdr* __restrict__
   int c[BS_ITEMS][BK_CPB], t[BS_ITEMS];
   const int v = brick_counters_load<false>(cnt, blockIdx.x, nb, c, t);
   int tot;
-  block_excl_scan_256(v, tot, lds);
+  iso_block_excl_scan<4>(v, tot, lds);
   if (threadIdx.x == 0) sums[blockIdx.x] = tot;
 }
 
@@ -410,7 +387,7 @@ __global__ __launch_bounds__(256) void k_brick_offsets(const BrickHdr* __restric
   int before = 0;
   for (int i = threadIdx.x; i < (int)blockIdx.x; i += 256) before += sums[i];
   int base;
-  block_excl_scan_256(before, base, lds);                       // base = total of the chunks before this one
+  iso_block_excl_scan<4>(before, base, lds);                       // base = total of the chunks before this one
   int c[BS_ITEMS][BK_CPB], t[BS_ITEMS];
   const int v = brick_counters_load<true>(cnt, blockIdx.x, nb, c, t);
   int occ = 0;
@@ -419,8 +396,8 @@ __global__ __launch_bounds__(256) void k_brick_offsets(const BrickHdr* __restric
 #pragma unroll
   for (int k = 0; k < BS_ITEMS; ++k) occ += listed[k] ? 1 : 0;
   int tot, occ_tot;
-  const int ex = base + block_excl_scan_256(v, tot, lds);
-  int at = block_excl_scan_256(occ, occ_tot, lds);
+  const int ex = base + iso_block_excl_scan<4>(v, tot, lds);
+  int at = iso_block_excl_scan<4>(occ, occ_tot, lds);
   if (threadIdx.x == 0) s_base = occ_tot ? atomicAdd(&counters[0], occ_tot) : 0;
   __syncthreads();
   brick_offsets_store(off, list, blockIdx.x, nb, c, t, ex, at + s_base, listed);
@@ -450,7 +427,7 @@ __global__ __launch_bounds__(256) void k_brick_offsets1(const BrickHdr* __restri
 #pragma unroll
   for (int k = 0; k < BS_ITEMS; ++k) occ += listed[k] ? 1 : 0;
   int tot, occ_tot;
-  int ex = block_excl_scan_256(v, tot, lds);
+  int ex = iso_block_excl_scan<4>(v, tot, lds);
   if (threadIdx.x == 0) __hip_atomic_store(&sums[blockIdx.x], 0x80000000u | (unsigned)tot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   int before = 0;
   for (int i = threadIdx.x; i < (int)blockIdx.x; i += 256) {
@@ -459,9 +436,9 @@ __global__ __launch_bounds__(256) void k_brick_offsets1(const BrickHdr* __restri
     before += (int)(q & 0x7fffffffu);
   }
   int base;
-  block_excl_scan_256(before, base, lds);                       // base = total of the chunks before this one
+  iso_block_excl_scan<4>(before, base, lds);                       // base = total of the chunks before this one
   ex += base;
-  int at = block_excl_scan_256(occ, occ_tot, lds);
+  int at = iso_block_excl_scan<4>(occ, occ_tot, lds);
   if (threadIdx.x == 0) s_base = occ_tot ? atomicAdd(&counters[0], occ_tot) : 0;
   __syncthreads();
   brick_offsets_store(off, list, blockIdx.x, nb, c, t, ex, at + s_base, listed);
@@ -597,7 +574,7 @@ __device__ int stage_brick(BrickStage<WITH_NRM, SUB, CAP>& S, const BrickHdr& h,
   __syncthreads();
   if (tid < 64) {                                    // exclusive prefix of the run lengths (one wave)
     const int len = tid < kStageRuns ? S.run_pre[tid + 1] : 0;
-    const int inc = wave_incl_scan_i(len);
+    const int inc = iso_wave_incl_scan(len);
     if (tid < kStageRuns) S.run_pre[tid + 1] = inc;
     if (tid == 0) S.run_pre[0] = 0;
   }
@@ -636,7 +613,7 @@ __device__ int stage_brick(BrickStage<WITH_NRM, SUB, CAP>& S, const BrickHdr& h,
       constexpr int PER = (NCELL + 63) / 64;
       int sum = 0;
       for (int k = 0; k < PER; ++k) { const int c = tid * PER + k; sum += c < NCELL ? S.ccur[c] : 0; }
-      int ex = wave_incl_scan_i(sum) - sum;
+      int ex = iso_wave_incl_scan(sum) - sum;
       for (int k = 0; k < PER; ++k) {
         const int c = tid * PER + k;
         if (c < NCELL) { const int v = S.ccur[c]; S.cstart[c] = ex; S.ccur[c] = ex; ex += v; }
@@ -711,7 +688,7 @@ __device__ int stage_brick(BrickStage<WITH_NRM, SUB, CAP>& S, const BrickHdr& h,
     qlen = S.cstart[c + QA] - S.cstart[c];
   }
   if (tid < 64) {                                    // exclusive prefix of the run lengths (NQ <= 64: one wave)
-    const int inc = wave_incl_scan_i(qlen);
+    const int inc = iso_wave_incl_scan(qlen);
     if (tid < NQ) S.qpre[tid + 1] = inc;
     if (tid == 0) S.qpre[0] = 0;
   }

@@ -2,12 +2,11 @@
 // Stands in for pytorch3d.loss.chamfer_distance as the reference calls it (include/isopoints.h
 // section G for the call sites).
 //
-//   k_cham_pack     : (x, y, z, original index) record per sorted target point, one 16-B load per candidate
-//   k_cham_nearest  : one lane per query walks the 3x3x3 cell block and at most two more Chebyshev rings
-//                     around its cell (the exact K = 1 search of k_query, same d2 expression, same
-//                     (d2, index) order); a query still open after that is finished by its whole WAVE in
-//                     the same launch, the lanes splitting each further shell's cell columns.  The lane
-//                     then forms the normal term and the workgroup reduces both sums in a fixed order.
+//   k_cham_nearest  : one lane per query walks the cell grid as cell_grid.h states it (the walk, the d2
+//                     expression and the (d2, index) order k_query uses, with K = 1 and no radius); a query
+//                     still open after kRingCap further shells is finished by its whole WAVE in the same
+//                     launch.  The lane then forms the normal term and the workgroup reduces both sums in
+//                     a fixed order.
 //   k_cham_finish   : adds the workgroups' partial sums of a cloud in a fixed order (64 chunks in index order)
 //   backward        : k_cham_count / iso_prefix_sum / k_cham_fill sort the other cloud's nearest indices by
 //                     target (integer atomics only); k_cham_grad sums each target's list in ascending query
@@ -15,78 +14,17 @@
 //                     run in the same launches (blockIdx.z = the side).  No float atomics: two runs give the
 //                     same bits.
 #include <float.h>
-#include "iso_common.h"
+#include "cell_grid.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int kRingCap = 2;          // rings a lane walks alone beyond its first (k_query's value)
 constexpr int kNearBlock = 256;
 constexpr int kMaxPartials = 4096;   // workgroups per cloud of k_cham_nearest = partial sums k_cham_finish adds
 constexpr int kLightList = 8;        // targets chosen by at most this many queries are summed by their own lane
 constexpr int kSortList = 1024;      // longer lists are not sorted: the wave scans the whole index row instead
 constexpr float kNormEps = 1e-6f;    // torch.nn.functional.cosine_similarity's eps
-
-__device__ __forceinline__ bool pair_lt(float d1, int i1, float d2, int i2) {
-  return d1 < d2 || (d1 == d2 && i1 < i2);
-}
-
-__global__ void k_cham_pack(const float* __restrict__ sorted, const int32_t* __restrict__ sorted_idx,
-                            const int64_t* __restrict__ lengths, int64_t p_stride, float4* __restrict__ out) {
-  const int n = blockIdx.y;
-  const int64_t len = lengths ? lengths[n] : p_stride;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (int64_t)gridDim.x * blockDim.x) {
-    const float* q = sorted + ((int64_t)n * p_stride + i) * 3;
-    out[(int64_t)n * p_stride + i] = make_float4(q[0], q[1], q[2], __int_as_float(sorted_idx[(int64_t)n * p_stride + i]));
-  }
-}
-
-struct Grid3 {
-  float mnx, mny, mnz, delta, cell;
-  int rx, ry, rz, total;
-};
-
-__device__ __forceinline__ void scan_run(const float4* __restrict__ s4, int64_t i0, int64_t i1, float qx, float qy,
-                                         float qz, float& bd, int& bi) {
-  // two candidates per trip: two independent 16-B loads in flight per lane
-  for (int64_t i = i0; i < i1; i += 2) {
-    const bool two = i + 1 < i1;
-    const float4 ca = s4[i];
-    const float4 cb = s4[two ? i + 1 : i];
-    {
-      const float dx = qx - ca.x, dy = qy - ca.y, dz = qz - ca.z;
-      const float d2 = (dx * dx + dy * dy) + dz * dz;
-      const int oi = __float_as_int(ca.w);
-      if (pair_lt(d2, oi, bd, bi)) { bd = d2; bi = oi; }
-    }
-    if (two) {
-      const float dx = qx - cb.x, dy = qy - cb.y, dz = qz - cb.z;
-      const float d2 = (dx * dx + dy * dy) + dz * dz;
-      const int oi = __float_as_int(cb.w);
-      if (pair_lt(d2, oi, bd, bi)) { bd = d2; bi = oi; }
-    }
-  }
-}
-
-// the cells of column (x, y) that belong to shell rho around (cx, cy, cz): an edge column is one z-run, an
-// interior column its two cap cells
-__device__ __forceinline__ void scan_column(const float4* __restrict__ s4, const int32_t* __restrict__ offn,
-                                            const Grid3& g, int64_t len2, int x, int y, int cx, int cy, int cz, int rho,
-                                            float qx, float qy, float qz, float& bd, int& bi) {
-  const bool edge = (x == cx - rho) || (x == cx + rho) || (y == cy - rho) || (y == cy + rho);
-  const int nseg = (edge || rho == 0) ? 1 : 2;
-  for (int sgm = 0; sgm < nseg; ++sgm) {
-    int za, zb;
-    if (edge) { za = cz - rho; zb = cz + rho; }
-    else if (sgm == 0) { za = cz - rho; zb = cz - rho; }
-    else { za = cz + rho; zb = cz + rho; }
-    za = max(za, 0); zb = min(zb, g.rz - 1);
-    if (za > zb) continue;
-    const int c0 = (x * g.ry + y) * g.rz + za, c1 = (x * g.ry + y) * g.rz + zb;
-    scan_run(s4, offn[c0], (c1 + 1 < g.total) ? (int64_t)offn[c1 + 1] : len2, qx, qy, qz, bd, bi);
-  }
-}
 
 // 1 - |cos(a, b)|, cos = a.b / (max(|a|, eps) max(|b|, eps))
 __device__ __forceinline__ float normal_term(const float* __restrict__ a, const float* __restrict__ b) {
@@ -109,11 +47,7 @@ __global__ __launch_bounds__(kNearBlock) void k_cham_nearest(
   const float4* s4 = xyzi + (int64_t)n * p2;
   const int64_t len2 = y_len ? y_len[n] : p2;
   const int64_t len1 = x_len ? x_len[n] : p1;
-  const float* gp = params + n * ISO_GRID3_PARAMS;
-  Grid3 g;
-  g.mnx = gp[0]; g.mny = gp[1]; g.mnz = gp[2]; g.delta = gp[3];
-  g.rx = (int)gp[4]; g.ry = (int)gp[5]; g.rz = (int)gp[6]; g.total = (int)gp[7];
-  g.cell = 1.0f / g.delta;
+  const Grid3 g = grid3_load(params, n);
   const int32_t* offn = off + (int64_t)n * g_stride;
   float acc_d = 0.f, acc_n = 0.f;
 
@@ -124,50 +58,38 @@ __global__ __launch_bounds__(kNearBlock) void k_cham_nearest(
     float qx = 0.f, qy = 0.f, qz = 0.f;
     float bd = FLT_MAX;
     int bi = 0x7fffffff;
-    int cx = 0, cy = 0, cz = 0, rho_next = 0, rho_max = -1;
+    QueryCell c = {0, 0, 0, 0, -1};
+    int rho_next = 0;
     bool open = false;
     if (row && t < len1 && len2 > 0) {
       const float* q = x + ((int64_t)n * p1 + t) * 3;
       qx = q[0]; qy = q[1]; qz = q[2];
     }
     if (row && t < len1 && len2 > 0 && qx == qx && qy == qy && qz == qz) {
-      // unclamped integer cell of the query (may lie outside the grid)
-      const float lim = 1.0e6f;
-      cx = (int)fminf(fmaxf(floorf((qx - g.mnx) * g.delta), -lim), lim);
-      cy = (int)fminf(fmaxf(floorf((qy - g.mny) * g.delta), -lim), lim);
-      cz = (int)fminf(fmaxf(floorf((qz - g.mnz) * g.delta), -lim), lim);
-      // rings below the distance (in cells) from the query's cell to the grid box are empty
-      const int gapx = cx < 0 ? -cx : (cx >= g.rx ? cx - g.rx + 1 : 0);
-      const int gapy = cy < 0 ? -cy : (cy >= g.ry ? cy - g.ry + 1 : 0);
-      const int gapz = cz < 0 ? -cz : (cz >= g.rz ? cz - g.rz + 1 : 0);
-      const int rho0 = max(gapx, max(gapy, gapz));
-      rho_max = max(g.rx, max(g.ry, g.rz)) + rho0;   // beyond this no cell exists
-      const int rho_stop = min(rho_max, rho0 + kRingCap);
+      c = query_cell(g, qx, qy, qz);
+      const int rho_stop = min(c.span, c.rho0 + kRingCap);
+      auto scan = [&](int64_t i0, int64_t i1) {
+        scan_run2(s4, i0, i1, qx, qy, qz, [&](float d2, int oi) {
+          if (pair_lt(d2, oi, bd, bi)) { bd = d2; bi = oi; }
+        });
+      };
       open = true;
-      int rho = rho0;
-      if (rho0 == 0 && rho_stop >= 1) {
-        // rings 0 and 1 together: nine z-runs, each one contiguous range of the sorted array
-        const int za = max(cz - 1, 0), zb = min(cz + 1, g.rz - 1);
-        for (int xx = max(cx - 1, 0); xx <= min(cx + 1, g.rx - 1); ++xx)
-          for (int yy = max(cy - 1, 0); yy <= min(cy + 1, g.ry - 1); ++yy) {
-            const int c0 = (xx * g.ry + yy) * g.rz + za, c1 = (xx * g.ry + yy) * g.rz + zb;
-            scan_run(s4, offn[c0], (c1 + 1 < g.total) ? (int64_t)offn[c1 + 1] : len2, qx, qy, qz, bd, bi);
-          }
-        const float gg = g.cell * 0.999f;
-        if (bd < FLT_MAX && bd <= gg * gg) open = false;
+      int rho = c.rho0;
+      if (c.rho0 == 0 && rho_stop >= 1) {
+        visit_block27(g, offn, len2, c, scan);
+        const float reach = ring_reach(1, g.cell);
+        if (bd < FLT_MAX && bd <= reach * reach) open = false;
         rho = 2;
       }
       for (; rho <= rho_stop && open; ++rho) {
-        for (int xx = max(cx - rho, 0); xx <= min(cx + rho, g.rx - 1); ++xx)
-          for (int yy = max(cy - rho, 0); yy <= min(cy + rho, g.ry - 1); ++yy)
-            scan_column(s4, offn, g, len2, xx, yy, cx, cy, cz, rho, qx, qy, qz, bd, bi);
+        visit_shell_lane(g, offn, len2, c, rho, scan);
         if (rho >= 1) {
-          const float gg = (float)rho * g.cell * 0.999f;
-          if (bd < FLT_MAX && bd <= gg * gg) open = false;
+          const float reach = ring_reach(rho, g.cell);
+          if (bd < FLT_MAX && bd <= reach * reach) open = false;
         }
       }
       rho_next = rho;
-      if (rho_next > rho_max) open = false;
+      if (rho_next > c.span) open = false;
     }
     // the wave finishes its open queries one after the other (an isolated point, a query far from the cloud): one
     // slow lane would otherwise hold its wave for thousands of dependent loads
@@ -176,27 +98,21 @@ __global__ __launch_bounds__(kNearBlock) void k_cham_nearest(
       const int src = __ffsll((long long)todo) - 1;
       todo &= todo - 1;
       const float wx = __shfl(qx, src), wy = __shfl(qy, src), wz = __shfl(qz, src);
-      const int wcx = __shfl(cx, src), wcy = __shfl(cy, src), wcz = __shfl(cz, src);
-      const int w_first = __shfl(rho_next, src), w_max = __shfl(rho_max, src);
+      QueryCell wc;
+      wc.cx = __shfl(c.cx, src); wc.cy = __shfl(c.cy, src); wc.cz = __shfl(c.cz, src);
+      wc.rho0 = __shfl(c.rho0, src); wc.span = __shfl(c.span, src);
+      const int w_first = __shfl(rho_next, src);
       float wd = __shfl(bd, src);
       int wi = __shfl(bi, src);
-      for (int rho = w_first; rho <= w_max; ++rho) {
-        const int x0 = max(wcx - rho, 0), x1 = min(wcx + rho, g.rx - 1);
-        const int y0 = max(wcy - rho, 0), y1 = min(wcy + rho, g.ry - 1);
-        if (x0 <= x1 && y0 <= y1) {
-          const int ny = y1 - y0 + 1;
-          const int ncols = (x1 - x0 + 1) * ny;
-          for (int col = lane; col < ncols; col += 64)
-            scan_column(s4, offn, g, len2, x0 + col / ny, y0 + col % ny, wcx, wcy, wcz, rho, wx, wy, wz, wd, wi);
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-          const float od = __shfl_xor(wd, o);
-          const int oi = __shfl_xor(wi, o);
-          if (pair_lt(od, oi, wd, wi)) { wd = od; wi = oi; }
-        }
-        const float gg = (float)rho * g.cell * 0.999f;
-        if (rho >= 1 && wd < FLT_MAX && wd <= gg * gg) break;
+      for (int rho = w_first; rho <= wc.span; ++rho) {
+        visit_shell_wave(g, offn, len2, wc, rho, lane, [&](int64_t i0, int64_t i1) {
+          scan_run2(s4, i0, i1, wx, wy, wz, [&](float d2, int oi) {
+            if (pair_lt(d2, oi, wd, wi)) { wd = d2; wi = oi; }
+          });
+        });
+        wave_argmin(wd, wi);
+        const float reach = ring_reach(rho, g.cell);
+        if (rho >= 1 && wd < FLT_MAX && wd <= reach * reach) break;
       }
       if (lane == src) { bd = wd; bi = wi; }
     }
@@ -475,11 +391,7 @@ extern "C" int iso_chamfer_nearest(const float* x, const int64_t* x_lengths, con
   float4* xyzi = reinterpret_cast<float4*>(workspace);
   float* partials = reinterpret_cast<float*>((char*)workspace + 16 * (int64_t)n_clouds * p2);
   const int gx = near_grid(p1);
-  if (p2 > 0) {
-    int gp = iso_div_up(p2, 256);
-    if (gp > 4096) gp = 4096;
-    hipLaunchKernelGGL(k_cham_pack, dim3(gp, n_clouds), dim3(256), 0, s, sorted_y, sorted_idx_y, y_lengths, p2, xyzi);
-  }
+  pack_xyzi(sorted_y, sorted_idx_y, y_lengths, n_clouds, p2, xyzi, s);
   if (x_normals)
     hipLaunchKernelGGL(k_cham_nearest<true>, dim3(gx, n_clouds), dim3(kNearBlock), 0, s, x, x_lengths, xyzi, y_lengths, off,
                        grid_params, x_normals, y_normals, d2_out, idx_out, nterm_out, partials, p1, p2, g_stride);

@@ -9,30 +9,18 @@
 //   scan_cells  : exclusive prefix sum of the cell counters (wave scan via
 //                 DPP shuffles, block scan via LDS, 3-phase across blocks)
 //   counting_sort: scatter points into cell order
-//   query       : one lane per query point walks Chebyshev rings of cells
-//                 around its own cell, keeps the K best (d2, idx) pairs in
-//                 registers, stops as soon as the ring guarantee covers the
-//                 K-th distance or the radius.  Result = exact K nearest
-//                 within r, so it is independent of the cell size.
-//
-// Distances are d2 = (dx*dx + dy*dy) + dz*dz in f32 with contraction off, the
-// same expression the oracle evaluates, so neighbour lists are bit-exact.
+//   query       : one lane per query point walks the cell grid as cell_grid.h
+//                 states it, keeps the K best (d2, idx) pairs in registers,
+//                 stops as soon as the ring guarantee covers the K-th distance
+//                 or the radius.  Result = exact K nearest within r, so it is
+//                 independent of the cell size, and bit-exact against the
+//                 oracle (same d2 expression, contraction off).
 #include <float.h>
-#include "iso_common.h"
+#include "cell_grid.h"
 
 #pragma clang fp contract(off)
 
 namespace {
-
-// ---- order-preserving float <-> uint key ----------------------------------
-__device__ __forceinline__ unsigned f2key(float f) {
-  unsigned u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key2f(unsigned k) {
-  unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
 
 __global__ void k_bbox_init(unsigned* __restrict__ keys, int n_clouds) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -102,8 +90,8 @@ __global__ __launch_bounds__(BLOCK) void k_bbox(const float* __restrict__ pts,
     float lo = s_mn[0][a], hi = s_mx[0][a];
 #pragma unroll
     for (int k = 1; k < BLOCK / 64; ++k) { lo = fminf(lo, s_mn[k][a]); hi = fmaxf(hi, s_mx[k][a]); }
-    atomicMin(&keys[n * 8 + a], f2key(lo));
-    atomicMax(&keys[n * 8 + 4 + a], f2key(hi));
+    atomicMin(&keys[n * 8 + a], iso_f2key(lo));
+    atomicMax(&keys[n * 8 + 4 + a], iso_f2key(hi));
   }
 }
 
@@ -115,7 +103,7 @@ __global__ void k_bbox_decode(unsigned* __restrict__ keys, const int64_t* __rest
   const int64_t len = lengths ? lengths[n] : p_stride;
   float* f = reinterpret_cast<float*>(keys + n * 8);
   for (int a = 0; a < 3; ++a) {
-    float lo = key2f(keys[n * 8 + a]), hi = key2f(keys[n * 8 + 4 + a]);
+    float lo = iso_key2f(keys[n * 8 + a]), hi = iso_key2f(keys[n * 8 + 4 + a]);
     if (len <= 0) { lo = 0.f; hi = 0.f; }
     f[a] = lo; f[4 + a] = hi;
   }
@@ -133,8 +121,8 @@ __global__ void k_grid_finalize(float* __restrict__ params,
   const int64_t len = lengths ? lengths[n] : p_stride;
   float mn[3], mx[3];
   for (int a = 0; a < 3; ++a) {
-    mn[a] = key2f(keys[a]);
-    mx[a] = key2f(keys[4 + a]);
+    mn[a] = iso_key2f(keys[a]);
+    mx[a] = iso_key2f(keys[4 + a]);
   }
   if (len <= 0) {
     for (int a = 0; a < 3; ++a) { mn[a] = 0.f; mx[a] = 0.f; }
@@ -224,39 +212,9 @@ __global__ void k_counting_sort(const float* __restrict__ pts,
 }
 
 // ---- exclusive scan -------------------------------------------------------
-// inclusive scan across the 64 lanes of a wave
-__device__ __forceinline__ int wave_incl_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    int t = __shfl_up(v, o);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
 constexpr int SCAN_BLOCK = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_CHUNK = SCAN_BLOCK * SCAN_ITEMS;  // 2048 counters per block
-
-// block-wide exclusive scan of one int per thread; returns exclusive prefix,
-// total in `total` (valid in all threads)
-__device__ __forceinline__ int block_excl_scan(int v, int& total, int* lds /*>=5*/) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  int inc = wave_incl_scan(v);
-  if (lane == 63) lds[w] = inc;
-  __syncthreads();
-  int base = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < SCAN_BLOCK / 64; ++i) {
-    int s = lds[i];
-    if (i < w) base += s;
-    tot += s;
-  }
-  total = tot;
-  __syncthreads();
-  return base + inc - v;
-}
 
 __device__ __forceinline__ int64_t row_len(const float* params, int n, int dim,
                                            int64_t n_host, int64_t g_stride) {
@@ -285,7 +243,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_sums(
     }
   }
   int tot;
-  block_excl_scan(v, tot, lds);
+  iso_block_excl_scan<SCAN_BLOCK / 64>(v, tot, lds);
   if (threadIdx.x == 0) sums[n * chunks_per_row + blockIdx.x] = tot;
 }
 
@@ -299,7 +257,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_mid(int32_t* __restrict__ s
     int i = c0 + threadIdx.x;
     int v = (i < chunks_per_row) ? row[i] : 0;
     int tot;
-    int ex = block_excl_scan(v, tot, lds);
+    int ex = iso_block_excl_scan<SCAN_BLOCK / 64>(v, tot, lds);
     if (i < chunks_per_row) row[i] = carry + ex;
     carry += tot;
   }
@@ -326,7 +284,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_final(
     v += vals[k];
   }
   int tot;
-  int ex = block_excl_scan(v, tot, lds) + sums[n * chunks_per_row + blockIdx.x];
+  int ex = iso_block_excl_scan<SCAN_BLOCK / 64>(v, tot, lds) + sums[n * chunks_per_row + blockIdx.x];
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k) {
     int64_t i = c0 + threadIdx.x * SCAN_ITEMS + k;
@@ -336,12 +294,6 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_final(
 }
 
 // ---- query ----------------------------------------------------------------
-constexpr int kRingCap = 2;
-
-__device__ __forceinline__ bool pair_lt(float d1, int i1, float d2, int i2) {
-  return d1 < d2 || (d1 == d2 && i1 < i2);
-}
-
 template <int KMAX>
 struct TopK {
   float d[KMAX];
@@ -391,13 +343,9 @@ __global__ __launch_bounds__(256) void k_query(
   const float4* s4 = xyzi + (int64_t)blockIdx.y * p2_stride;
   const int64_t len2 = lengths2 ? lengths2[n] : p2_stride;
   const int64_t len1 = self ? len2 : (lengths1 ? lengths1[n] : p1_stride);
-  const float* gp = params + n * ISO_GRID3_PARAMS;
-  const float mnx = gp[0], mny = gp[1], mnz = gp[2], delta = gp[3];
-  const int rx = (int)gp[4], ry = (int)gp[5], rz = (int)gp[6];
-  const int total = (int)gp[7];
+  const Grid3 g = grid3_load(params, n);
   const float r = radius[n];
   const float r2 = r * r;
-  const float cell = 1.0f / delta;
   const float* s2 = sorted2 + (int64_t)n * p2_stride * 3;
   const int32_t* sidx = sorted_idx2 + (int64_t)n * p2_stride;
   const int32_t* offn = off + (int64_t)n * g_stride;
@@ -420,105 +368,39 @@ __global__ __launch_bounds__(256) void k_query(
     int wi = 0x7fffffff;
     bool unfinished = false;
     if (len2 > 0 && r > 0.f && qx == qx && qy == qy && qz == qz) {
-      // unclamped integer cell of the query (may lie outside the grid)
-      float fx = floorf((qx - mnx) * delta), fy = floorf((qy - mny) * delta),
-            fz = floorf((qz - mnz) * delta);
-      const float lim = 1.0e6f;
-      int cx = (int)fminf(fmaxf(fx, -lim), lim);
-      int cy = (int)fminf(fmaxf(fy, -lim), lim);
-      int cz = (int)fminf(fmaxf(fz, -lim), lim);
+      const QueryCell c = query_cell(g, qx, qy, qz);
       // rings needed so that rho*cell*(1-1e-3) >= r
-      float rho_f = ceilf(r * delta * 1.0011f);
-      // distance (in cells) from the query's cell to the grid box: rings
-      // below that are empty
-      int gapx = cx < 0 ? -cx : (cx >= rx ? cx - rx + 1 : 0);
-      int gapy = cy < 0 ? -cy : (cy >= ry ? cy - ry + 1 : 0);
-      int gapz = cz < 0 ? -cz : (cz >= rz ? cz - rz + 1 : 0);
-      int rho0 = max(gapx, max(gapy, gapz));
-      int span = max(rx, max(ry, rz)) + rho0;  // beyond this no cell exists
-      int rho_max = (rho_f < (float)span) ? (int)rho_f : span;
+      float rho_f = ceilf(r * g.delta * 1.0011f);
+      int rho_max = (rho_f < (float)c.span) ? (int)rho_f : c.span;
       // A lane walks at most kRingCap rings itself; the rare query that is still open after
       // that (an isolated point, a huge radius) is handed to k_query_tail, where a whole
       // wave sweeps the remaining cell columns -- one slow lane would otherwise hold up its
       // wave for thousands of dependent loads.
-      const int rho_stop = min(rho_max, rho0 + kRingCap);
+      const int rho_stop = min(rho_max, c.rho0 + kRingCap);
       unfinished = rho_stop < rho_max;
       auto scan = [&](int64_t i0, int64_t i1) {
-        // two candidates per trip: two independent 16-B loads in flight per lane
-        for (int64_t i = i0; i < i1; i += 2) {
-          const bool two = i + 1 < i1;
-          const float4 ca = s4[i];
-          const float4 cb = s4[two ? i + 1 : i];
-          {
-            float dx = qx - ca.x, dy = qy - ca.y, dz = qz - ca.z;
-            float d2 = (dx * dx + dy * dy) + dz * dz;
-            if (d2 < r2 && d2 <= wd) {
-              int oi = __float_as_int(ca.w);
-              if (pair_lt(d2, oi, wd, wi)) {
-                best.push(d2, oi, K);
-                wd = best.worst(K);
-                wi = best.worst_id(K);
-              }
-            }
+        scan_run2(s4, i0, i1, qx, qy, qz, [&](float d2, int oi) {
+          if (d2 < r2 && d2 <= wd && pair_lt(d2, oi, wd, wi)) {
+            best.push(d2, oi, K);
+            wd = best.worst(K);
+            wi = best.worst_id(K);
           }
-          if (two) {
-            float dx = qx - cb.x, dy = qy - cb.y, dz = qz - cb.z;
-            float d2 = (dx * dx + dy * dy) + dz * dz;
-            if (d2 < r2 && d2 <= wd) {
-              int oi = __float_as_int(cb.w);
-              if (pair_lt(d2, oi, wd, wi)) {
-                best.push(d2, oi, K);
-                wd = best.worst(K);
-                wi = best.worst_id(K);
-              }
-            }
-          }
-        }
+        });
       };
-      int rho_first = rho0;
+      int rho_first = c.rho0;
       bool done = false;
-      if (rho0 == 0 && rho_stop >= 1) {
-        // rings 0 and 1 together: the 3x3x3 block is nine z-runs, each one contiguous range of the
-        // sorted array (the common case ends here)
-        const int za = max(cz - 1, 0), zb = min(cz + 1, rz - 1);
-        for (int x = max(cx - 1, 0); x <= min(cx + 1, rx - 1); ++x)
-          for (int y = max(cy - 1, 0); y <= min(cy + 1, ry - 1); ++y) {
-            const int c0 = (x * ry + y) * rz + za, c1 = (x * ry + y) * rz + zb;
-            scan(offn[c0], (c1 + 1 < total) ? (int64_t)offn[c1 + 1] : len2);
-          }
-        const float g = cell * 0.999f;
-        if (g >= r || (wd < FLT_MAX && wd <= g * g)) { done = true; unfinished = false; }
+      if (c.rho0 == 0 && rho_stop >= 1) {
+        visit_block27(g, offn, len2, c, scan);   // the common case ends here
+        const float reach = ring_reach(1, g.cell);
+        if (reach >= r || (wd < FLT_MAX && wd <= reach * reach)) { done = true; unfinished = false; }
         rho_first = 2;
       }
       for (int rho = rho_first; rho <= rho_stop && !done; ++rho) {
-        const int x0 = max(cx - rho, 0), x1 = min(cx + rho, rx - 1);
-        const int y0 = max(cy - rho, 0), y1 = min(cy + rho, ry - 1);
-        for (int x = x0; x <= x1; ++x) {
-          const bool ex = (x == cx - rho) || (x == cx + rho);
-          for (int y = y0; y <= y1; ++y) {
-            const bool edge = ex || (y == cy - rho) || (y == cy + rho);
-            const int zlo = cz - rho, zhi = cz + rho;
-            // edge columns take the whole z run, interior ones the two caps
-            const int nseg = edge ? 1 : (rho == 0 ? 1 : 2);
-            for (int sgm = 0; sgm < nseg; ++sgm) {
-              int za, zb;
-              if (edge) { za = zlo; zb = zhi; }
-              else if (sgm == 0) { za = zlo; zb = zlo; }
-              else { za = zhi; zb = zhi; }
-              za = max(za, 0); zb = min(zb, rz - 1);
-              if (za > zb) continue;
-              const int c0 = (x * ry + y) * rz + za;
-              const int c1 = (x * ry + y) * rz + zb;
-              const int64_t i0 = offn[c0];
-              const int64_t i1 = (c1 + 1 < total) ? (int64_t)offn[c1 + 1] : len2;
-              scan(i0, i1);
-            }
-          }
-        }
+        visit_shell_lane(g, offn, len2, c, rho, scan);
         if (rho >= 1) {
-          float g = (float)rho * cell * 0.999f;
-          if (g >= r) { unfinished = false; break; }
-          if (wd < FLT_MAX && wd <= g * g) { unfinished = false; break; }
+          const float reach = ring_reach(rho, g.cell);
+          if (reach >= r) { unfinished = false; break; }
+          if (wd < FLT_MAX && wd <= reach * reach) { unfinished = false; break; }
         }
       }
     }
@@ -552,9 +434,8 @@ __global__ __launch_bounds__(256) void k_query(
 }
 
 
-// One WAVE per unfinished query.  The wave walks the same Chebyshev shells as k_query, but the
-// lanes split each shell's cell columns (an edge column is one contiguous z-run, an interior
-// column its two cap cells) and keep private top-K lists.  After every shell the global K-th
+// One WAVE per unfinished query.  The wave walks the same shells as k_query, but the lanes split
+// each shell's cell columns (visit_shell_wave) and keep private top-K lists.  After every shell the global K-th
 // distance is obtained by K rounds of a wave-wide arg-min over the lanes' list heads, and the
 // same stopping rule as k_query is applied; the final K results come out of the same merge --
 // identical (d2, idx) order, so the output does not depend on which kernel served a query.
@@ -572,12 +453,7 @@ __device__ __forceinline__ void wave_merge(const TopK<KMAX>& best, int K, float&
     for (int j = 0; j < KMAX; ++j) if (j == head) { hd = best.d[j]; hi = best.id[j]; }
     float md = hd;
     int mi = hi;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      float od = __shfl_xor(md, o);
-      int oi = __shfl_xor(mi, o);
-      if (pair_lt(od, oi, md, mi)) { md = od; mi = oi; }
-    }
+    wave_argmin(md, mi);
     if (hd == md && hi == mi && md < FLT_MAX) ++head;   // the winner pops its head
     if (k == K - 1) kth = md;
     if (drow && lane == 0) {
@@ -611,13 +487,9 @@ __global__ __launch_bounds__(64) void k_query_tail(
   const float4* s4 = xyzi + (int64_t)blockIdx.y * p2_stride;
   const bool self = (points1 == nullptr);
   const int64_t len2 = lengths2 ? lengths2[n] : p2_stride;
-  const float* gp = params + n * ISO_GRID3_PARAMS;
-  const float mnx = gp[0], mny = gp[1], mnz = gp[2], delta = gp[3];
-  const int rx = (int)gp[4], ry = (int)gp[5], rz = (int)gp[6];
-  const int total = (int)gp[7];
+  const Grid3 g = grid3_load(params, n);
   const float r = radius[n];
   const float r2 = r * r;
-  const float cell = 1.0f / delta;
   const float* s2 = sorted2 + (int64_t)n * p2_stride * 3;
   const int32_t* sidx = sorted_idx2 + (int64_t)n * p2_stride;
   const int32_t* offn = off + (int64_t)n * g_stride;
@@ -634,71 +506,42 @@ __global__ __launch_bounds__(64) void k_query_tail(
       qx = q[0]; qy = q[1]; qz = q[2];
       row = t;
     }
-    const float lim = 1.0e6f;
-    const int cx = (int)fminf(fmaxf(floorf((qx - mnx) * delta), -lim), lim);
-    const int cy = (int)fminf(fmaxf(floorf((qy - mny) * delta), -lim), lim);
-    const int cz = (int)fminf(fmaxf(floorf((qz - mnz) * delta), -lim), lim);
-    const float rho_f = ceilf(r * delta * 1.0011f);
-    const int gapx = cx < 0 ? -cx : (cx >= rx ? cx - rx + 1 : 0);
-    const int gapy = cy < 0 ? -cy : (cy >= ry ? cy - ry + 1 : 0);
-    const int gapz = cz < 0 ? -cz : (cz >= rz ? cz - rz + 1 : 0);
-    const int rho0 = max(gapx, max(gapy, gapz));
-    const int span = max(rx, max(ry, rz)) + rho0;
-    const int rho_max = (rho_f < (float)span) ? (int)rho_f : span;
+    const QueryCell c = query_cell(g, qx, qy, qz);
+    const float rho_f = ceilf(r * g.delta * 1.0011f);
+    const int rho_max = (rho_f < (float)c.span) ? (int)rho_f : c.span;
     TopK<KMAX> best;
     best.init();
     float wd = FLT_MAX;
     int wi = 0x7fffffff;
     int found = 0;   // candidates within r seen by this lane (capped: only >= K matters)
-    for (int rho = rho0; rho <= rho_max; ++rho) {
-      const int x0 = max(cx - rho, 0), x1 = min(cx + rho, rx - 1);
-      const int y0 = max(cy - rho, 0), y1 = min(cy + rho, ry - 1);
-      if (x0 <= x1 && y0 <= y1) {
-        const int ny = y1 - y0 + 1;
-        const int ncols = (x1 - x0 + 1) * ny;
-        for (int col = lane; col < ncols; col += 64) {
-          const int x = x0 + col / ny, y = y0 + col % ny;
-          const bool edge = (x == cx - rho) || (x == cx + rho) || (y == cy - rho) || (y == cy + rho);
-          const int nseg = edge ? 1 : (rho == 0 ? 1 : 2);
-          for (int sgm = 0; sgm < nseg; ++sgm) {
-            int za, zb;
-            if (edge) { za = cz - rho; zb = cz + rho; }
-            else if (sgm == 0) { za = cz - rho; zb = cz - rho; }
-            else { za = cz + rho; zb = cz + rho; }
-            za = max(za, 0); zb = min(zb, rz - 1);
-            if (za > zb) continue;
-            const int c0 = (x * ry + y) * rz + za, c1 = (x * ry + y) * rz + zb;
-            const int64_t i0 = offn[c0];
-            const int64_t i1 = (c1 + 1 < total) ? (int64_t)offn[c1 + 1] : len2;
-            for (int64_t i = i0; i < i1; ++i) {
-              const float4 ca = s4[i];
-              float dx = qx - ca.x, dy = qy - ca.y, dz = qz - ca.z;
-              float d2 = (dx * dx + dy * dy) + dz * dz;
-              if (d2 < r2) {
-                if (found < KMAX) ++found;
-                if (d2 <= wd) {
-                  int oi = __float_as_int(ca.w);
-                  if (pair_lt(d2, oi, wd, wi)) {
-                    best.push(d2, oi, K);
-                    wd = best.worst(K);
-                    wi = best.worst_id(K);
-                  }
-                }
+    for (int rho = c.rho0; rho <= rho_max; ++rho) {
+      visit_shell_wave(g, offn, len2, c, rho, lane, [&](int64_t i0, int64_t i1) {
+        for (int64_t i = i0; i < i1; ++i) {
+          const float4 ca = s4[i];
+          const float d2 = rec_d2(qx, qy, qz, ca);
+          if (d2 < r2) {
+            if (found < KMAX) ++found;
+            if (d2 <= wd) {
+              int oi = __float_as_int(ca.w);
+              if (pair_lt(d2, oi, wd, wi)) {
+                best.push(d2, oi, K);
+                wd = best.worst(K);
+                wi = best.worst_id(K);
               }
             }
           }
         }
-      }
+      });
       if (rho >= 1) {
-        const float g = (float)rho * cell * 0.999f;
-        if (g >= r) break;
+        const float reach = ring_reach(rho, g.cell);
+        if (reach >= r) break;
         int tot = found;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) tot += __shfl_xor(tot, o);
         if (tot >= K) {                       // wave-uniform
           float kth;
           wave_merge<KMAX>(best, K, kth, nullptr, nullptr, nullptr, nullptr, lane);
-          if (kth < FLT_MAX && kth <= g * g) break;
+          if (kth < FLT_MAX && kth <= reach * reach) break;
         }
       }
     }
@@ -707,19 +550,6 @@ __global__ __launch_bounds__(64) void k_query_tail(
                      idxs_out + ((int64_t)n * p1_stride + row) * K,
                      nn_out ? nn_out + ((int64_t)n * p1_stride + row) * K * 3 : nullptr,
                      points2 ? points2 + (int64_t)n * p2_stride * 3 : nullptr, lane);
-  }
-}
-
-// candidate records for the query kernels: (x, y, z, original index as bits) -- one 16-B load per
-// candidate instead of three strided dword loads plus the index load
-__global__ void k_pack_xyzi(const float* __restrict__ sorted, const int32_t* __restrict__ sorted_idx,
-                            const int64_t* __restrict__ lengths, int64_t p_stride, float4* __restrict__ out) {
-  const int n = blockIdx.y;
-  const int64_t len = lengths ? lengths[n] : p_stride;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len;
-       i += (int64_t)gridDim.x * blockDim.x) {
-    const float* q = sorted + ((int64_t)n * p_stride + i) * 3;
-    out[(int64_t)n * p_stride + i] = make_float4(q[0], q[1], q[2], __int_as_float(sorted_idx[(int64_t)n * p_stride + i]));
   }
 }
 
@@ -951,11 +781,7 @@ extern "C" int iso_frnn_query(const float* points1, const int64_t* lengths1,
   int32_t* tail_list = tail_count + 64 * ((n_clouds + 63) / 64);
   float4* xyzi = reinterpret_cast<float4*>((char*)workspace + query_ws_tail_bytes(n_clouds, p1_stride));
   hipLaunchKernelGGL(k_zero_i32, dim3(iso_div_up(n_clouds, 64)), dim3(64), 0, s, tail_count, n_clouds);
-  if (p2_stride > 0) {
-    int gp = iso_div_up(p2_stride, 256);
-    if (gp > 4096) gp = 4096;
-    hipLaunchKernelGGL(k_pack_xyzi, dim3(gp, n_clouds), dim3(256), 0, s, sorted2, sorted_idx2, lengths2, p2_stride, xyzi);
-  }
+  pack_xyzi(sorted2, sorted_idx2, lengths2, n_clouds, p2_stride, xyzi, s);
   int gx = iso_div_up(p1_stride, 256);
   if (gx > 65535) gx = 65535;
 #define ISO_LAUNCH_Q(KM)                                                          \

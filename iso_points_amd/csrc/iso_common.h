@@ -88,6 +88,47 @@ __device__ __forceinline__ float iso_wave_sum(float v) {
   return v;
 }
 
+// order-preserving float <-> uint key (integer atomicMin / atomicMax on floats)
+__device__ __forceinline__ unsigned iso_f2key(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float iso_key2f(unsigned k) {
+  const unsigned u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
+  return __uint_as_float(u);
+}
+
+// inclusive scan across the 64 lanes of a wave
+__device__ __forceinline__ int iso_wave_incl_scan(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// exclusive scan of one int per thread over a workgroup of WAVES waves (all threads call); returns the exclusive
+// prefix, the workgroup's total in `total` (valid in all threads).  lds: WAVES ints, free again on return.
+template <int WAVES>
+__device__ __forceinline__ int iso_block_excl_scan(int v, int& total, int* lds) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int inc = iso_wave_incl_scan(v);
+  if (lane == 63) lds[w] = inc;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int i = 0; i < WAVES; ++i) {
+    const int t = lds[i];
+    if (i < w) base += t;
+    tot += t;
+  }
+  total = tot;
+  __syncthreads();
+  return base + inc - v;
+}
+
 // Zero a few words with a kernel instead of hipMemsetAsync: memset nodes of a few bytes captured into a
 // HIP graph were observed to leave garbage on replay (ROCm 7.2), a kernel node is exact.
 static __global__ void iso_k_zero_words(uint32_t* p, int64_t n) {

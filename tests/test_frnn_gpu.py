@@ -195,3 +195,47 @@ def test_tail_kernel_isolated_queries(dev, K):
     q = torch.cat([outl * 1.5, far + 0.1, dense[:, :100]], dim=1)
     d, i, nn, grid = _cmp(dev, q, p, None, None, K, 0.45)
     assert int(grid.tail_counts.sum()) > 0
+
+
+def _slab_and_queries():
+    """A flat slab (constant z: one layer of cells, rz == 1; x extent twice the y extent: rx != ry) and queries inside
+    it and beyond each of its six faces at 0.01, 0.5 and 5 times its largest extent E.  The diagonal set lies beyond
+    the slab's four corners: the first shells that touch the grid hold no point near enough, so those queries are
+    still open after the lane's own shells."""
+    g = torch.Generator().manual_seed(31)
+    E, z0 = 2.0, 0.3
+    lo = torch.tensor([0.0, 0.0, z0])
+    ext = torch.tensor([E, 0.5 * E, 0.0])
+    slab = lo + ext * torch.rand(3000, 3, generator=g)
+    slab[:4, :2] = torch.tensor([[0.0, 0.0], [E, 0.0], [0.0, 0.5 * E], [E, 0.5 * E]])   # the box is exactly E x E/2
+    qs = [lo + ext * torch.rand(64, 3, generator=g)]
+    for dist in (0.01 * E, 0.5 * E, 5.0 * E):
+        for axis in range(3):
+            for side in (0, 1):
+                q = lo + ext * torch.rand(8, 3, generator=g)
+                q[:, axis] = lo[axis] - dist if side == 0 else lo[axis] + ext[axis] + dist
+                qs.append(q)
+    q = torch.cat(qs)
+    assert q.shape == (208, 3)
+    corners = torch.tensor([[sx, sy, sz] for sx in (-1.0, 1.0) for sy in (-1.0, 1.0) for sz in (0.0, 1.0)])
+    diag = lo + 0.5 * ext + corners * (0.5 * ext + 5.0 * E)
+    return E, slab[None], q[None], diag[None]
+
+
+@pytest.mark.parametrize("K", [1, 8])
+def test_slab_grid_queries_beyond_every_face(dev, K):
+    """Every way into the cell-grid walk at once, where its callers could disagree: a one-layer grid with rx != ry,
+    queries inside, just outside, and many shells away from every face.  Radius 20 E: everything is in reach; radius
+    0.25 E: the far queries get -1 rows.  The Chamfer search returns the kNN's K = 1 column.  Exact, every row."""
+    from iso_points_amd.loss import nearest_points
+    E, slab, q, diag = _slab_and_queries()
+    d, i, _, _ = _cmp(dev, q, slab, None, None, K, 20.0 * E)
+    assert (i >= 0).all()
+    _, i_near, _, _ = _cmp(dev, q, slab, None, None, K, 0.25 * E)
+    assert (i_near[0, :64, 0] >= 0).all() and (i_near[0, 64 + 48:] == -1).all()   # 0.5 E and 5 E away: no hit
+    _, i_diag, _, grid = _cmp(dev, diag, slab, None, None, K, 20.0 * E)
+    assert int(grid.tail_counts.sum()) == diag.shape[1]     # all of them finished by k_query_tail
+    if K == 1:
+        for qq, ii in ((q, i), (diag, i_diag)):
+            _, idx = nearest_points(qq.to(dev), slab.to(dev))
+            assert torch.equal(idx, ii[..., 0])
