@@ -961,6 +961,60 @@ int iso_chamfer_backward(const float* x, const float* y, const int64_t* x_length
                          int n_clouds, int64_t p1, int64_t p2, void* workspace, int64_t workspace_bytes,
                          void* stream);
 
+/* ----------------------------------------------------------------------
+ * H. Point-to-mesh face distances (csrc/pfdist.hip)
+ *    replaces pytorch3d.loss.point_mesh_face_distance and pytorch3d.loss.point_mesh_distance.point_face_distance
+ *    (CUDA-only, not vendored) where the reference calls them:
+ *      evaluation.py:78, :123-126, :146, :173-176   pf_dist of the checkpoints' and the final mesh
+ *      DSS/training/losses.py:536-598                SignedDistanceLoss: the distance it signs
+ *    Clouds and meshes are PACKED: points (P,3), tris (T,3,3) f32, with first (N) and len (N) i64 per cloud / mesh; point
+ *    and face indices are packed indices.  All entries enqueue on `stream` and do not synchronise; no float atomics: two
+ *    runs give the same bits.
+ *
+ * d2(p, t): the squared distance from p to the closed triangle t, evaluated as |p - (b0 v0 + b1 v1 + b2 v2)|^2 in f32
+ * without FMA contraction: a pure function of the pair.  A triangle of area > min_triangle_area whose plane projection
+ * of p has no negative weight is measured there, every other pair by the triangle's three edges; a triangle without
+ * area gives no NaN.
+ *
+ * iso_pfdist_prepare: what the searches need of their inputs, either half optional (NULL output):
+ *   points_padded_out (N,p_stride,3): the clouds, one row each (the input of the point grid);
+ *   centroids_out (N,t_stride,3): the faces' centroids, one row per mesh (the input of the face grid); radius_out (T):
+ *   R_t = the largest centroid-to-vertex distance, rounded up; rmax_out (N): the largest R_t of each mesh.
+ *
+ * iso_pfdist_forward, direction 0 (point -> face): for every point the nearest face of its own mesh, ties -> the lower
+ * face index.  The grid (sorted_targets, sorted_idx, off, grid_params; section B at an infinite radius) is built on the
+ * CENTROIDS; after shell rho of the walk every unseen face is at least ring_reach(rho) - R_max away, which is the stop
+ * rule.  One face far larger than a cell drives every walk of its mesh toward brute force; the result stays exact.
+ * direction 1 (face -> point): for every face the nearest point of its own cloud, ties -> the lower point index; the
+ * grid is built on the padded POINTS, the walk starts at the face's centroid and stops once
+ * sqrt(best) + R_t <= ring_reach(rho).  d2_out (Q) f32, idx_out (Q) i32 (packed index; a query without targets: d2 = 0,
+ * idx = -1), sums_out (N) = the sum of d2 over the cloud's points / the mesh's faces: per-workgroup partial sums added in
+ * a fixed order.  p_stride / t_stride >= every len.  workspace: iso_pfdist_forward_workspace_bytes(direction, N,
+ * the queries' stride, the targets' stride), 16-B aligned.
+ *
+ * iso_pfdist_backward: gradient of sum_q weights[q] d2(q, idx[q]) of one direction w.r.t. the points and the
+ * triangles, indices constant: with r = p - c, d d2 / d p = 2 r and d d2 / d v_k = -2 b_k r.  The queries' side is
+ * written directly; the targets' side is a gather over lists counting-sorted by target (integer atomics,
+ * iso_prefix_sum), each list summed in ascending query order by its own lane (up to 8 entries) or by one wave (sorted up
+ * to 1024 entries, beyond that a strided scan of idx).  grad_points (P,3) or grad_tris (T,9) may be NULL: that side is
+ * skipped.  workspace: iso_pfdist_backward_workspace_bytes(direction, P, T), 16-B aligned.                          */
+int iso_pfdist_prepare(const float* points, const int64_t* pts_first, const int64_t* pts_len, const float* tris,
+                       const int64_t* tris_first, const int64_t* tris_len, int n_clouds, int64_t n_points,
+                       int64_t n_tris, int64_t p_stride, int64_t t_stride, float* points_padded_out,
+                       float* centroids_out, float* radius_out, float* rmax_out, void* stream);
+int64_t iso_pfdist_forward_workspace_bytes(int direction, int n_clouds, int64_t q_stride, int64_t target_stride);
+int iso_pfdist_forward(int direction, const float* points, const int64_t* pts_first, const int64_t* pts_len,
+                       const float* tris, const int64_t* tris_first, const int64_t* tris_len,
+                       const float* sorted_targets, const int32_t* sorted_idx, const int32_t* off,
+                       const float* grid_params, const float* centroids, const float* radius, const float* rmax,
+                       float min_triangle_area, float* d2_out, int32_t* idx_out, float* sums_out, int n_clouds,
+                       int64_t n_points, int64_t n_tris, int64_t p_stride, int64_t t_stride, int64_t g_stride,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+int64_t iso_pfdist_backward_workspace_bytes(int direction, int64_t n_points, int64_t n_tris);
+int iso_pfdist_backward(int direction, const float* points, const float* tris, const int32_t* idx,
+                        const float* weights, float min_triangle_area, float* grad_points, float* grad_tris,
+                        int64_t n_points, int64_t n_tris, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

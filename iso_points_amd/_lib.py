@@ -149,6 +149,12 @@ SIGNATURES = {
     "iso_chamfer_nearest": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _L, _P, _L, _P]),
     "iso_chamfer_backward_workspace_bytes": (_L, [_I, _L, _L]),
     "iso_chamfer_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _P, _L, _P]),
+    "iso_pfdist_prepare": (_I, [_P, _P, _P, _P, _P, _P, _I, _L, _L, _L, _L, _P, _P, _P, _P, _P]),
+    "iso_pfdist_forward_workspace_bytes": (_L, [_I, _I, _L, _L]),
+    "iso_pfdist_forward": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _P, _I, _L, _L, _L, _L, _L,
+                                _P, _L, _P]),
+    "iso_pfdist_backward_workspace_bytes": (_L, [_I, _L, _L]),
+    "iso_pfdist_backward": (_I, [_I, _P, _P, _P, _P, _F, _P, _P, _L, _L, _P, _L, _P]),
 }
 
 class Follow(ctypes.Structure):

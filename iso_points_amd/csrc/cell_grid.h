@@ -1,5 +1,5 @@
 // The walk over the uniform cell grid of frnn.hip, stated once for the kernels that search it (k_query, k_query_tail,
-// k_cham_nearest).  Device code only, private to csrc/.
+// k_cham_nearest, k_pf_nearest).  Device code only, private to csrc/.
 //
 // A cloud's points are sorted by cell (x-major, z fastest), so a run of cells of one (x, y) column is one contiguous
 // range of (x, y, z, original index) records.  A query walks Chebyshev shells of cells around its own cell: shells 0 and

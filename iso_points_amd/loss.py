@@ -1,6 +1,8 @@
 """Chamfer distance between point clouds: pytorch3d.loss.chamfer_distance as the reference calls it
 (evaluation.py:119-122 and :169-172 -- chamfer_p / chamfer_n; DSS/training/trainer.py:256 -- the validation
-metric train_mvr.py:196 selects checkpoints by).
+metric train_mvr.py:196 selects checkpoints by), and the distances between point clouds and mesh faces:
+pytorch3d.loss.point_mesh_face_distance (evaluation.py:123-126, :173-176 -- pf_dist) and
+pytorch3d.loss.point_mesh_distance.point_face_distance (DSS/training/losses.py:536-598, SignedDistanceLoss).
 
 The nearest-point search runs on the cell grid of iso_points_amd.frnn (exact, any distance), fused with the
 normal term and the per-cloud sums; the backward pass is a gather over counting-sorted index lists.  Neither
@@ -10,7 +12,7 @@ import torch
 
 from . import _lib
 from . import frnn
-from .levelset_sampling import convert_pointclouds_to_tensor
+from .levelset_sampling import convert_pointclouds_to_tensor, host_lengths, with_host_lengths
 
 _INF = float("inf")
 
@@ -181,3 +183,247 @@ def chamfer_distance(x, y, x_lengths=None, y_lengths=None, x_normals=None, y_nor
         return sx + sy
 
     return reduce(cham_x, cham_y), (reduce(norm_x, norm_y) if normals else None)
+
+
+# ------------------------------------------------------------------------------------------ point <-> mesh face distances
+class _Segments(object):
+    """The packed layout of a batch: per cloud and per mesh the first row and the row count, on the device (int64) and on
+    the host; the strides are the longest cloud and the longest mesh (at least one row)."""
+
+    def __init__(self, p_first, p_host, P, t_first, t_host, T, fn):
+        if len(p_host) != len(t_host):
+            raise ValueError("%s: points and tris must have the same batch size" % fn)
+        self.N, self.P, self.T = len(p_host), P, T
+        self.p_first, self.p_len, self.p_len_host = self._lengths(p_first, p_host, P, "points_first_idx", fn)
+        self.t_first, self.t_len, self.t_len_host = self._lengths(t_first, t_host, T, "tris_first_idx", fn)
+        self.p_stride = max(self.p_len_host + [1])
+        self.t_stride = max(self.t_len_host + [1])
+
+    @staticmethod
+    def _lengths(first, host, total, what, fn):
+        # a packed layout tiles its rows: the first cloud starts at row 0 and every cloud ends where the next one starts
+        ends = host[1:] + [total]
+        if host and (host[0] != 0 or any(e < f for f, e in zip(host, ends))):
+            raise ValueError("%s: %s must start at 0, ascend and stay within the %d packed rows" % (fn, what, total))
+        first = first.to(torch.int64)
+        end = torch.full((1,), total, dtype=torch.int64, device=first.device)
+        return first.contiguous(), (torch.cat([first[1:], end]) - first).contiguous(), [e - f for f, e in zip(host, ends)]
+
+    def to(self, dev):
+        for k in ("p_first", "p_len", "t_first", "t_len"):
+            setattr(self, k, getattr(self, k).to(dev))
+        return self
+
+
+def _host_copy(t):
+    host = getattr(t, "_iso_host", None)
+    if host is None or getattr(t, "_iso_host_version", None) != t._version:
+        host = [int(v) for v in t.tolist()]    # one read: a first_idx built by the caller on the GPU
+    return host
+
+
+def _first_of(lengths, host):
+    """first_idx of clouds of these lengths, with its host copy."""
+    first, acc = [], 0
+    for l in host:
+        first.append(acc)
+        acc += int(l)
+    return with_host_lengths(torch.cumsum(lengths, 0) - lengths, first)
+
+
+def _pf_search(direction, points, tris, seg, min_area):
+    """One direction on validated float32 inputs: d2 (Q,) f32, idx (Q,) int32 packed, sums (N,) f32."""
+    dev = points.device
+    N, P, T = seg.N, seg.P, seg.T
+    Q = P if direction == 0 else T
+    cen = torch.empty((N, seg.t_stride, 3), dtype=torch.float32, device=dev)
+    rad = torch.empty((max(T, 1),), dtype=torch.float32, device=dev)
+    rmax = torch.empty((max(N, 1),), dtype=torch.float32, device=dev)
+    pad = torch.empty((N, seg.p_stride, 3), dtype=torch.float32, device=dev) if direction == 1 else None
+    d2 = torch.empty((Q,), dtype=torch.float32, device=dev)
+    idx = torch.empty((Q,), dtype=torch.int32, device=dev)
+    sums = torch.empty((N,), dtype=torch.float32, device=dev)
+    if N == 0:
+        return d2, idx, sums
+    p = _lib.ptr
+    _lib.call("iso_pfdist_prepare", p(points), p(seg.p_first), p(seg.p_len), p(tris), p(seg.t_first), p(seg.t_len), N, P, T,
+              seg.p_stride, seg.t_stride, p(pad), p(cen), p(rad), p(rmax), _lib.stream())
+    grid = _grid_of(cen, seg.t_len) if direction == 0 else _grid_of(pad, seg.p_len)
+    strides = (seg.p_stride, seg.t_stride) if direction == 0 else (seg.t_stride, seg.p_stride)
+    ws_bytes = _lib.load().iso_pfdist_forward_workspace_bytes(direction, N, *strides)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    _lib.call("iso_pfdist_forward", direction, p(points), p(seg.p_first), p(seg.p_len), p(tris), p(seg.t_first),
+              p(seg.t_len), p(grid.sorted_points), p(grid.sorted_idx), p(grid.off), p(grid.params), p(cen), p(rad), p(rmax),
+              float(min_area), p(d2), p(idx), p(sums), N, P, T, seg.p_stride, seg.t_stride, grid.g_stride, p(ws), ws_bytes,
+              _lib.stream())
+    return d2, idx, sums
+
+
+class _FaceDistance(torch.autograd.Function):
+    """(points (P,3), tris (T,3,3)) -> the squared distance of every query of one direction to its nearest target, the
+    per-cloud sums of them and the targets' packed indices (constants)."""
+
+    @staticmethod
+    def forward(ctx, points, tris, direction, min_area, seg):
+        d2, idx, sums = _pf_search(direction, points, tris, seg, min_area)
+        ctx.save_for_backward(points, tris, idx)
+        ctx.direction, ctx.min_area, ctx.seg = direction, min_area, seg
+        ctx.mark_non_differentiable(idx)
+        ctx.set_materialize_grads(False)
+        return d2, sums, idx
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_d2, g_sums, _g_idx):
+        points, tris, idx = ctx.saved_tensors
+        need_p, need_t = ctx.needs_input_grad[:2]
+        seg, direction = ctx.seg, ctx.direction
+        Q = seg.P if direction == 0 else seg.T
+        if not (need_p or need_t) or (g_d2 is None and g_sums is None) or Q == 0:
+            return None, None, None, None, None
+        # one weight per query: its own upstream gradient and its cloud's
+        w = g_d2.detach().float() if g_d2 is not None else None
+        if g_sums is not None:
+            rows = seg.p_len if direction == 0 else seg.t_len
+            per_cloud = torch.repeat_interleave(g_sums.detach().float(), rows, output_size=Q)
+            w = per_cloud if w is None else w + per_cloud
+        w = w.contiguous()
+        # only what is asked for: a ground-truth mesh costs neither a buffer nor its lists
+        grad_p = torch.empty_like(points) if need_p else None
+        grad_t = torch.empty_like(tris) if need_t else None
+        ws_bytes = _lib.load().iso_pfdist_backward_workspace_bytes(direction, seg.P, seg.T)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=points.device)
+        p = _lib.ptr
+        _lib.call("iso_pfdist_backward", direction, p(points), p(tris), p(idx), p(w), float(ctx.min_area), p(grad_p),
+                  p(grad_t), seg.P, seg.T, p(ws), ws_bytes, _lib.stream())
+        return grad_p, grad_t, None, None, None
+
+
+def _pf_inputs(points, points_first_idx, tris, tris_first_idx, max_points, min_triangle_area, fn):
+    """Validated (points f32 (P,3), tris f32 (T,3,3), segments) of a packed call; ValueError before any GPU work."""
+    for t, what in ((points, "points"), (tris, "tris"), (points_first_idx, "points_first_idx"),
+                    (tris_first_idx, "tris_first_idx")):
+        if not torch.is_tensor(t):
+            raise ValueError("%s: %s must be a tensor" % (fn, what))
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("%s: points must be (P, 3), got %s" % (fn, tuple(points.shape)))
+    if tris.dim() != 3 or tuple(tris.shape[1:]) != (3, 3):
+        raise ValueError("%s: tris must be (T, 3, 3), got %s" % (fn, tuple(tris.shape)))
+    if points_first_idx.dim() != 1 or tris_first_idx.dim() != 1:
+        raise ValueError("%s: points_first_idx and tris_first_idx must be of shape (N,)" % fn)
+    if points_first_idx.is_floating_point() or tris_first_idx.is_floating_point():
+        raise ValueError("%s: points_first_idx and tris_first_idx hold integer rows" % fn)
+    if not float(min_triangle_area) >= 0.0:
+        raise ValueError("%s: min_triangle_area must not be negative" % fn)
+    seg = _Segments(points_first_idx, _host_copy(points_first_idx), points.shape[0], tris_first_idx,
+                    _host_copy(tris_first_idx), tris.shape[0], fn)
+    if max_points is not None and max(seg.p_len_host + [0]) > int(max_points):
+        raise ValueError("%s: a cloud holds more than max_points = %d points" % (fn, int(max_points)))
+    _on_gpu(points, tris)
+    return points.float().contiguous(), tris.float().contiguous(), seg.to(points.device)
+
+
+def point_face_distance(points, points_first_idx, tris, tris_first_idx, max_points, min_triangle_area=0.0):
+    """pytorch3d.loss.point_mesh_distance.point_face_distance: (P,) squared distances from every point of the packed
+    clouds `points` (P,3) to the nearest face of its own mesh among the packed triangles `tris` (T,3,3);
+    points_first_idx / tris_first_idx (N,) give each cloud's / mesh's first row.  A point whose mesh is empty gets 0.
+
+    The distance to a face is |p - c|^2 at the closest point c of the closed triangle, in float32; a face whose area is
+    <= min_triangle_area is measured by its three edges only (pytorch3d's current default is 5e-3, the version the
+    reference pins has none: 0.0 here).  Differentiable w.r.t. points and tris with the nearest faces held constant;
+    values and gradients are the same bits from run to run.  The search walks the cell grid of the faces' centroids and
+    stops once the best distance is within the walked reach less the mesh's largest centroid-to-vertex distance: exact
+    for any mesh, but one face far larger than the rest makes that radius large and drives every walk of its mesh toward
+    a brute force."""
+    pts, tr, seg = _pf_inputs(points, points_first_idx, tris, tris_first_idx, max_points, min_triangle_area,
+                              "point_face_distance")
+    return _FaceDistance.apply(pts, tr, 0, float(min_triangle_area), seg)[0]
+
+
+def face_point_distance(points, points_first_idx, tris, tris_first_idx, max_points, min_triangle_area=0.0):
+    """pytorch3d.loss.point_mesh_distance.face_point_distance: (T,) squared distances from every face to the nearest
+    point of its own cloud; arguments, arithmetic and gradients as point_face_distance.  The search walks the cell grid
+    of the points from the face's centroid and allows for the face's own radius."""
+    pts, tr, seg = _pf_inputs(points, points_first_idx, tris, tris_first_idx, max_points, min_triangle_area,
+                              "face_point_distance")
+    return _FaceDistance.apply(pts, tr, 1, float(min_triangle_area), seg)[0]
+
+
+def nearest_faces(points, tris, points_first_idx=None, tris_first_idx=None, min_triangle_area=0.0):
+    """For every point of `points` (P,3) the nearest face of `tris` (T,3,3): (d2 (P,) f32, idx (P,) int64 into tris), ties
+    to the lower face index; without first_idx tensors one cloud against one mesh.  A point without faces gets d2 = 0,
+    idx = -1.  No gradient."""
+    if (points_first_idx is None) != (tris_first_idx is None):
+        raise ValueError("nearest_faces: first_idx for both points and tris or for neither")
+    if points_first_idx is None and torch.is_tensor(points):
+        points_first_idx = with_host_lengths(torch.zeros((1,), dtype=torch.int64, device=points.device), [0])
+        tris_first_idx = with_host_lengths(torch.zeros((1,), dtype=torch.int64, device=points.device), [0])
+    pts, tr, seg = _pf_inputs(points, points_first_idx, tris, tris_first_idx, None, min_triangle_area, "nearest_faces")
+    d2, idx, _ = _pf_search(0, pts.detach(), tr.detach(), seg, float(min_triangle_area))
+    return d2, idx.long()
+
+
+def _packed_mesh(meshes, fn):
+    """(tris (T,3,3), first_idx (N,)) of a Meshes-like object or a (verts (N,V,3), faces (N,F,3) long[, num_faces]) tuple."""
+    if all(hasattr(meshes, a) for a in ("verts_packed", "faces_packed", "mesh_to_faces_packed_first_idx",
+                                        "num_faces_per_mesh")):
+        verts, faces = meshes.verts_packed(), meshes.faces_packed()
+        if verts.dim() != 2 or verts.shape[-1] != 3 or faces.dim() != 2 or faces.shape[-1] != 3:
+            raise ValueError("%s: verts_packed must be (V, 3) and faces_packed (F, 3)" % fn)
+        return verts[faces.long()], meshes.mesh_to_faces_packed_first_idx()
+    if not isinstance(meshes, (tuple, list)) or len(meshes) not in (2, 3):
+        raise ValueError("%s: meshes must be a Meshes object or a (verts, faces[, num_faces]) tuple" % fn)
+    verts, faces = meshes[0], meshes[1]
+    if not torch.is_tensor(verts) or verts.dim() != 3 or verts.shape[-1] != 3:
+        raise ValueError("%s: verts must be (N, V, 3)" % fn)
+    if (not torch.is_tensor(faces) or faces.dim() != 3 or faces.shape[-1] != 3 or faces.shape[0] != verts.shape[0]
+            or faces.is_floating_point()):
+        raise ValueError("%s: faces must be an integer tensor (N, F, 3) with the batch size of verts" % fn)
+    N, F = faces.shape[0], faces.shape[1]
+    tris = verts[torch.arange(N, device=verts.device)[:, None, None], faces.long()]          # (N,F,3,3)
+    if len(meshes) == 2 or meshes[2] is None:
+        num = with_host_lengths(torch.full((N,), F, dtype=torch.int64, device=verts.device), [F] * N)
+        return tris.reshape(N * F, 3, 3), _first_of(num, [F] * N)
+    num = torch.as_tensor(meshes[2])
+    host = host_lengths(num)
+    num = num.reshape(-1)
+    if len(host) != N or any(l < 0 or l > F for l in host):
+        raise ValueError("%s: num_faces must hold one count in [0, %d] per mesh" % (fn, F))
+    tris = torch.cat([tris[n, :host[n]] for n in range(N)]) if N else tris.reshape(0, 3, 3)
+    return tris, _first_of(num.to(device=verts.device, dtype=torch.int64), host)
+
+
+def point_mesh_face_distance(meshes, pcls, min_triangle_area=0.0):
+    """pytorch3d.loss.point_mesh_face_distance: the scalar
+    sum_p d2_p / num_points[cloud(p)] / N + sum_t d2_t / num_faces[mesh(t)] / N
+    over the points' distances to the nearest face of their mesh and the faces' distances to the nearest point of their
+    cloud (point_face_distance, face_point_distance).  `meshes` is an object with verts_packed / faces_packed /
+    mesh_to_faces_packed_first_idx / num_faces_per_mesh or a (verts (N,V,3), faces (N,F,3) long[, num_faces]) tuple;
+    `pcls` a padded (N,P,3) tensor or a Pointclouds-like object.  The per-cloud and per-mesh sums are added in a fixed
+    order: the value and the gradients w.r.t. the points and the triangles are the same bits from run to run (the step from
+    the triangles to shared vertices is torch's own indexing backward).  With lengths that carry a host copy (or none) the
+    call reads nothing back from the device."""
+    fn = "point_mesh_face_distance"
+    tris, t_first = _packed_mesh(meshes, fn)
+    pts, p_len = convert_pointclouds_to_tensor(pcls)
+    if pts.dim() != 3 or pts.shape[-1] != 3:
+        raise ValueError("%s: pcls must be (N, P, 3), got %s" % (fn, tuple(pts.shape)))
+    N, P = pts.shape[0], pts.shape[1]
+    p_len = torch.as_tensor(p_len)
+    host = host_lengths(p_len)               # before any view of it: the host copy rides on this very tensor
+    p_len = p_len.reshape(-1)
+    if len(host) != N or any(l < 0 or l > P for l in host):
+        raise ValueError("%s: the clouds' lengths must hold one count in [0, %d] per cloud" % (fn, P))
+    if t_first.shape[0] != N:
+        raise ValueError("%s: meshes and pcls must have the same batch size" % fn)
+    if all(l == P for l in host):
+        packed = pts.reshape(N * P, 3)
+    else:
+        packed = torch.cat([pts[n, :host[n]] for n in range(N)])
+    p_first = _first_of(p_len.to(device=pts.device, dtype=torch.int64), host)
+    pts32, tr32, seg = _pf_inputs(packed, p_first, tris, t_first, None, min_triangle_area, fn)
+    _, sums_p, _ = _FaceDistance.apply(pts32, tr32, 0, float(min_triangle_area), seg)
+    _, sums_t, _ = _FaceDistance.apply(pts32, tr32, 1, float(min_triangle_area), seg)
+    point_dist = (sums_p / seg.p_len.clamp(min=1).float()).sum() / float(max(N, 1))
+    face_dist = (sums_t / seg.t_len.clamp(min=1).float()).sum() / float(max(N, 1))
+    return point_dist + face_dist
