@@ -6,9 +6,14 @@
 // 1 together as the nine z-runs of the 3x3x3 block, every further shell rho column by column -- an edge column
 // (|x - cx| = rho or |y - cy| = rho) is one z-run, an interior column its two cap cells.  After shell rho every point
 // within ring_reach(rho, cell) of the query has been seen.  The visitors below clamp to the grid and hand each run to
-// `visit(i0, i1)` as a record range; what a kernel does with a record, when it stops and who finishes an open query
-// stay with the kernel.  Candidates are ordered by (d2, index) with d2 = rec_d2(), so a result does not depend on the
-// order of visits, nor on which kernel or lane served the query.
+// `visit(i0, i1)` as a record range.  Candidates are ordered by (d2, index) with d2 = rec_d2(), so a result does not
+// depend on the order of visits, nor on which kernel or lane served the query.
+//
+// Who finishes a query its lane leaves open: a search for the single nearest target (k_cham_nearest, k_pf_nearest) runs
+// nearest_walk() below, which owns both phases -- the lane's own shells, then the lane's whole wave, one open query after
+// the other, inside the same launch.  Such a kernel supplies how a record range is scored, when a query is closed and
+// how the wave gets at another lane's query, nothing else.  The K-best list of k_query and its hand-off of open queries to
+// k_query_tail through a second launch stay with frnn.hip.
 #pragma once
 #include <float.h>
 #include "iso_common.h"
@@ -142,6 +147,72 @@ __device__ __forceinline__ void scan_run2(const float4* __restrict__ s4, int64_t
     const float4 cb = s4[two ? i + 1 : i];
     cand(rec_d2(qx, qy, qz, ca), __float_as_int(ca.w));
     if (two) cand(rec_d2(qx, qy, qz, cb), __float_as_int(cb.w));
+  }
+}
+
+// ---- the nearest target of one query per lane, (d2, index) smallest ---------------------------------------------------
+// The lane walks the 3x3x3 block and up to kRingCap further shells alone; a query still open then (an isolated point, a
+// query far from the targets, a stop rule that needs a long reach) is finished by the whole wave, one open query after the
+// other: one slow lane would otherwise hold its wave for thousands of dependent loads.  The kernel supplies
+//   score(q, i0, i1, bd, bi) : the records [i0, i1) against query q, folded into the pair (bd, bi)
+//   closed(q, bd, rho)       : nothing beyond shell rho (>= 1) can beat bd
+//   wave_query(src, q)       : q = lane src's query, the same value in every lane of the wave
+// and starts from bd = FLT_MAX, bi = INT_MAX; the result is left in the owning lane, bd = FLT_MAX without a target.
+
+// where a lane left its query: its cell, the next shell to walk, and whether anything is left to walk
+struct WalkState { QueryCell c; int rho_next; bool open; };
+
+// the lane's own shells of the query `own` at p.  A function of its own: written into nearest_walk, k_pf_nearest<1> needs
+// 131 instead of 127 VGPRs and loses a wave
+template <class Q, class Score, class Closed>
+__device__ __forceinline__ WalkState nearest_lane_phase(const Grid3& g, const int32_t* __restrict__ off, int64_t len,
+                                                        const Q& own, float px, float py, float pz, Score&& score,
+                                                        Closed&& closed, float& bd, int& bi) {
+  WalkState w;
+  w.c = query_cell(g, px, py, pz);
+  const int rho_stop = min(w.c.span, w.c.rho0 + kRingCap);
+  auto scan = [&](int64_t i0, int64_t i1) { score(own, i0, i1, bd, bi); };
+  w.open = true;
+  int rho = w.c.rho0;
+  if (w.c.rho0 == 0 && rho_stop >= 1) {
+    visit_block27(g, off, len, w.c, scan);
+    if (closed(own, bd, 1)) w.open = false;
+    rho = 2;
+  }
+  for (; rho <= rho_stop && w.open; ++rho) {
+    visit_shell_lane(g, off, len, w.c, rho, scan);
+    if (rho >= 1 && closed(own, bd, rho)) w.open = false;
+  }
+  w.rho_next = rho;
+  if (w.rho_next > w.c.span) w.open = false;
+  return w;
+}
+
+// both phases; EVERY lane of the wave calls it, `live` says whether the lane has a query at all
+template <class Q, class Score, class Closed, class WaveQuery>
+__device__ __forceinline__ void nearest_walk(const Grid3& g, const int32_t* __restrict__ off, int64_t len, int lane,
+                                             bool live, const Q& own, float px, float py, float pz, Score&& score,
+                                             Closed&& closed, WaveQuery&& wave_query, float& bd, int& bi) {
+  WalkState w = {{0, 0, 0, 0, -1}, 0, false};
+  if (live) w = nearest_lane_phase(g, off, len, own, px, py, pz, score, closed, bd, bi);
+  unsigned long long todo = __ballot(w.open);
+  while (todo) {
+    const int src = __ffsll((long long)todo) - 1;
+    todo &= todo - 1;
+    Q wq;
+    wave_query(src, wq);
+    QueryCell wc;
+    wc.cx = __shfl(w.c.cx, src); wc.cy = __shfl(w.c.cy, src); wc.cz = __shfl(w.c.cz, src);
+    wc.rho0 = __shfl(w.c.rho0, src); wc.span = __shfl(w.c.span, src);
+    const int w_first = __shfl(w.rho_next, src);
+    float wd = __shfl(bd, src);
+    int wi = __shfl(bi, src);
+    for (int rho = w_first; rho <= wc.span; ++rho) {
+      visit_shell_wave(g, off, len, wc, rho, lane, [&](int64_t i0, int64_t i1) { score(wq, i0, i1, wd, wi); });
+      wave_argmin(wd, wi);
+      if (rho >= 1 && closed(wq, wd, rho)) break;
+    }
+    if (lane == src) { bd = wd; bi = wi; }
   }
 }
 

@@ -2,19 +2,18 @@
 // Stands in for pytorch3d.loss.chamfer_distance as the reference calls it (include/isopoints.h
 // section G for the call sites).
 //
-//   k_cham_nearest  : one lane per query walks the cell grid as cell_grid.h states it (the walk, the d2
-//                     expression and the (d2, index) order k_query uses, with K = 1 and no radius); a query
-//                     still open after kRingCap further shells is finished by its whole WAVE in the same
-//                     launch.  The lane then forms the normal term and the workgroup reduces both sums in
-//                     a fixed order.
+//   k_cham_nearest  : one lane per query runs cell_grid.h's nearest_walk (the walk, the d2 expression and the
+//                     (d2, index) order k_query uses, with K = 1 and no radius; a query still open after
+//                     kRingCap further shells is finished by its whole WAVE in the same launch).  The lane
+//                     then forms the normal term and the workgroup reduces both sums in a fixed order.
 //   k_cham_finish   : adds the workgroups' partial sums of a cloud in a fixed order (64 chunks in index order)
-//   backward        : k_cham_count / iso_prefix_sum / k_cham_fill sort the other cloud's nearest indices by
-//                     target (integer atomics only); k_cham_grad sums each target's list in ascending query
-//                     order, k_cham_grad_heavy serves the long lists with one wave each.  Both clouds' gradients
-//                     run in the same launches (blockIdx.z = the side).  No float atomics: two runs give the
-//                     same bits.
+//   backward        : gather_lists.h sorts the other cloud's nearest indices by target (integer atomics only);
+//                     k_cham_grad sums each target's list in ascending query order, k_cham_grad_heavy serves the
+//                     long lists with one wave each.  Both clouds' gradients run in the same launches
+//                     (blockIdx.z = the side).  No float atomics: two runs give the same bits.
 #include <float.h>
 #include "cell_grid.h"
+#include "gather_lists.h"
 
 #pragma clang fp contract(off)
 
@@ -22,8 +21,6 @@ namespace {
 
 constexpr int kNearBlock = 256;
 constexpr int kMaxPartials = 4096;   // workgroups per cloud of k_cham_nearest = partial sums k_cham_finish adds
-constexpr int kLightList = 8;        // targets chosen by at most this many queries are summed by their own lane
-constexpr int kSortList = 1024;      // longer lists are not sorted: the wave scans the whole index row instead
 constexpr float kNormEps = 1e-6f;    // torch.nn.functional.cosine_similarity's eps
 
 // 1 - |cos(a, b)|, cos = a.b / (max(|a|, eps) max(|b|, eps))
@@ -33,6 +30,8 @@ __device__ __forceinline__ float normal_term(const float* __restrict__ a, const 
   const float dot = (ax * bx + ay * by) + az * bz;
   return 1.0f - fabsf(dot / (fmaxf(la, kNormEps) * fmaxf(lb, kNormEps)));
 }
+
+struct Pt { float x, y, z; };
 
 template <bool NORMALS>
 __global__ __launch_bounds__(kNearBlock) void k_cham_nearest(
@@ -55,67 +54,26 @@ __global__ __launch_bounds__(kNearBlock) void k_cham_nearest(
   for (int64_t t0 = (int64_t)blockIdx.x * kNearBlock; t0 < p1; t0 += (int64_t)gridDim.x * kNearBlock) {
     const int64_t t = t0 + threadIdx.x;
     const bool row = t < p1;
-    float qx = 0.f, qy = 0.f, qz = 0.f;
+    Pt q = {0.f, 0.f, 0.f};
+    if (row && t < len1 && len2 > 0) {
+      const float* qp = x + ((int64_t)n * p1 + t) * 3;
+      q.x = qp[0]; q.y = qp[1]; q.z = qp[2];
+    }
+    const bool live = row && t < len1 && len2 > 0 && q.x == q.x && q.y == q.y && q.z == q.z;
     float bd = FLT_MAX;
     int bi = 0x7fffffff;
-    QueryCell c = {0, 0, 0, 0, -1};
-    int rho_next = 0;
-    bool open = false;
-    if (row && t < len1 && len2 > 0) {
-      const float* q = x + ((int64_t)n * p1 + t) * 3;
-      qx = q[0]; qy = q[1]; qz = q[2];
-    }
-    if (row && t < len1 && len2 > 0 && qx == qx && qy == qy && qz == qz) {
-      c = query_cell(g, qx, qy, qz);
-      const int rho_stop = min(c.span, c.rho0 + kRingCap);
-      auto scan = [&](int64_t i0, int64_t i1) {
-        scan_run2(s4, i0, i1, qx, qy, qz, [&](float d2, int oi) {
-          if (pair_lt(d2, oi, bd, bi)) { bd = d2; bi = oi; }
-        });
-      };
-      open = true;
-      int rho = c.rho0;
-      if (c.rho0 == 0 && rho_stop >= 1) {
-        visit_block27(g, offn, len2, c, scan);
-        const float reach = ring_reach(1, g.cell);
-        if (bd < FLT_MAX && bd <= reach * reach) open = false;
-        rho = 2;
-      }
-      for (; rho <= rho_stop && open; ++rho) {
-        visit_shell_lane(g, offn, len2, c, rho, scan);
-        if (rho >= 1) {
-          const float reach = ring_reach(rho, g.cell);
-          if (bd < FLT_MAX && bd <= reach * reach) open = false;
-        }
-      }
-      rho_next = rho;
-      if (rho_next > c.span) open = false;
-    }
-    // the wave finishes its open queries one after the other (an isolated point, a query far from the cloud): one
-    // slow lane would otherwise hold its wave for thousands of dependent loads
-    unsigned long long todo = __ballot(open);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const float wx = __shfl(qx, src), wy = __shfl(qy, src), wz = __shfl(qz, src);
-      QueryCell wc;
-      wc.cx = __shfl(c.cx, src); wc.cy = __shfl(c.cy, src); wc.cz = __shfl(c.cz, src);
-      wc.rho0 = __shfl(c.rho0, src); wc.span = __shfl(c.span, src);
-      const int w_first = __shfl(rho_next, src);
-      float wd = __shfl(bd, src);
-      int wi = __shfl(bi, src);
-      for (int rho = w_first; rho <= wc.span; ++rho) {
-        visit_shell_wave(g, offn, len2, wc, rho, lane, [&](int64_t i0, int64_t i1) {
-          scan_run2(s4, i0, i1, wx, wy, wz, [&](float d2, int oi) {
-            if (pair_lt(d2, oi, wd, wi)) { wd = d2; wi = oi; }
+    nearest_walk(
+        g, offn, len2, lane, live, q, q.x, q.y, q.z,
+        [&](const Pt& w, int64_t i0, int64_t i1, float& d, int& i) {
+          scan_run2(s4, i0, i1, w.x, w.y, w.z, [&](float d2, int oi) {
+            if (pair_lt(d2, oi, d, i)) { d = d2; i = oi; }
           });
-        });
-        wave_argmin(wd, wi);
-        const float reach = ring_reach(rho, g.cell);
-        if (rho >= 1 && wd < FLT_MAX && wd <= reach * reach) break;
-      }
-      if (lane == src) { bd = wd; bi = wi; }
-    }
+        },
+        [&](const Pt&, float d, int rho) {
+          const float reach = ring_reach(rho, g.cell);
+          return d < FLT_MAX && d <= reach * reach;
+        },
+        [&](int src, Pt& w) { w.x = __shfl(q.x, src); w.y = __shfl(q.y, src); w.z = __shfl(q.z, src); }, bd, bi);
     if (row) {
       const bool found = bd < FLT_MAX;
       const float d2 = found ? bd : 0.f;
@@ -168,8 +126,9 @@ __global__ __launch_bounds__(128) void k_cham_finish(const float* __restrict__ p
 
 // ---- backward ---------------------------------------------------------------------------------------------------
 // One side of the backward pass: cloud A (p1 rows, the gradient's owner) and cloud B (p2 rows).  idx_b[j] = the row of A
-// that row j of B chose.  Both sides (x as A, y as A) run in the same launches, blockIdx.z picks the side.  Count and
-// offset rows have the common stride pm = max(P1, P2), so that one batched prefix sum serves both sides.
+// that row j of B chose: B's rows are the queries of the gather `lists`, A's rows its targets.  Both sides (x as A, y as
+// A) run in the same launches, blockIdx.z picks the side.  Count and offset rows have the common stride pm = max(P1, P2),
+// so that one batched prefix sum serves both sides.
 struct Side {
   const float* a;        // (N,p1,3)
   const float* b;        // (N,p2,3)
@@ -177,40 +136,18 @@ struct Side {
   const float* bn;
   const int64_t* a_len;
   const int32_t* idx_a;  // (N,p1): row of B chosen by row i of A
-  const int32_t* idx_b;  // (N,p2)
   const float* g_own;    // (N) scale of A's own terms
   const float* g_other;  // (N) scale of the terms of B's rows
   const float* gn_own;
   const float* gn_other;
   float* grad_a;
   float* grad_an;        // null: the normals' gradient is not wanted
-  int64_t p1, p2, pm;
-  int32_t* cnt;          // (N,pm)
-  int32_t* off;          // (N,pm)
-  int32_t* slot;         // (N,p2)
-  int32_t* list;         // (N,p2)
+  int64_t p1, p2;
+  GatherView lists;      // idx = idx_b (N,p2), rows of stride p2 (queries) and pm (targets)
   int32_t* heavy;        // (N*p1)
   int32_t* heavy_count;
 };
 struct Sides { Side d[2]; };
-
-__global__ void k_cham_count(Sides both) {
-  const Side s = blockIdx.z ? both.d[1] : both.d[0];
-  const int n = blockIdx.y;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < s.p2; j += (int64_t)gridDim.x * blockDim.x) {
-    const int i = s.idx_b[(int64_t)n * s.p2 + j];
-    if (i >= 0) s.slot[(int64_t)n * s.p2 + j] = atomicAdd(&s.cnt[(int64_t)n * s.pm + i], 1);
-  }
-}
-
-__global__ void k_cham_fill(Sides both) {
-  const Side s = blockIdx.z ? both.d[1] : both.d[0];
-  const int n = blockIdx.y;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < s.p2; j += (int64_t)gridDim.x * blockDim.x) {
-    const int i = s.idx_b[(int64_t)n * s.p2 + j];
-    if (i >= 0) s.list[(int64_t)n * s.p2 + s.off[(int64_t)n * s.pm + i] + s.slot[(int64_t)n * s.p2 + j]] = (int32_t)j;
-  }
-}
 
 // d(1 - |cos(a, b)|) / da
 __device__ __forceinline__ void normal_term_grad(const float (&a)[3], const float* __restrict__ b, float (&out)[3]) {
@@ -251,7 +188,7 @@ __global__ __launch_bounds__(256) void k_cham_grad(Sides both) {
   const float no = NORMALS ? s.gn_own[n] : 0.f, nt = NORMALS ? s.gn_other[n] : 0.f;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < s.p1; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t r = (int64_t)n * s.p1 + i;
-    const int64_t c_row = (int64_t)n * s.pm + i;
+    const int64_t c_row = (int64_t)n * s.lists.t_stride + i;
     float gp[3] = {0.f, 0.f, 0.f}, gq[3] = {0.f, 0.f, 0.f};
     if (i < len) {
       float ai[3], ani[3] = {0.f, 0.f, 0.f};
@@ -268,20 +205,12 @@ __global__ __launch_bounds__(256) void k_cham_grad(Sides both) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) { gp[c] = go * pos[c]; gq[c] = no * nrm[c]; }
       }
-      const int L = s.cnt[c_row];
+      const int L = s.lists.cnt[c_row];
       if (L > kLightList) {
         s.heavy[atomicAdd(s.heavy_count, 1)] = (int32_t)r;  // the order of this list decides nothing: one wave per entry
       } else if (L > 0) {
-        // ascending query order: take the smallest index above the last one taken, L times
-        const int32_t* li = s.list + (int64_t)n * s.p2 + s.off[c_row];
         float pos[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f};
-        int last = -1;
-        for (int k = 0; k < L; ++k) {
-          int nxt = 0x7fffffff;
-          for (int m = 0; m < L; ++m) { const int v = li[m]; if (v > last && v < nxt) nxt = v; }
-          add_pair<NORMALS>(s, n, ai, ani, nxt, pos, nrm);
-          last = nxt;
-        }
+        gather_lane(gather_list(s.lists, n, i), L, [&](int j) { add_pair<NORMALS>(s, n, ai, ani, j, pos, nrm); });
 #pragma unroll
         for (int c = 0; c < 3; ++c) { gp[c] += gt * pos[c]; gq[c] += nt * nrm[c]; }
       }
@@ -295,9 +224,8 @@ __global__ __launch_bounds__(256) void k_cham_grad(Sides both) {
   }
 }
 
-// One wave per long list.  Up to kSortList entries: the list is rank-sorted into LDS and lane l sums entries l, l + 64, ...
-// of the sorted list; beyond that: lane l visits rows l, l + 64, ... of B and takes those that chose this target.  Either
-// way every lane's sum runs in ascending query order and the 64 sums are added by the same butterfly: a fixed order.
+// One wave per long list (gather_wave): every lane's sum runs in ascending query order and the 64 sums are added by the
+// same butterfly, a fixed order.
 template <bool NORMALS>
 __global__ __launch_bounds__(64) void k_cham_grad_heavy(Sides both) {
   __shared__ int32_t s_raw[kSortList], s_sorted[kSortList];
@@ -308,8 +236,7 @@ __global__ __launch_bounds__(64) void k_cham_grad_heavy(Sides both) {
     const int64_t r = s.heavy[w];
     const int n = (int)(r / s.p1);
     const int i = (int)(r - (int64_t)n * s.p1);
-    const int64_t c_row = (int64_t)n * s.pm + i;
-    const int L = s.cnt[c_row];
+    const int L = s.lists.cnt[(int64_t)n * s.lists.t_stride + i];
     float ai[3], ani[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < 3; ++c) ai[c] = s.a[r * 3 + c];
@@ -318,24 +245,8 @@ __global__ __launch_bounds__(64) void k_cham_grad_heavy(Sides both) {
       for (int c = 0; c < 3; ++c) ani[c] = s.an[r * 3 + c];
     }
     float pos[3] = {0.f, 0.f, 0.f}, nrm[3] = {0.f, 0.f, 0.f};
-    if (L <= kSortList) {
-      const int32_t* li = s.list + (int64_t)n * s.p2 + s.off[c_row];
-      __syncthreads();                                   // the previous entry's readers of the LDS lists are done
-      for (int m = lane; m < L; m += 64) s_raw[m] = li[m];
-      __syncthreads();
-      for (int m = lane; m < L; m += 64) {
-        const int v = s_raw[m];
-        int rank = 0;
-        for (int q = 0; q < L; ++q) rank += (s_raw[q] < v) ? 1 : 0;   // query indices are distinct
-        s_sorted[rank] = v;
-      }
-      __syncthreads();
-      for (int m = lane; m < L; m += 64) add_pair<NORMALS>(s, n, ai, ani, s_sorted[m], pos, nrm);
-    } else {
-      const int32_t* ib = s.idx_b + (int64_t)n * s.p2;
-      for (int64_t j = lane; j < s.p2; j += 64)
-        if (ib[j] == i) add_pair<NORMALS>(s, n, ai, ani, j, pos, nrm);
-    }
+    gather_wave(s.lists, n, i, L, lane, s_raw, s_sorted,
+                [&](int64_t j) { add_pair<NORMALS>(s, n, ai, ani, j, pos, nrm); });
 #pragma unroll
     for (int c = 0; c < 3; ++c) { pos[c] = iso_wave_sum(pos[c]); nrm[c] = iso_wave_sum(nrm[c]); }
     if (lane == 0) {
@@ -351,14 +262,6 @@ __global__ __launch_bounds__(64) void k_cham_grad_heavy(Sides both) {
   }
 }
 
-int near_grid(int64_t p1) {
-  int gx = iso_div_up(p1, kNearBlock);
-  if (gx > kMaxPartials) gx = kMaxPartials;
-  return gx < 1 ? 1 : gx;
-}
-
-int64_t align16(int64_t b) { return (b + 15) / 16 * 16; }
-
 }  // namespace
 
 // workspace of iso_chamfer_nearest: [candidate records: N*P2 float4][partials: N * grid * 2 floats]
@@ -366,7 +269,7 @@ extern "C" int64_t iso_chamfer_nearest_workspace_bytes(int n_clouds, int64_t p1,
   if (n_clouds < 0) n_clouds = 0;
   if (p1 < 0) p1 = 0;
   if (p2 < 0) p2 = 0;
-  return 16 * (int64_t)n_clouds * p2 + align16((int64_t)n_clouds * near_grid(p1) * 2 * 4) + 16;
+  return 16 * (int64_t)n_clouds * p2 + iso_align16((int64_t)n_clouds * iso_capped_grid(p1, kNearBlock, kMaxPartials) * 2 * 4) + 16;
 }
 
 extern "C" int iso_chamfer_nearest(const float* x, const int64_t* x_lengths, const float* sorted_y,
@@ -390,7 +293,7 @@ extern "C" int iso_chamfer_nearest(const float* x, const int64_t* x_lengths, con
   hipStream_t s = (hipStream_t)stream;
   float4* xyzi = reinterpret_cast<float4*>(workspace);
   float* partials = reinterpret_cast<float*>((char*)workspace + 16 * (int64_t)n_clouds * p2);
-  const int gx = near_grid(p1);
+  const int gx = iso_capped_grid(p1, kNearBlock, kMaxPartials);
   pack_xyzi(sorted_y, sorted_idx_y, y_lengths, n_clouds, p2, xyzi, s);
   if (x_normals)
     hipLaunchKernelGGL(k_cham_nearest<true>, dim3(gx, n_clouds), dim3(kNearBlock), 0, s, x, x_lengths, xyzi, y_lengths, off,
@@ -403,16 +306,12 @@ extern "C" int iso_chamfer_nearest(const float* x, const int64_t* x_lengths, con
   return ISO_OK;
 }
 
-// workspace of iso_chamfer_backward: cnt, off (N*P1 ints each), slot, list (N*P2 each), heavy (N*P1), heavy_count (4 ints),
-// then the prefix sum's own
-// workspace of iso_chamfer_backward, R = N * max(P1, P2) ints per array and side: cnt (2R) + heavy counters (4), off (2R),
-// heavy (2R), slot (2R), list (2R), then the prefix sum's own
-static int64_t backward_ints(int n_clouds, int64_t pm) { return 10 * (int64_t)n_clouds * pm + 4; }
-
+// workspace of iso_chamfer_backward: gather_lists.h's, with R = N * max(P1, P2) target rows and query rows per side
 extern "C" int64_t iso_chamfer_backward_workspace_bytes(int n_clouds, int64_t p1, int64_t p2) {
   if (n_clouds < 0) n_clouds = 0;
   const int64_t pm = p1 > p2 ? (p1 > 0 ? p1 : 0) : (p2 > 0 ? p2 : 0);
-  return align16(4 * backward_ints(n_clouds, pm)) + iso_prefix_sum_workspace_bytes(pm, 2 * n_clouds) + 16;
+  const int64_t R = (int64_t)n_clouds * pm;
+  return gather_workspace_bytes(2 * R, 2 * R, pm, 2 * n_clouds);
 }
 
 extern "C" int iso_chamfer_backward(const float* x, const float* y, const int64_t* x_lengths, const int64_t* y_lengths,
@@ -438,34 +337,28 @@ extern "C" int iso_chamfer_backward(const float* x, const float* y, const int64_
   ISO_REQUIRE(((uintptr_t)workspace & 15) == 0, ISO_ERR_INVALID, "iso_chamfer_backward: workspace must be 16-B aligned");
   hipStream_t s = (hipStream_t)stream;
   const int64_t R = (int64_t)n_clouds * pm;
-  int32_t* cnt = (int32_t*)workspace;       // [2][N][pm]
-  int32_t* heavy_count = cnt + 2 * R;       // zeroed together with cnt
-  int32_t* offp = heavy_count + 4;
-  int32_t* heavy = offp + 2 * R;
-  int32_t* slot = heavy + 2 * R;
-  int32_t* list = slot + 2 * R;
-  void* scan_ws = (char*)workspace + align16(4 * backward_ints(n_clouds, pm));
+  const GatherWorkspace w = gather_carve(workspace, 2 * R, 2 * R);   // every array [2][N][pm]
   Sides both;
   int ns = 0;
+  auto lists = [&](const int32_t* idx_b, int64_t n_a, int64_t n_b) {
+    return GatherView{idx_b, w.cnt + ns * R, w.off + ns * R, w.slot + ns * R, w.list + ns * R, n_b, n_a, n_b, pm};
+  };
   if (grad_x && p1 > 0) {
-    both.d[ns] = Side{x, y, x_normals, y_normals, x_lengths, idx_x, idx_y, g_dx, g_dy, g_nx, g_ny, grad_x, grad_x_normals,
-                      p1, p2, pm, cnt + ns * R, offp + ns * R, slot + ns * R, list + ns * R, heavy + ns * R, heavy_count + ns};
+    both.d[ns] = Side{x, y, x_normals, y_normals, x_lengths, idx_x, g_dx, g_dy, g_nx, g_ny, grad_x, grad_x_normals,
+                      p1, p2, lists(idx_y, p1, p2), w.heavy + ns * R, w.heavy_count + ns};
     ++ns;
   }
   if (grad_y && p2 > 0) {
-    both.d[ns] = Side{y, x, y_normals, x_normals, y_lengths, idx_y, idx_x, g_dy, g_dx, g_ny, g_nx, grad_y, grad_y_normals,
-                      p2, p1, pm, cnt + ns * R, offp + ns * R, slot + ns * R, list + ns * R, heavy + ns * R, heavy_count + ns};
+    both.d[ns] = Side{y, x, y_normals, x_normals, y_lengths, idx_y, g_dy, g_dx, g_ny, g_nx, grad_y, grad_y_normals,
+                      p2, p1, lists(idx_x, p2, p1), w.heavy + ns * R, w.heavy_count + ns};
     ++ns;
   }
   if (ns == 0) return ISO_OK;
   if (ns == 1) both.d[1] = both.d[0];
-  iso_zero_words(cnt, 2 * R + 4, s);
-  int gm = iso_div_up(pm, 256);
-  if (gm > 4096) gm = 4096;
-  hipLaunchKernelGGL(k_cham_count, dim3(gm, n_clouds, ns), dim3(256), 0, s, both);
-  int rc = iso_prefix_sum(cnt, offp, pm, ns * n_clouds, pm, scan_ws, iso_prefix_sum_workspace_bytes(pm, 2 * n_clouds), stream);
+  const int gm = iso_capped_grid(pm, 256, 4096);
+  const int rc = gather_build(GatherViews{{both.d[0].lists, both.d[1].lists}}, ns, n_clouds, pm, w, 2 * R, pm,
+                              2 * n_clouds, s);
   if (rc != ISO_OK) return rc;
-  hipLaunchKernelGGL(k_cham_fill, dim3(gm, n_clouds, ns), dim3(256), 0, s, both);
   const int gh = (int)(R < 2048 ? R : 2048);
   if (normals) {
     hipLaunchKernelGGL(k_cham_grad<true>, dim3(gm, n_clouds, ns), dim3(256), 0, s, both);

@@ -29,6 +29,16 @@ void iso_set_error(const char* fmt, ...);
 
 static inline int iso_div_up(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
+static inline int64_t iso_align16(int64_t bytes) { return (bytes + 15) / 16 * 16; }
+
+// One thread per row up to `cap` workgroups (at least one), grid-stride beyond.  Where every workgroup writes a partial
+// sum, the cap is the number of partials and so part of the result's bits: it stays with the caller.
+static inline int iso_capped_grid(int64_t rows, int block, int cap) {
+  int g = iso_div_up(rows, block);
+  if (g > cap) g = cap;
+  return g < 1 ? 1 : g;
+}
+
 // Grid for an HBM-bound element-wise kernel: enough workgroups to fill 256 CUs
 // several times over, grid-stride the rest (guide: cap ~2048 blocks).
 static inline int iso_stream_grid(int64_t n, int block) {

@@ -7,22 +7,22 @@
 //                      non-negative float: a max has no order)
 //   k_pf_pack_tris   : the records of the point -> face walk: three float4 per face in the grid's sorted order,
 //                      (v0, local face index as bits), (v1, -), (v2, -): a candidate is 48 contiguous bytes
-//   k_pf_nearest<0>  : point -> face.  One lane per point walks the grid of the CENTROIDS as cell_grid.h states it; after
-//                      shell rho every unseen face lies at least ring_reach(rho) - R_max away, so the walk stops once
-//                      sqrt(best) <= ring_reach(rho) - R_max.  A query still open after kRingCap further shells is
-//                      finished by its whole wave.
+//   k_pf_nearest<0>  : point -> face.  One lane per point walks the grid of the CENTROIDS with cell_grid.h's
+//                      nearest_walk (the lane's own shells, then its whole wave); after shell rho every unseen face lies
+//                      at least ring_reach(rho) - R_max away, so the walk stops once sqrt(best) <= ring_reach(rho) - R_max.
 //   k_pf_nearest<1>  : face -> point.  The query walks the grid of the POINTS from the face's centroid; a point at distance
 //                      d from the face is at most d + R_t from the centroid: stop once sqrt(best) + R_t <= ring_reach(rho).
 //   k_pf_finish      : adds the workgroups' partial sums of a cloud in a fixed order
-//   backward         : the query side is one term per query (k_pf_grad_query); the target side is a gather over
-//                      counting-sorted lists (k_pf_count / iso_prefix_sum / k_pf_fill, integer atomics only), each list
-//                      summed in ascending query order by its own lane (k_pf_grad_target) or by one wave
-//                      (k_pf_grad_heavy).  No float atomics: two runs give the same bits.
+//   backward         : the query side is one term per query (k_pf_grad_query); the target side is a gather over the
+//                      counting-sorted lists of gather_lists.h (integer atomics only), each list summed in ascending
+//                      query order by its own lane (k_pf_grad_target) or by one wave (k_pf_grad_heavy).  No float
+//                      atomics: two runs give the same bits.
 //
 // d2(p, t) is pf_closest(): a pure function of the pair (contraction off), so a result does not depend on the order of
 // visits, the lane or the kernel that served the query.  Candidates are ordered by (d2, index).
 #include <float.h>
 #include "cell_grid.h"
+#include "gather_lists.h"
 
 #pragma clang fp contract(off)
 
@@ -30,8 +30,6 @@ namespace {
 
 constexpr int kPfBlock = 256;
 constexpr int kPfMaxPartials = 1024;   // workgroups per cloud of k_pf_nearest = partial sums k_pf_finish adds
-constexpr int kPfLightList = 8;        // targets chosen by at most this many queries are summed by their own lane
-constexpr int kPfSortList = 1024;      // longer lists are not sorted: the wave scans the whole index array instead
 constexpr float kRadiusUp = 1.00001f;  // R_t is rounded up: the stop rules may only stop late
 constexpr float kReachDown = 0.9999f;  // and the reach left after R is rounded down
 
@@ -248,53 +246,19 @@ __global__ __launch_bounds__(kPfBlock) void k_pf_nearest(PfSearch a) {
     PfQuery qu;
     qu.p[0] = qu.p[1] = qu.p[2] = 0.f;
     qu.R = 0.f;
+    if (row && len2 > 0) pf_load_query<DIR>(a, n, t, q, qu);
+    const bool live = row && len2 > 0 && qu.p[0] == qu.p[0] && qu.p[1] == qu.p[1] && qu.p[2] == qu.p[2];
     float bd = FLT_MAX;
     int bi = 0x7fffffff;
-    QueryCell c = {0, 0, 0, 0, -1};
-    int rho_next = 0;
-    bool open = false;
-    if (row && len2 > 0) pf_load_query<DIR>(a, n, t, q, qu);
-    if (row && len2 > 0 && qu.p[0] == qu.p[0] && qu.p[1] == qu.p[1] && qu.p[2] == qu.p[2]) {
-      c = query_cell(g, qu.p[0], qu.p[1], qu.p[2]);
-      const int rho_stop = min(c.span, c.rho0 + kRingCap);
-      auto scan = [&](int64_t i0, int64_t i1) { pf_scan<DIR>(rec, i0, i1, qu, a.min_area, bd, bi); };
-      open = true;
-      int rho = c.rho0;
-      if (c.rho0 == 0 && rho_stop >= 1) {
-        visit_block27(g, offn, len2, c, scan);
-        if (pf_closed(bd, 1, g.cell, qu.R)) open = false;
-        rho = 2;
-      }
-      for (; rho <= rho_stop && open; ++rho) {
-        visit_shell_lane(g, offn, len2, c, rho, scan);
-        if (rho >= 1 && pf_closed(bd, rho, g.cell, qu.R)) open = false;
-      }
-      rho_next = rho;
-      if (rho_next > c.span) open = false;
-    }
-    // the wave finishes its open queries one after the other: with R_max above a cell, or a query far from the mesh, one
-    // slow lane would otherwise hold its wave for thousands of dependent loads
-    unsigned long long todo = __ballot(open);
-    while (todo) {
-      const int src = __ffsll((long long)todo) - 1;
-      todo &= todo - 1;
-      const int64_t wt = t0 + (threadIdx.x - lane) + src;
-      PfQuery wq;
-      pf_load_query<DIR>(a, n, wt, q_first + wt, wq);
-      QueryCell wc;
-      wc.cx = __shfl(c.cx, src); wc.cy = __shfl(c.cy, src); wc.cz = __shfl(c.cz, src);
-      wc.rho0 = __shfl(c.rho0, src); wc.span = __shfl(c.span, src);
-      const int w_first = __shfl(rho_next, src);
-      float wd = __shfl(bd, src);
-      int wi = __shfl(bi, src);
-      for (int rho = w_first; rho <= wc.span; ++rho) {
-        visit_shell_wave(g, offn, len2, wc, rho, lane,
-                         [&](int64_t i0, int64_t i1) { pf_scan<DIR>(rec, i0, i1, wq, a.min_area, wd, wi); });
-        wave_argmin(wd, wi);
-        if (rho >= 1 && pf_closed(wd, rho, g.cell, wq.R)) break;
-      }
-      if (lane == src) { bd = wd; bi = wi; }
-    }
+    nearest_walk(
+        g, offn, len2, lane, live, qu, qu.p[0], qu.p[1], qu.p[2],
+        [&](const PfQuery& w, int64_t i0, int64_t i1, float& d, int& i) { pf_scan<DIR>(rec, i0, i1, w, a.min_area, d, i); },
+        [&](const PfQuery& w, float d, int rho) { return pf_closed(d, rho, g.cell, w.R); },
+        [&](int src, PfQuery& wq) {   // the wave reloads the open query: cheaper than shuffling up to 13 floats
+          const int64_t wt = t0 + (threadIdx.x - lane) + src;
+          pf_load_query<DIR>(a, n, wt, q_first + wt, wq);
+        },
+        bd, bi);
     if (row) {
       const bool found = bd < FLT_MAX;
       const float d2 = found ? bd : 0.f;
@@ -336,15 +300,11 @@ __global__ __launch_bounds__(64) void k_pf_finish(const float* __restrict__ part
 struct PfBack {
   const float* points;
   const float* tris;
-  const int32_t* idx;   // (Q)
   const float* w;       // (Q)
   float* grad_query;    // DIR 0: (P,3); DIR 1: (T,9); null = not wanted
   float* grad_target;   // DIR 0: (T,9); DIR 1: (P,3); null = not wanted
   int64_t n_q, n_t;
-  int32_t* cnt;         // (n_t)
-  int32_t* off;         // (n_t)
-  int32_t* slot;        // (n_q)
-  int32_t* list;        // (n_q)
+  GatherView lists;     // one cloud: idx (Q) = the packed target of each query
   int32_t* heavy;       // (n_t)
   int32_t* heavy_count;
   float min_area;
@@ -387,7 +347,7 @@ __global__ __launch_bounds__(256) void k_pf_grad_query(PfBack a) {
     float out[W];
 #pragma unroll
     for (int c = 0; c < W; ++c) out[c] = 0.f;
-    const int i = a.idx[q];
+    const int i = a.lists.idx[q];
     if (i >= 0 && i < a.n_t) {
       float r[3], bw[3];
       pf_pair<DIR>(a, q, i, r, bw);
@@ -409,21 +369,7 @@ __global__ __launch_bounds__(256) void k_pf_grad_query(PfBack a) {
   }
 }
 
-__global__ void k_pf_count(PfBack a) {
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < a.n_q; q += (int64_t)gridDim.x * blockDim.x) {
-    const int i = a.idx[q];
-    if (i >= 0 && i < a.n_t) a.slot[q] = atomicAdd(&a.cnt[i], 1);
-  }
-}
-
-__global__ void k_pf_fill(PfBack a) {
-  for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < a.n_q; q += (int64_t)gridDim.x * blockDim.x) {
-    const int i = a.idx[q];
-    if (i >= 0 && i < a.n_t) a.list[a.off[i] + a.slot[q]] = (int32_t)q;
-  }
-}
-
-// One lane per target: a list of up to kPfLightList queries is summed here in ascending query order, a longer one is
+// One lane per target: a list of up to kLightList queries is summed here in ascending query order, a longer one is
 // left to k_pf_grad_heavy (this kernel writes zero, that one adds the list's sum).
 template <int DIR>
 __global__ __launch_bounds__(256) void k_pf_grad_target(PfBack a) {
@@ -432,57 +378,32 @@ __global__ __launch_bounds__(256) void k_pf_grad_target(PfBack a) {
     float acc[W];
 #pragma unroll
     for (int c = 0; c < W; ++c) acc[c] = 0.f;
-    const int L = a.cnt[i];
-    if (L > kPfLightList) {
+    const int L = a.lists.cnt[i];
+    if (L > kLightList) {
       a.heavy[atomicAdd(a.heavy_count, 1)] = (int32_t)i;   // the order of this list decides nothing: one wave per entry
     } else if (L > 0) {
-      // ascending query order: take the smallest index above the last one taken, L times
-      const int32_t* li = a.list + a.off[i];
-      int last = -1;
-      for (int k = 0; k < L; ++k) {
-        int nxt = 0x7fffffff;
-        for (int m = 0; m < L; ++m) { const int v = li[m]; if (v > last && v < nxt) nxt = v; }
-        pf_add_target<DIR>(a, nxt, i, acc);
-        last = nxt;
-      }
+      gather_lane(gather_list(a.lists, 0, i), L, [&](int q) { pf_add_target<DIR>(a, q, i, acc); });
     }
 #pragma unroll
     for (int c = 0; c < W; ++c) a.grad_target[i * W + c] = acc[c];
   }
 }
 
-// One wave per long list.  Up to kPfSortList entries: the list is rank-sorted into LDS and lane l sums entries l, l + 64,
-// ... of the sorted list; beyond that lane l visits queries l, l + 64, ... and takes those that chose this target.  Either
-// way every lane's sum runs in ascending query order and the 64 sums are added by the same butterfly: a fixed order.
+// One wave per long list (gather_wave): every lane's sum runs in ascending query order and the 64 sums are added by the
+// same butterfly, a fixed order.
 template <int DIR>
 __global__ __launch_bounds__(64) void k_pf_grad_heavy(PfBack a) {
   constexpr int W = DIR == 0 ? 9 : 3;
-  __shared__ int32_t s_raw[kPfSortList], s_sorted[kPfSortList];
+  __shared__ int32_t s_raw[kSortList], s_sorted[kSortList];
   const int lane = threadIdx.x;
   const int count = *a.heavy_count;
   for (int w = blockIdx.x; w < count; w += gridDim.x) {
     const int i = a.heavy[w];
-    const int L = a.cnt[i];
+    const int L = a.lists.cnt[i];
     float acc[W];
 #pragma unroll
     for (int c = 0; c < W; ++c) acc[c] = 0.f;
-    if (L <= kPfSortList) {
-      const int32_t* li = a.list + a.off[i];
-      __syncthreads();                                   // the previous entry's readers of the LDS lists are done
-      for (int m = lane; m < L; m += 64) s_raw[m] = li[m];
-      __syncthreads();
-      for (int m = lane; m < L; m += 64) {
-        const int v = s_raw[m];
-        int rank = 0;
-        for (int q = 0; q < L; ++q) rank += (s_raw[q] < v) ? 1 : 0;   // query indices are distinct
-        s_sorted[rank] = v;
-      }
-      __syncthreads();
-      for (int m = lane; m < L; m += 64) pf_add_target<DIR>(a, s_sorted[m], i, acc);
-    } else {
-      for (int64_t q = lane; q < a.n_q; q += 64)
-        if (a.idx[q] == i) pf_add_target<DIR>(a, q, i, acc);
-    }
+    gather_wave(a.lists, 0, i, L, lane, s_raw, s_sorted, [&](int64_t q) { pf_add_target<DIR>(a, q, i, acc); });
 #pragma unroll
     for (int c = 0; c < W; ++c) acc[c] = iso_wave_sum(acc[c]);
     if (lane == 0) {
@@ -491,14 +412,6 @@ __global__ __launch_bounds__(64) void k_pf_grad_heavy(PfBack a) {
     }
   }
 }
-
-int pf_grid(int64_t rows, int cap) {
-  int gx = iso_div_up(rows, kPfBlock);
-  if (gx > cap) gx = cap;
-  return gx < 1 ? 1 : gx;
-}
-
-int64_t pf_align16(int64_t b) { return (b + 15) / 16 * 16; }
 
 template <int DIR>
 void pf_launch_backward(const PfBack& a, bool query_side, bool target_side, int gq, int gt, int gh, hipStream_t s) {
@@ -522,7 +435,7 @@ extern "C" int iso_pfdist_prepare(const float* points, const int64_t* pts_first,
   hipStream_t s = (hipStream_t)stream;
   if (points_padded_out && p_stride > 0 && n_points > 0) {
     ISO_REQUIRE(points && pts_first && pts_len, ISO_ERR_INVALID, "iso_pfdist_prepare: null pointer");
-    hipLaunchKernelGGL(k_pf_pad_points, dim3(pf_grid(p_stride, 4096), n_clouds), dim3(256), 0, s, points, pts_first,
+    hipLaunchKernelGGL(k_pf_pad_points, dim3(iso_capped_grid(p_stride, kPfBlock, 4096), n_clouds), dim3(256), 0, s, points, pts_first,
                        pts_len, n_points, p_stride, points_padded_out);
   }
   if (centroids_out) {
@@ -530,7 +443,7 @@ extern "C" int iso_pfdist_prepare(const float* points, const int64_t* pts_first,
                 "iso_pfdist_prepare: null pointer");
     iso_zero_words(rmax_out, n_clouds, s);
     if (t_stride > 0 && n_tris > 0)
-      hipLaunchKernelGGL(k_pf_prepare, dim3(pf_grid(t_stride, 4096), n_clouds), dim3(256), 0, s, tris, tris_first,
+      hipLaunchKernelGGL(k_pf_prepare, dim3(iso_capped_grid(t_stride, kPfBlock, 4096), n_clouds), dim3(256), 0, s, tris, tris_first,
                          tris_len, n_tris, t_stride, centroids_out, radius_out, rmax_out);
   }
   ISO_CHECK_LAUNCH("iso_pfdist_prepare");
@@ -544,7 +457,7 @@ extern "C" int64_t iso_pfdist_forward_workspace_bytes(int direction, int n_cloud
   if (q_stride < 0) q_stride = 0;
   if (target_stride < 0) target_stride = 0;
   return (direction == 0 ? 48 : 16) * (int64_t)n_clouds * target_stride +
-         pf_align16((int64_t)n_clouds * pf_grid(q_stride, kPfMaxPartials) * 4) + 16;
+         iso_align16((int64_t)n_clouds * iso_capped_grid(q_stride, kPfBlock, kPfMaxPartials) * 4) + 16;
 }
 
 extern "C" int iso_pfdist_forward(int direction, const float* points, const int64_t* pts_first, const int64_t* pts_len,
@@ -577,12 +490,12 @@ extern "C" int iso_pfdist_forward(int direction, const float* points, const int6
   hipStream_t s = (hipStream_t)stream;
   float4* rec = reinterpret_cast<float4*>(workspace);
   float* partials = reinterpret_cast<float*>((char*)workspace + (direction == 0 ? 48 : 16) * (int64_t)n_clouds * target_stride);
-  const int gx = pf_grid(q_stride, kPfMaxPartials);
+  const int gx = iso_capped_grid(q_stride, kPfBlock, kPfMaxPartials);
   PfSearch a{points, pts_first, pts_len, tris, tris_first, tris_len, rec, off, grid_params, centroids, radius, rmax,
              d2_out, idx_out, partials, n_points, n_tris, t_stride, target_stride, g_stride, min_triangle_area};
   if (direction == 0) {
     if (t_stride > 0)
-      hipLaunchKernelGGL(k_pf_pack_tris, dim3(pf_grid(t_stride, 4096), n_clouds), dim3(256), 0, s, tris, tris_first,
+      hipLaunchKernelGGL(k_pf_pack_tris, dim3(iso_capped_grid(t_stride, kPfBlock, 4096), n_clouds), dim3(256), 0, s, tris, tris_first,
                          tris_len, sorted_idx, n_tris, t_stride, rec);
     hipLaunchKernelGGL(k_pf_nearest<0>, dim3(gx, n_clouds), dim3(kPfBlock), 0, s, a);
   } else {
@@ -594,15 +507,12 @@ extern "C" int iso_pfdist_forward(int direction, const float* points, const int6
   return ISO_OK;
 }
 
-// workspace of iso_pfdist_backward: cnt (n_t) + heavy counter (4), off (n_t), heavy (n_t), slot (n_q), list (n_q), then the
-// prefix sum's own
-static int64_t pf_backward_ints(int64_t n_q, int64_t n_t) { return 3 * n_t + 2 * n_q + 4; }
-
+// workspace of iso_pfdist_backward: gather_lists.h's, with n_t target rows and n_q query rows
 extern "C" int64_t iso_pfdist_backward_workspace_bytes(int direction, int64_t n_points, int64_t n_tris) {
   if (n_points < 0) n_points = 0;
   if (n_tris < 0) n_tris = 0;
   const int64_t n_q = direction == 0 ? n_points : n_tris, n_t = direction == 0 ? n_tris : n_points;
-  return pf_align16(4 * pf_backward_ints(n_q, n_t)) + iso_prefix_sum_workspace_bytes(n_t, 1) + 16;
+  return gather_workspace_bytes(n_t, n_q, n_t, 1);
 }
 
 extern "C" int iso_pfdist_backward(int direction, const float* points, const float* tris, const int32_t* idx,
@@ -623,23 +533,14 @@ extern "C" int iso_pfdist_backward(int direction, const float* points, const flo
               ISO_ERR_WORKSPACE, "iso_pfdist_backward: workspace too small");
   ISO_REQUIRE(((uintptr_t)workspace & 15) == 0, ISO_ERR_INVALID, "iso_pfdist_backward: workspace must be 16-B aligned");
   hipStream_t s = (hipStream_t)stream;
-  int32_t* cnt = (int32_t*)workspace;
-  int32_t* heavy_count = cnt + n_t;           // zeroed together with cnt
-  int32_t* offp = heavy_count + 4;
-  int32_t* heavy = offp + n_t;
-  int32_t* slot = heavy + n_t;
-  int32_t* list = slot + n_q;
-  void* scan_ws = (char*)workspace + pf_align16(4 * pf_backward_ints(n_q, n_t));
-  PfBack a{points, tris, idx, weights, grad_query, grad_target, n_q, n_t, cnt, offp, slot, list, heavy, heavy_count,
-           min_triangle_area};
-  const int gq = pf_grid(n_q, 4096), gt = pf_grid(n_t, 4096);
+  const GatherWorkspace w = gather_carve(workspace, n_t, n_q);
+  const GatherView lists{idx, w.cnt, w.off, w.slot, w.list, n_q, n_t, n_q, n_t};
+  PfBack a{points, tris, weights, grad_query, grad_target, n_q, n_t, lists, w.heavy, w.heavy_count, min_triangle_area};
+  const int gq = iso_capped_grid(n_q, kPfBlock, 4096), gt = iso_capped_grid(n_t, kPfBlock, 4096);
   const int gh = (int)(n_t < 2048 ? (n_t < 1 ? 1 : n_t) : 2048);
   if (target_side) {
-    iso_zero_words(cnt, n_t + 4, s);
-    if (n_q > 0) hipLaunchKernelGGL(k_pf_count, dim3(gq), dim3(256), 0, s, a);
-    int rc = iso_prefix_sum(cnt, offp, n_t, 1, n_t, scan_ws, iso_prefix_sum_workspace_bytes(n_t, 1), stream);
+    const int rc = gather_build(GatherViews{{lists, lists}}, 1, 1, n_q, w, n_t, n_t, 1, s);
     if (rc != ISO_OK) return rc;
-    if (n_q > 0) hipLaunchKernelGGL(k_pf_fill, dim3(gq), dim3(256), 0, s, a);
   }
   if (direction == 0) pf_launch_backward<0>(a, query_side, target_side, gq, gt, gh, s);
   else pf_launch_backward<1>(a, query_side, target_side, gq, gt, gh, s);

@@ -46,9 +46,11 @@ def with_host_lengths(num_points, host):
 
 
 def host_lengths(num_points):
+    """The host copy of a lengths / first_idx tensor: the one it carries (with_host_lengths), else one device read, kept
+    on the tensor.  Take it before any reshape or cast of the tensor: a view does not carry the copy."""
     h = getattr(num_points, "_iso_host", None)
     if h is None or getattr(num_points, "_iso_host_version", None) != num_points._version:
-        h = [int(x) for x in num_points.tolist()]  # host sync, as the reference (:308)
+        h = [int(x) for x in num_points.reshape(-1).tolist()]  # host sync, as the reference (:308)
         with_host_lengths(num_points, h)
     return h
 

@@ -89,15 +89,14 @@ def _clouds(points, lengths, normals, what):
     if lengths is None:
         lengths = conv_len
     lengths = torch.as_tensor(lengths)
+    # the range check reads the lengths on the host: the host copy where the tensor carries one (full_lengths and every
+    # lengths tensor this package returns), so that only lengths built by the caller on the GPU cost a device read.  Taken
+    # before any reshape: the host copy rides on this very tensor
+    host = host_lengths(lengths)
     if lengths.dim() != 1:
         lengths = lengths.reshape(-1)
     if lengths.shape[0] != pts.shape[0]:
         raise ValueError("chamfer_distance: %s_lengths must have one entry per cloud" % what)
-    # the range check reads the lengths on the host: the host copy where the tensor carries one (full_lengths and every
-    # lengths tensor this package returns), so that only lengths built by the caller on the GPU cost a device read
-    host = getattr(lengths, "_iso_host", None)
-    if host is None or getattr(lengths, "_iso_host_version", None) != lengths._version:
-        host = lengths.tolist()
     if any(l > pts.shape[1] or l < 0 for l in host):
         raise ValueError("chamfer_distance: %s_lengths must lie in [0, %d]" % (what, pts.shape[1]))
     lengths = lengths.to(torch.int64)
@@ -215,13 +214,6 @@ class _Segments(object):
         return self
 
 
-def _host_copy(t):
-    host = getattr(t, "_iso_host", None)
-    if host is None or getattr(t, "_iso_host_version", None) != t._version:
-        host = [int(v) for v in t.tolist()]    # one read: a first_idx built by the caller on the GPU
-    return host
-
-
 def _first_of(lengths, host):
     """first_idx of clouds of these lengths, with its host copy."""
     first, acc = [], 0
@@ -315,8 +307,8 @@ def _pf_inputs(points, points_first_idx, tris, tris_first_idx, max_points, min_t
         raise ValueError("%s: points_first_idx and tris_first_idx hold integer rows" % fn)
     if not float(min_triangle_area) >= 0.0:
         raise ValueError("%s: min_triangle_area must not be negative" % fn)
-    seg = _Segments(points_first_idx, _host_copy(points_first_idx), points.shape[0], tris_first_idx,
-                    _host_copy(tris_first_idx), tris.shape[0], fn)
+    seg = _Segments(points_first_idx, host_lengths(points_first_idx), points.shape[0], tris_first_idx,
+                    host_lengths(tris_first_idx), tris.shape[0], fn)
     if max_points is not None and max(seg.p_len_host + [0]) > int(max_points):
         raise ValueError("%s: a cloud holds more than max_points = %d points" % (fn, int(max_points)))
     _on_gpu(points, tris)

@@ -280,6 +280,27 @@ def test_gradients_long_lists(dev, p1, p2):
     grad_case(dev, x, y, xn, yn)
 
 
+def test_gradients_scanned_list_behind_another_cloud(dev):
+    """The heavy paths with more than one cloud and P1 != P2: in cloud 1 all 1200 queries choose y[1, 0], a list beyond the
+    1024 a wave sorts, so the wave scans cloud 1's own index row (row stride 1300) behind cloud 0's, whose lists are sorted
+    by a wave; count and offset rows have the stride max(P1, P2) = 1300, the lists of this side 1300, of the other side 40."""
+    x, y = cube(1300, 101, N=2), cube(40, 102, N=2)
+    xn, yn = random_normals((2, 1300, 3), 103), random_normals((2, 40, 3), 104)
+    xl, yl = torch.tensor([1300, 1200]), torch.tensor([40, 1])
+    for t, l in ((x, xl), (y, yl), (xn, xl), (yn, yl)):
+        t[1, int(l[1]):] = float("nan")                        # padding that must never be read
+    for n in range(2):
+        assert_fair(x[n, : int(xl[n])], y[n, : int(yl[n])])
+        assert_fair(y[n, : int(yl[n])], x[n, : int(xl[n])])
+    c0, c1 = chosen_counts(x[0], y[0]), chosen_counts(x[1, :1200], y[1, :1])
+    assert 8 < c0.max() <= 1024, int(c0.max())
+    assert c1.max() > 1024, int(c1.max())
+    gpu_in = grad_case(dev, x, y, xn, yn, xl, yl)
+    # rows beyond the lengths (NaN inputs) get a zero gradient
+    assert (gpu_in[0].grad[1, 1200:] == 0).all() and (gpu_in[1].grad[1, 1:] == 0).all()
+    assert (gpu_in[2].grad[1, 1200:] == 0).all() and (gpu_in[3].grad[1, 1:] == 0).all()
+
+
 def test_gradients_ragged_batch(dev):
     x, y, xl, yl, xn, yn = ragged_batch()
     gpu_in = grad_case(dev, x, y, xn, yn, xl, yl)

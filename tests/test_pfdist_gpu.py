@@ -419,6 +419,39 @@ def test_gradient_of_a_face_chosen_by_more_than_a_thousand_points(dev):
     close(fine.grad, gt, A_t)
 
 
+def test_gradient_of_a_long_list_in_the_second_mesh_of_a_packed_batch(dev):
+    """Two icosahedra packed, 400 shell points around the first; 1100 points above one face of the second (plus 200 on its
+    shell): the list longer than 1024 belongs to a packed face index >= 20 and its queries start at packed row 400.  Point ->
+    face with a weight per query."""
+    from iso_points_amd import loss
+    centre = torch.tensor([4.0, 0.0, 0.0])
+    meshes = [sphere_tris(0), sphere_tris(0, centre=(4.0, 0.0, 0.0))]
+    g = torch.Generator().manual_seed(27)
+    c = meshes[1][7].mean(dim=0) - centre
+    near = centre + c * 1.2 + (torch.rand(1100, 3, generator=g) - 0.5) * 0.2
+    clouds = [shell_cloud(400, 28) * 1.3,
+              torch.cat([shell_cloud(200, 29) * 1.3 + centre, near])[torch.randperm(1300, generator=g)]]
+    counts = torch.bincount(all_pairs(clouds[1], meshes[1]).argmin(dim=1), minlength=20)
+    assert counts.max() > 1024 and ((counts > 8) & (counts <= 1024)).any(), counts
+    points, tris = torch.cat(clouds), torch.cat(meshes)
+    p_first, t_first = torch.tensor([0, 400], device=dev), torch.tensor([0, 20], device=dev)
+    p = points.to(dev).requires_grad_(True)
+    t = tris.to(dev).requires_grad_(True)
+    d2 = loss.point_face_distance(p, p_first, t, t_first, 1300)
+    w = torch.rand(1700, generator=g) + 0.5
+    (d2 * w.to(dev)).sum().backward()
+    pts, tr, seg = loss._pf_inputs(points.to(dev), p_first, tris.to(dev), t_first, None, 0.0, "test")
+    _, idx, _ = loss._pf_search(0, pts, tr, seg, 0.0)
+    # the search's own counts (float32: points nearest to an edge two faces share may go to either face, so they are not
+    # the float64 counts to the last point): the list beyond 1024 is the one of that face, behind mesh 0's rows
+    packed = torch.bincount(idx.long().cpu(), minlength=40)
+    assert packed[:20].max() <= 1024 and int(packed.argmax()) == 20 + int(counts.argmax()) and packed.max() > 1024, packed
+    (gp, gt), (A_p, A_t) = tol_grads(points, tris, idx.long(), w, 0)
+    print("A points %.3g, tris %.3g" % (A_p, A_t))
+    close(p.grad, gp, A_p)
+    close(t.grad, gt, A_t)
+
+
 def test_only_the_requested_gradients_are_computed(dev, monkeypatch):
     from iso_points_amd import _lib, loss
     points, tris = shell_cloud(300, 25), sphere_tris(1)
