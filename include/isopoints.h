@@ -1015,6 +1015,57 @@ int iso_pfdist_backward(int direction, const float* points, const float* tris, c
                         const float* weights, float min_triangle_area, float* grad_points, float* grad_tris,
                         int64_t n_points, int64_t n_tris, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ----------------------------------------------------------------------
+ * I. Sampling points on meshes (csrc/mesh_sample.hip)
+ *    replaces pytorch3d.ops.sample_points_from_meshes (CUDA-only, not vendored) where the reference calls it:
+ *      evaluation.py:113, :164                    the points and normals that chamfer_p / chamfer_n / pf_dist grade
+ *      scripts/create_mvr_data_from_mesh.py:171   the ground-truth cloud of a scene
+ *      tests/test_projection.py:347               the reference's own projection test
+ *    Meshes are PACKED as in section H: tris (T,3,3) f32 with first (N) and len (N) i64 per mesh (rows outside the packed
+ *    array are ignored); face indices are packed indices.  Limits: T < 2^31 and N * S < 2^31, refused beyond.  The device
+ *    entries enqueue on `stream` and do not synchronise; no float atomics: two runs give the same bits.
+ *
+ * Per face, in f32 without FMA contraction: m = (v1 - v0) x (v2 - v0), area = 0.5f * sqrtf((m.x*m.x + m.y*m.y) + m.z*m.z),
+ * unit normal = m / max(|m|, 2.220446e-16f).  iso_mesh_face_areas writes areas_out (T) and normals_out (T,3); either may
+ * be NULL.
+ *
+ * iso_mesh_sample: S samples on each of N meshes.  Sample s of mesh n takes the four words r0..r3 of Philox4x32-10 with
+ * key = (seed & 0xffffffff, seed >> 32) and counter = (s & 0xffffffff, s >> 32, n, 0):
+ *   uf = ((uint64(r0) << 21) | (r1 >> 11)) * 2^-53 (f64), u = (r2 >> 8) * 2^-24, v = (r3 >> 8) * 2^-24 (f32), all exact.
+ * C is the inclusive running sum of the mesh's f32 areas accumulated in f64 (a thread adds 8 faces in order, the 256
+ * threads of a tile of 2048 faces and then the tiles are added in order: a fixed shape, C never descends and a face
+ * without area has the C of its predecessor), A its last entry.  The face is the first f of the mesh with C[f] > uf * A
+ * (a face without area is never chosen); the point is (w0 v0 + w1 v1) + w2 v2 per component with sq = sqrtf(u),
+ * w0 = 1 - sq, w1 = sq * (1 - v), w2 = sq * v.  So a sample depends on (seed, n, s) and its mesh only: not on S, not on
+ * the other meshes, not on a launch shape.
+ *   points_out (N,S,3); normals_out (N,S,3) = the face's unit normal, face_idx_out (N,S) i32 = the packed face row,
+ *   bary_out (N,S,3) = (w0, w1, w2): each of the three may be NULL.
+ * A mesh without faces or whose A is not a positive finite number gets points = normals = bary = 0 and face_idx = -1.
+ * Launches: areas, the scan (three), the draw.  workspace: iso_mesh_sample_workspace_bytes(N, T), 16-B aligned.
+ *
+ * iso_mesh_sample_backward: gradient w.r.t. the triangles of sum_q g_points[q] . point_q + g_normals[q] . normal_q over
+ * the n_rows = N * S samples, faces and weights constant (face_idx < 0: no term):
+ *   grad_tris[f,k,:] = sum_{q: face_idx[q] = f} bary[q,k] g_points[q]   and, with G = sum_{q: face_idx[q] = f} g_normals[q],
+ *   dm = (G - n (n.G)) / |m| (G / 2.220446e-16f where |m| is below that), de1 = e2 x dm, de2 = dm x e1:
+ *   v1 += de1, v2 += de2, v0 -= de1 + de2.
+ * The sums are the gather of sections G and H: lists counting-sorted by face (integer atomics, iso_prefix_sum), each
+ * summed in ascending sample order by its own lane (up to 8 entries) or by one wave (sorted up to 1024 entries, beyond
+ * that a strided scan of face_idx).  g_normals may be NULL; faces nobody chose get 0.
+ * workspace: iso_mesh_sample_backward_workspace_bytes(T, N * S), 16-B aligned.
+ *
+ * iso_mesh_sample_draw: a HOST function (no device, no stream): out_words[4] = r0..r3 of sample `sample` of mesh `mesh`
+ * by the very routine the kernel runs, for tests that pin the generator.                                              */
+int iso_mesh_face_areas(const float* tris, int64_t n_tris, float* areas_out, float* normals_out, void* stream);
+int64_t iso_mesh_sample_workspace_bytes(int n_meshes, int64_t n_tris);
+int iso_mesh_sample(const float* tris, const int64_t* tris_first, const int64_t* tris_len, int n_meshes,
+                    int64_t n_tris, int64_t n_samples, int64_t seed, float* points_out, float* normals_out,
+                    int32_t* face_idx_out, float* bary_out, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t iso_mesh_sample_backward_workspace_bytes(int64_t n_tris, int64_t n_rows);
+int iso_mesh_sample_backward(const float* tris, const int32_t* face_idx, const float* bary, const float* g_points,
+                             const float* g_normals, float* grad_tris, int64_t n_tris, int64_t n_rows,
+                             void* workspace, int64_t workspace_bytes, void* stream);
+int iso_mesh_sample_draw(int64_t seed, int mesh, int64_t sample, uint32_t* out_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -155,6 +155,12 @@ SIGNATURES = {
                                 _P, _L, _P]),
     "iso_pfdist_backward_workspace_bytes": (_L, [_I, _L, _L]),
     "iso_pfdist_backward": (_I, [_I, _P, _P, _P, _P, _F, _P, _P, _L, _L, _P, _L, _P]),
+    "iso_mesh_face_areas": (_I, [_P, _L, _P, _P, _P]),
+    "iso_mesh_sample_workspace_bytes": (_L, [_I, _L]),
+    "iso_mesh_sample": (_I, [_P, _P, _P, _I, _L, _L, _L, _P, _P, _P, _P, _P, _L, _P]),
+    "iso_mesh_sample_backward_workspace_bytes": (_L, [_L, _L]),
+    "iso_mesh_sample_backward": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _P]),
+    "iso_mesh_sample_draw": (_I, [_L, _I, _L, _P]),
 }
 
 class Follow(ctypes.Structure):

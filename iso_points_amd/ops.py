@@ -1,0 +1,129 @@
+"""Points and normals sampled on meshes: pytorch3d.ops.sample_points_from_meshes as the reference calls it
+(evaluation.py:113 and :164 -- the clouds that chamfer_p / chamfer_n / pf_dist grade; scripts/create_mvr_data_from_mesh.py:171;
+tests/test_projection.py:347), and pytorch3d.ops.mesh_face_areas_normals.
+
+One host-side seed per call, everything else counter-based inside the kernel (Philox4x32-10 on (seed, mesh, sample)): a
+sample does not depend on num_samples, on the other meshes or on a launch shape.  The backward pass is the gather over
+counting-sorted lists of the loss module: no float atomics, values and gradients are the same bits from run to run
+(include/isopoints.h section I).
+"""
+import torch
+
+from . import _lib
+from .loss import _on_gpu, _packed_mesh
+
+_ROW_LIMIT = 2 ** 31
+
+
+class _MeshSample(torch.autograd.Function):
+    """tris (T,3,3) -> points (N,S,3), normals (N,S,3) or None, face_idx (N,S) int32 and bary (N,S,3) (constants; None
+    unless asked for or needed by the backward pass)."""
+
+    @staticmethod
+    def forward(ctx, tris, first, length, S, seed, want_normals, want_faces):
+        N, T, dev = first.shape[0], tris.shape[0], tris.device
+        keep = want_faces or ctx.needs_input_grad[0]
+        points = torch.empty((N, S, 3), dtype=torch.float32, device=dev)
+        normals = torch.empty((N, S, 3), dtype=torch.float32, device=dev) if want_normals else None
+        face = torch.empty((N, S), dtype=torch.int32, device=dev) if keep else None
+        bary = torch.empty((N, S, 3), dtype=torch.float32, device=dev) if keep else None
+        ws_bytes = _lib.load().iso_mesh_sample_workspace_bytes(N, T)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        p = _lib.ptr
+        _lib.call("iso_mesh_sample", p(tris), p(first), p(length), N, T, S, seed, p(points), p(normals), p(face), p(bary),
+                  p(ws), ws_bytes, _lib.stream())
+        ctx.save_for_backward(tris, face, bary)
+        ctx.want_normals = want_normals
+        if keep:
+            ctx.mark_non_differentiable(face, bary)
+        return points, normals, face, bary
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_points, g_normals, _g_face, _g_bary):
+        tris, face, bary = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 7
+        grad = torch.empty_like(tris)
+        T, rows = tris.shape[0], face.numel()
+        if T == 0:
+            return (grad,) + (None,) * 6
+        g_points = g_points.detach().float().contiguous()
+        g_normals = g_normals.detach().float().contiguous() if ctx.want_normals and g_normals is not None else None
+        ws_bytes = _lib.load().iso_mesh_sample_backward_workspace_bytes(T, rows)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=tris.device)
+        p = _lib.ptr
+        _lib.call("iso_mesh_sample_backward", p(tris), p(face), p(bary), p(g_points), p(g_normals), p(grad), T, rows, p(ws),
+                  ws_bytes, _lib.stream())
+        return (grad,) + (None,) * 6
+
+
+def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, return_textures=False, *, generator=None,
+                              return_faces=False):
+    """pytorch3d.ops.sample_points_from_meshes: `num_samples` points on every mesh of the batch, uniform over its surface
+    (a face with probability area / total area, a point uniform inside the face).  Returns points (N,S,3) float32; with
+    return_normals also normals (N,S,3), the unit normal of each sample's face; with return_faces also face_idx (N,S) int64
+    into the packed faces and bary (N,S,3) float32, the weights of the face's three vertices.
+
+    `meshes` is an object with verts_packed / faces_packed / mesh_to_faces_packed_first_idx / num_faces_per_mesh or a
+    (verts (N,V,3), faces (N,F,3) integer[, num_faces]) tuple.  A mesh without faces or without area gets zero points and
+    normals, face_idx = -1 and bary = 0: nothing is read back from the device to find out.  return_textures is not
+    supported.
+
+    The call draws one int64 seed on the host from `generator` (a CPU generator; torch's default one without, so
+    torch.manual_seed governs the call); sample s of mesh n is a function of (seed, n, s) and that mesh alone, so the first
+    k samples of a larger request are the smaller request.  Differentiable w.r.t. the vertices through points and normals,
+    with the faces and weights held constant; values and gradients are the same bits from run to run.  Limits, refused
+    beyond: fewer than 2^31 packed faces and fewer than 2^31 samples in all."""
+    fn = "sample_points_from_meshes"
+    if return_textures:
+        raise NotImplementedError("%s: textures are not supported" % fn)
+    S = int(num_samples)
+    if S < 0:
+        raise ValueError("%s: num_samples must not be negative" % fn)
+    tris, first = _packed_mesh(meshes, fn)
+    if not torch.is_tensor(first) or first.dim() != 1 or first.is_floating_point():
+        raise ValueError("%s: mesh_to_faces_packed_first_idx must be an integer tensor of shape (N,)" % fn)
+    N, T = first.shape[0], tris.shape[0]
+    if T >= _ROW_LIMIT:
+        raise ValueError("%s: %d packed faces; the limit is 2^31 - 1" % (fn, T))
+    if N * S >= _ROW_LIMIT:
+        raise ValueError("%s: %d meshes x %d samples; the limit is 2^31 - 1 samples in all" % (fn, N, S))
+    _on_gpu(tris)
+    dev = tris.device
+    seed = int(torch.empty((), dtype=torch.int64).random_(generator=generator))
+    if N == 0 or S == 0:
+        points = tris.new_zeros((N, S, 3), dtype=torch.float32)
+        out = (points, torch.zeros_like(points)) if return_normals else (points,)
+        if return_faces:
+            out = out + (torch.zeros((N, S), dtype=torch.int64, device=dev), torch.zeros_like(points))
+        return out if len(out) > 1 else out[0]
+    first = first.to(device=dev, dtype=torch.int64).contiguous()
+    end = torch.full((1,), T, dtype=torch.int64, device=dev)
+    length = (torch.cat([first[1:], end]) - first).contiguous()
+    points, normals, face, bary = _MeshSample.apply(tris.float().contiguous(), first, length, S, seed, bool(return_normals),
+                                                    bool(return_faces))
+    out = (points, normals) if return_normals else (points,)
+    if return_faces:
+        out = out + (face.long(), bary)
+    return out if len(out) > 1 else out[0]
+
+
+def mesh_face_areas_normals(verts, faces):
+    """pytorch3d.ops.mesh_face_areas_normals on packed inputs verts (V,3), faces (F,3) integer: (areas (F,), unit normals
+    (F,3)), float32: area = |(v1 - v0) x (v2 - v0)| / 2, normal = the cross product over max(its length, 2.2e-16).  No
+    gradient."""
+    fn = "mesh_face_areas_normals"
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[-1] != 3:
+        raise ValueError("%s: verts must be (V, 3)" % fn)
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[-1] != 3 or faces.is_floating_point():
+        raise ValueError("%s: faces must be an integer tensor (F, 3)" % fn)
+    if faces.shape[0] >= _ROW_LIMIT:
+        raise ValueError("%s: %d faces; the limit is 2^31 - 1" % (fn, faces.shape[0]))
+    _on_gpu(verts, faces)
+    tris = verts.detach()[faces.long()].float().contiguous()
+    F = tris.shape[0]
+    areas = torch.empty((F,), dtype=torch.float32, device=tris.device)
+    normals = torch.empty((F, 3), dtype=torch.float32, device=tris.device)
+    _lib.call("iso_mesh_face_areas", _lib.ptr(tris), F, _lib.ptr(areas), _lib.ptr(normals), _lib.stream())
+    return areas, normals
