@@ -1066,6 +1066,54 @@ int iso_mesh_sample_backward(const float* tris, const int32_t* face_idx, const f
                              void* workspace, int64_t workspace_bytes, void* stream);
 int iso_mesh_sample_draw(int64_t seed, int mesh, int64_t sample, uint32_t* out_words);
 
+/* ----------------------------------------------------------------------
+ * J. Sign of the point-to-mesh distance (csrc/pfsign.hip)
+ *    replaces the inside test of the reference's SignedDistanceLoss (DSS/training/losses.py:536-598), which takes the
+ *    parity of four rasterised depth layers of pytorch3d's CUDA-only MeshRasterizer under each point.  Here the sign is
+ *    exact by orientation: the angle-weighted pseudonormal test of Baerentzen & Aanaes.  With c the closest point of the
+ *    mesh to p and N the pseudonormal of the feature c lies on, the sign is that of (p - c) . N:
+ *      face interior   the face's unit normal (v1 - v0) x (v2 - v0) / |.|
+ *      edge            the sum of the unit normals of all faces that hold both end vertices
+ *      vertex          the sum over the incident corners of corner angle * the corner's face normal
+ *    Outward-wound faces give -1 inside and +1 outside; reversing the winding reverses the sign.  Meshes are PACKED:
+ *    verts (V,3) f32, faces (F,3) i64 rows of verts (a face with a row outside [0, V) counts as a face without area),
+ *    tris (F,3,3) f32 = verts[faces] as section H takes them.  Limits: V < 2^31 - 1, F < (2^31 - 1) / 3, P < 2^31 - 1, refused beyond.
+ *    The device entries enqueue on `stream` and do not synchronise; no float atomics: two runs give the same bits.
+ *
+ * iso_pfsign_normals: in f32 without FMA contraction, per face m = (v1 - v0) x (v2 - v0), n = m / |m|; a face whose |m| is
+ * not a positive finite number gets n = 0 and angles 0, so it contributes nothing anywhere and gives no NaN.  The angle of
+ * corner k is atan2f(|a x b|, a . b) with a = v[k+1] - v[k], b = v[k+2] - v[k] (indices mod 3).
+ *   face_normals_out (F,3) = n;
+ *   vert_normals_out (V,3) = sum of angle * n over the corners at the vertex, in ascending corner order (corner = 3 f + k):
+ *   the corner lists are the gather of sections G to I (counting sort on integer atomics, iso_prefix_sum), a list summed by
+ *   its own lane (up to 8 corners) or by one wave (sorted up to 1024, beyond that a strided scan of the corners);
+ *   edge_normals_out (F,3,3): slot k of face f is the edge from its vertex k to its vertex k + 1 mod 3 and holds the sum of
+ *   n_g over all faces g that hold both end vertices, in ascending g: a boundary edge gets its one face, a non-manifold
+ *   edge all of its faces; a slot whose two ends are the same vertex gets 0.
+ * The vectors are not normalised: only their direction is used.  A mesh without faces gets zero vectors.
+ * workspace: iso_pfsign_normals_workspace_bytes(V, F), 16-B aligned.
+ *
+ * iso_pfsign_sign: one lane per point.  idx (P) i32 is the packed nearest face as iso_pfdist_forward (direction 0) wrote
+ * it, -1 = none; min_triangle_area the value that search ran with.  The lane evaluates section H's d2(p, t) again for the
+ * closest point's weights (b0, b1, b2) and reads the feature off the weights that are exactly zero (the edge branch of
+ * d2 produces exact zeros and ones): none -> the face; one -> the edge opposite that vertex; two -> the vertex that is
+ * left.  c = (b0 v0 + b1 v1) + b2 v2, sign = ((p - c) . N < 0) ? -1 : +1: a zero product, a zero N and a point without a
+ * face give +1.
+ *   sign_out (P) f32; feature_out (P) i32: 0 = face, 1..3 = edge slot + 1, 4..6 = corner + 4, -1 = no face.
+ *
+ * iso_pfsign_pair: a HOST function (no device, no stream): one point (3) against one triangle (9) by the very routines
+ * the kernels run: d2_out[1], weights_out[3], feature_out[1], for tests that pin the arithmetic.                      */
+int64_t iso_pfsign_normals_workspace_bytes(int64_t n_verts, int64_t n_faces);
+int iso_pfsign_normals(const float* verts, const int64_t* faces, int64_t n_verts, int64_t n_faces,
+                       float* face_normals_out, float* edge_normals_out, float* vert_normals_out, void* workspace,
+                       int64_t workspace_bytes, void* stream);
+int iso_pfsign_sign(const float* points, const int32_t* idx, const float* tris, const int64_t* faces,
+                    const float* face_normals, const float* edge_normals, const float* vert_normals,
+                    float min_triangle_area, float* sign_out, int32_t* feature_out, int64_t n_points, int64_t n_faces,
+                    int64_t n_verts, void* stream);
+int iso_pfsign_pair(const float* point, const float* tri, float min_triangle_area, float* d2_out, float* weights_out,
+                    int32_t* feature_out);
+
 #ifdef __cplusplus
 }
 #endif

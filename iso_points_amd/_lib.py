@@ -161,6 +161,10 @@ SIGNATURES = {
     "iso_mesh_sample_backward_workspace_bytes": (_L, [_L, _L]),
     "iso_mesh_sample_backward": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _P, _L, _P]),
     "iso_mesh_sample_draw": (_I, [_L, _I, _L, _P]),
+    "iso_pfsign_normals_workspace_bytes": (_L, [_L, _L]),
+    "iso_pfsign_normals": (_I, [_P, _P, _L, _L, _P, _P, _P, _P, _L, _P]),
+    "iso_pfsign_sign": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _L, _L, _L, _P]),
+    "iso_pfsign_pair": (_I, [_P, _P, _F, _P, _P, _P]),
 }
 
 class Follow(ctypes.Structure):

@@ -2,7 +2,9 @@
 (evaluation.py:119-122 and :169-172 -- chamfer_p / chamfer_n; DSS/training/trainer.py:256 -- the validation
 metric train_mvr.py:196 selects checkpoints by), and the distances between point clouds and mesh faces:
 pytorch3d.loss.point_mesh_face_distance (evaluation.py:123-126, :173-176 -- pf_dist) and
-pytorch3d.loss.point_mesh_distance.point_face_distance (DSS/training/losses.py:536-598, SignedDistanceLoss).
+pytorch3d.loss.point_mesh_distance.point_face_distance (DSS/training/losses.py:536-598, SignedDistanceLoss), and the sign
+that loss gives the distance: point_mesh_sign / point_mesh_signed_distance / mesh_pseudonormals, an exact inside test by
+angle-weighted pseudonormals in place of the reference's raster parity (include/isopoints.h section J).
 
 The nearest-point search runs on the cell grid of iso_points_amd.frnn (exact, any distance), fused with the
 normal term and the per-cloud sums; the backward pass is a gather over counting-sorted index lists.  Neither
@@ -385,6 +387,34 @@ def _packed_mesh(meshes, fn):
     return tris, _first_of(num.to(device=verts.device, dtype=torch.int64), host)
 
 
+def _packed_clouds(pcls, n_meshes, flat_ok, fn):
+    """(points (P,3) packed, first_idx (N,) with its host copy) of a padded (N,P,3) tensor or a Pointclouds-like object,
+    one cloud per mesh; with flat_ok a (P,3) tensor is one cloud when there is one mesh."""
+    if flat_ok and torch.is_tensor(pcls) and pcls.dim() == 2:
+        if pcls.shape[-1] != 3 or n_meshes != 1:
+            raise ValueError("%s: a (P, 3) tensor is one cloud and needs one mesh, got %s against %d meshes"
+                             % (fn, tuple(pcls.shape), n_meshes))
+        pcls = pcls[None]
+    if flat_ok and torch.is_tensor(pcls) and pcls.dim() != 3:
+        raise ValueError("%s: pcls must be (N, P, 3) or (P, 3), got %s" % (fn, tuple(pcls.shape)))
+    pts, p_len = convert_pointclouds_to_tensor(pcls)
+    if pts.dim() != 3 or pts.shape[-1] != 3:
+        raise ValueError("%s: pcls must be (N, P, 3), got %s" % (fn, tuple(pts.shape)))
+    N, P = pts.shape[0], pts.shape[1]
+    p_len = torch.as_tensor(p_len)
+    host = host_lengths(p_len)               # before any view of it: the host copy rides on this very tensor
+    p_len = p_len.reshape(-1)
+    if len(host) != N or any(l < 0 or l > P for l in host):
+        raise ValueError("%s: the clouds' lengths must hold one count in [0, %d] per cloud" % (fn, P))
+    if n_meshes != N:
+        raise ValueError("%s: meshes and pcls must have the same batch size" % fn)
+    if all(l == P for l in host):
+        packed = pts.reshape(N * P, 3)
+    else:
+        packed = torch.cat([pts[n, :host[n]] for n in range(N)])
+    return packed, _first_of(p_len.to(device=pts.device, dtype=torch.int64), host)
+
+
 def point_mesh_face_distance(meshes, pcls, min_triangle_area=0.0):
     """pytorch3d.loss.point_mesh_face_distance: the scalar
     sum_p d2_p / num_points[cloud(p)] / N + sum_t d2_t / num_faces[mesh(t)] / N
@@ -397,25 +427,153 @@ def point_mesh_face_distance(meshes, pcls, min_triangle_area=0.0):
     call reads nothing back from the device."""
     fn = "point_mesh_face_distance"
     tris, t_first = _packed_mesh(meshes, fn)
-    pts, p_len = convert_pointclouds_to_tensor(pcls)
-    if pts.dim() != 3 or pts.shape[-1] != 3:
-        raise ValueError("%s: pcls must be (N, P, 3), got %s" % (fn, tuple(pts.shape)))
-    N, P = pts.shape[0], pts.shape[1]
-    p_len = torch.as_tensor(p_len)
-    host = host_lengths(p_len)               # before any view of it: the host copy rides on this very tensor
-    p_len = p_len.reshape(-1)
-    if len(host) != N or any(l < 0 or l > P for l in host):
-        raise ValueError("%s: the clouds' lengths must hold one count in [0, %d] per cloud" % (fn, P))
-    if t_first.shape[0] != N:
-        raise ValueError("%s: meshes and pcls must have the same batch size" % fn)
-    if all(l == P for l in host):
-        packed = pts.reshape(N * P, 3)
-    else:
-        packed = torch.cat([pts[n, :host[n]] for n in range(N)])
-    p_first = _first_of(p_len.to(device=pts.device, dtype=torch.int64), host)
+    packed, p_first = _packed_clouds(pcls, t_first.shape[0], False, fn)
+    N = t_first.shape[0]
     pts32, tr32, seg = _pf_inputs(packed, p_first, tris, t_first, None, min_triangle_area, fn)
     _, sums_p, _ = _FaceDistance.apply(pts32, tr32, 0, float(min_triangle_area), seg)
     _, sums_t, _ = _FaceDistance.apply(pts32, tr32, 1, float(min_triangle_area), seg)
     point_dist = (sums_p / seg.p_len.clamp(min=1).float()).sum() / float(max(N, 1))
     face_dist = (sums_t / seg.t_len.clamp(min=1).float()).sum() / float(max(N, 1))
     return point_dist + face_dist
+
+
+# --------------------------------------------------------------------------------------- the sign of the distance to a mesh
+_INDEX_LIMIT = 2 ** 31 - 1
+
+
+def _eps_sqrt(squared, eps=1e-17):
+    """DSS/utils/mathHelper.py:20-25: clamp(|x|, eps); the caller takes the root."""
+    return squared.abs().clamp_min(eps)
+
+
+def _packed_mesh_indexed(meshes, fn):
+    """_packed_mesh with the indices kept: (verts (V,3), faces (F,3) int64 rows of verts, tris (F,3,3), first_idx (N,)).
+    The tuple form's local indices get n * V added; face rows outside [0, V) are the caller's duty (checking them would
+    read the device)."""
+    tris, first = _packed_mesh(meshes, fn)
+    if not isinstance(meshes, (tuple, list)):
+        return meshes.verts_packed(), meshes.faces_packed().to(torch.int64), tris, first
+    verts, faces = meshes[0], meshes[1]
+    N, V, F = verts.shape[0], verts.shape[1], faces.shape[1]
+    packed = faces.to(torch.int64) + (torch.arange(N, device=faces.device, dtype=torch.int64) * V)[:, None, None]
+    if len(meshes) == 2 or meshes[2] is None:
+        packed = packed.reshape(N * F, 3)
+    else:
+        host = host_lengths(torch.as_tensor(meshes[2]))
+        packed = torch.cat([packed[n, :host[n]] for n in range(N)]) if N else packed.reshape(0, 3)
+    return verts.reshape(N * V, 3), packed, tris, first
+
+
+def _pseudonormals(verts, faces):
+    """The three vector sets of packed float32 verts (V,3) and int64 faces (F,3) on the GPU."""
+    V, F, dev = verts.shape[0], faces.shape[0], verts.device
+    face_n = torch.empty((F, 3), dtype=torch.float32, device=dev)
+    edge_n = torch.empty((F, 3, 3), dtype=torch.float32, device=dev)
+    vert_n = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    ws_bytes = _lib.load().iso_pfsign_normals_workspace_bytes(V, F)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    p = _lib.ptr
+    _lib.call("iso_pfsign_normals", p(verts), p(faces), V, F, p(face_n), p(edge_n), p(vert_n), p(ws), ws_bytes, _lib.stream())
+    return face_n, edge_n, vert_n
+
+
+def _sign_mesh(meshes, fn):
+    """Validated (verts f32 (V,3), faces int64 (F,3), tris (F,3,3), first_idx) of a mesh argument; the tensors still where
+    the caller has them."""
+    verts, faces, tris, first = _packed_mesh_indexed(meshes, fn)
+    # the library's own inequalities (iso_pfsign_normals, iso_pfsign_sign): what passes here is not refused there
+    if faces.shape[0] >= _INDEX_LIMIT // 3 or verts.shape[0] >= _INDEX_LIMIT:
+        raise ValueError("%s: %d vertices and %d faces; the limits are V < 2^31 - 1 and F < (2^31 - 1) / 3"
+                         % (fn, verts.shape[0], faces.shape[0]))
+    return verts, faces, tris, first
+
+
+def mesh_pseudonormals(meshes):
+    """The angle-weighted pseudonormals of a batch of meshes (Baerentzen & Aanaes), in packed order:
+    (face_normals (F,3), edge_normals (F,3,3), vert_normals (V,3)), float32, no gradient.
+
+    face_normals are the unit normals (v1 - v0) x (v2 - v0) / |.|; edge_normals[f, k] belongs to the edge from vertex k
+    to vertex k + 1 mod 3 of face f and is the sum of the unit normals of all faces that hold both of its end vertices (one
+    face on a boundary, every face of a non-manifold edge); vert_normals[v] is the sum over the corners at v of corner
+    angle * face normal.  A face without area has a zero normal and contributes nothing.  Edge and vertex vectors are not
+    normalised.  `meshes` as in point_mesh_face_distance; face indices outside the vertices are the caller's duty.  The
+    sums run in a fixed order: the same bits from run to run.  A ground-truth mesh does not change between steps: compute
+    this once and hand it to point_mesh_sign / point_mesh_signed_distance as `normals`."""
+    fn = "mesh_pseudonormals"
+    verts, faces, _, _ = _sign_mesh(meshes, fn)
+    _on_gpu(verts, faces)
+    return _pseudonormals(verts.detach().float().contiguous(), faces.contiguous())
+
+
+def _sign_normals(normals, verts, faces, fn):
+    """The `normals` argument checked against the mesh: three float tensors (F,3), (F,3,3), (V,3)."""
+    if not isinstance(normals, (tuple, list)) or len(normals) != 3 or not all(torch.is_tensor(t) for t in normals):
+        raise ValueError("%s: normals must be the three tensors mesh_pseudonormals returns" % fn)
+    V, F = verts.shape[0], faces.shape[0]
+    for t, shape in zip(normals, ((F, 3), (F, 3, 3), (V, 3))):
+        if tuple(t.shape) != shape or not t.is_floating_point():
+            raise ValueError("%s: normals must be float tensors (F,3), (F,3,3), (V,3) of this mesh, got %s for %s"
+                             % (fn, tuple(t.shape), shape))
+    return normals
+
+
+def _sign_inputs(meshes, pcls, min_triangle_area, normals, fn):
+    """Everything the two signed calls share, validated before any GPU work."""
+    verts, faces, tris, t_first = _sign_mesh(meshes, fn)
+    packed, p_first = _packed_clouds(pcls, t_first.shape[0], True, fn)
+    if packed.shape[0] >= _INDEX_LIMIT:
+        raise ValueError("%s: %d points; the limit is P < 2^31 - 1" % (fn, packed.shape[0]))
+    if normals is not None:
+        normals = _sign_normals(normals, verts, faces, fn)
+    pts32, tr32, seg = _pf_inputs(packed, p_first, tris, t_first, None, min_triangle_area, fn)
+    _on_gpu(verts, faces, *(normals or ()))
+    return pts32, tr32, seg, verts.detach().float().contiguous(), faces.contiguous(), normals
+
+
+def _sign_of(points, idx, tris, verts, faces, normals, min_area):
+    """sign (P,) f32 and feature (P,) int32 of points whose nearest faces idx (P,) int32 the search has found."""
+    if normals is None:
+        normals = _pseudonormals(verts, faces)
+    face_n, edge_n, vert_n = (t.detach().float().contiguous() for t in normals)
+    P, dev = points.shape[0], points.device
+    sign = torch.empty((P,), dtype=torch.float32, device=dev)
+    feature = torch.empty((P,), dtype=torch.int32, device=dev)
+    p = _lib.ptr
+    _lib.call("iso_pfsign_sign", p(points), p(idx), p(tris), p(faces), p(face_n), p(edge_n), p(vert_n), float(min_area),
+              p(sign), p(feature), P, faces.shape[0], verts.shape[0], _lib.stream())
+    return sign, feature
+
+
+def point_mesh_sign(meshes, pcls, min_triangle_area=0.0, normals=None, return_parts=False):
+    """The sign of the distance from every point to its mesh: (P_total,) float32 in {-1, +1}, packed order, no gradient;
+    -1 inside and +1 outside a mesh whose faces are wound outward (reversing the winding reverses the sign).
+
+    The sign is that of (p - c) . N with c the closest point of the mesh (the nearest face of point_face_distance, the
+    same min_triangle_area) and N the pseudonormal of the feature c lies on: the face, one of its edges or one of its
+    vertices (mesh_pseudonormals; pass its result as `normals` to reuse it).  It needs no closed mesh: an open one is
+    signed by the side of its nearest feature.  A point on the mesh, a point whose feature has a zero pseudonormal and a
+    point whose mesh has no faces get +1.  With return_parts also (idx (P_total,) int64 into the packed faces, -1 = none,
+    feature (P_total,) int32: 0 = face, 1..3 = edge slot + 1, 4..6 = corner + 4, -1 = none).
+
+    `meshes` as in point_mesh_face_distance (face indices outside the vertices are the caller's duty); `pcls` likewise,
+    and a (P,3) tensor is one cloud when there is one mesh.  With lengths that carry a host copy (or none) the call reads
+    nothing back from the device."""
+    fn = "point_mesh_sign"
+    pts32, tr32, seg, verts, faces, normals = _sign_inputs(meshes, pcls, min_triangle_area, normals, fn)
+    pts32, tr32 = pts32.detach(), tr32.detach()
+    _, idx, _ = _pf_search(0, pts32, tr32, seg, float(min_triangle_area))
+    sign, feature = _sign_of(pts32, idx, tr32, verts, faces, normals, min_triangle_area)
+    return (sign, idx.long(), feature) if return_parts else sign
+
+
+def point_mesh_signed_distance(meshes, pcls, min_triangle_area=0.0, normals=None):
+    """The signed distance from every point to its mesh: (P_total,) float32, packed order:
+    point_mesh_sign * sqrt(eps_sqrt(point_face_distance)), which is what the reference's SignedDistanceLoss compares an
+    SDF with (DSS/training/losses.py:596), with an exact sign in place of its raster parity.  Differentiable w.r.t. the
+    points and the vertices through the distance (point_face_distance's backward pass), the sign and the nearest faces
+    held constant.  Arguments as point_mesh_sign."""
+    fn = "point_mesh_signed_distance"
+    pts32, tr32, seg, verts, faces, normals = _sign_inputs(meshes, pcls, min_triangle_area, normals, fn)
+    d2, _, idx = _FaceDistance.apply(pts32, tr32, 0, float(min_triangle_area), seg)
+    sign, _ = _sign_of(pts32.detach(), idx, tr32.detach(), verts, faces, normals, min_triangle_area)
+    return sign * torch.sqrt(_eps_sqrt(d2))
