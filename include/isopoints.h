@@ -363,6 +363,20 @@ int iso_frnn_query(const float* points1, const int64_t* lengths1,
                    int64_t g_stride, void* workspace, int64_t workspace_bytes,
                    void* stream);
 
+/* The K nearest OTHER points of every point of cloud 2: iso_frnn_query with points1 == NULL (cloud 2 against itself,
+ * rows written at their original index) and one difference: the candidate whose original index equals the query's own
+ * row is passed over.  1 <= K <= 32, the same (d2, index) order, the same -1 / -1.0 padding, the same workspace
+ * (iso_frnn_query_workspace_bytes(n_clouds, p2_stride, p2_stride)).  This is the "self plus K" search of the reference's
+ * losses and filters (DSS/training/losses.py:169-180 asks pytorch3d for K = 33 and drops column 0) without the slot the
+ * query's own point would take: on a cloud without duplicate points the result equals columns 1..K of a (K+1)-query.
+ * With duplicates a (K+1)-query's column 0 may be the duplicate and not the point itself; here only the own row is left
+ * out, so a duplicate is a neighbour at distance 0.                                                              */
+int iso_frnn_query_others(const float* points2, const float* sorted2, const int32_t* sorted_idx2,
+                          const int64_t* lengths2, const int32_t* off, const float* grid_params,
+                          const float* radius, int K, float* dists_out, int64_t* idxs_out, float* nn_out,
+                          int n_clouds, int64_t p2_stride, int64_t g_stride, void* workspace,
+                          int64_t workspace_bytes, void* stream);
+
 /* frnn.frnn_gather: out[n,i,k,:] = x[n, idx[n,i,k], :], zeros where idx < 0.
  * x (N,P2,U) f32, idx (N,P1,K) i64, out (N,P1,K,U).                           */
 int iso_frnn_gather(const float* x, const int64_t* idx, float* out,
@@ -1113,6 +1127,60 @@ int iso_pfsign_sign(const float* points, const int32_t* idx, const float* tris, 
                     int64_t n_verts, void* stream);
 int iso_pfsign_pair(const float* point, const float* tri, float min_triangle_area, float* d2_out, float* weights_out,
                     int32_t* feature_out);
+
+/* ----------------------------------------------------------------------
+ * K. The point-cloud regularisers of the splatting renderer (csrc/surface_loss.hip)
+ *    replaces the bodies of SurfaceLoss / ProjectionLoss / RepulsionLoss (DSS/training/losses.py:149-515; Eq. 10-15 of the
+ *    DSS paper): two normal mollifications and the two losses over the K nearest OTHER points of every point, which the
+ *    reference composes from about twenty torch ops on (N,P,K) and (N,P,K,3) temporaries.
+ *
+ *    Notation.  Cloud b has L_b valid points; p_i is row i; j = idx[i,k] and d_k = dists[i,k] (squared, ascending,
+ *    k = 0..K-1; section B's iso_frnn_query_others), d_0 the nearest other point; fs = filter_scale; inv_sigma2 =
+ *    1 / sharpness_sigma^2 (the caller's division); sd(x) = sign(x) max(|x|, 1e-17) with sd(0) = 1e-17
+ *    (DSS/utils/mathHelper.py:14-18); u(v) = v / max(|v|, 1e-12).  All f32 without FMA contraction, expf the accurate one.
+ *      phi_ik = max(0, 1 - d_k / (((2 d_0) fs) fs))^4                         (:262-276)
+ *      nu_ik  = exp(-|u(m_j) - u(m_i)|^2 inv_sigma2)  for a normal field m     (:225-248)
+ *    Lanes.  One lane per neighbour slot, 32 lanes per row, two rows per wave: a row's indices are one 256-B read, its
+ *    distances one 128-B read, the neighbours' vectors 12-B gathers.  Every sum over k is the same xor butterfly over the
+ *    32 lanes (slots >= K, and slots whose index is outside [0), add zeros): a fixed order, no atomics, two
+ *    runs give the same bits.  idx / dists rows start at idx + row * idx_row_stride and dists + row * dists_row_stride
+ *    (row = n * p_stride + i), so columns 1.. of a wider query result need no copy.
+ *    K outside [1,32] -> ISO_ERR_UNSUPPORTED; null pointers, negative sizes, row strides < K -> ISO_ERR_INVALID.
+ *    Every cloud needs L_b >= K + 1 (every slot filled); the callers check that on the host.  Clouds with duplicate
+ *    points are undefined: d_0 = 0 makes phi 0/0, as in the reference.
+ *
+ * iso_surfloss_mollify: out_i = sum_k phi_ik [nu_ik] in_j / sd(sum_k phi_ik [nu_ik]); nu (from the field `in` itself) is
+ *   included when use_normal_w != 0.  The reference's two calls: n0 -> n1 without nu (:332), n1 -> n2 with nu (:337-342).
+ *   Neither sum is masked by the ball test, as in the reference.  Rows i >= L_b are written as zeros.  in != out.
+ *
+ * iso_surfloss_forward: x_j = nbr_points[n, j] ((N, 3): the points the neighbour lists were built on), or
+ *   knn[n, i, k] when knn != NULL ((N, p_stride, K, 3) contiguous).  With nu from n1:
+ *      ball_ik = d_k > (fs d_0) 2                                             (:349-351)
+ *      w_ik    = phi_ik nu_ik where not ball_ik, else 0
+ *      s_ik    = <x_j - p_i, n2_j>
+ *   projection (:367-403):  D_i = sum w s / sd(sum w);  proj_i = D_i^2;  dproj_i/dp_i = 2 D_i (-sum_k w_ik n2_j / sd(sum w))
+ *   repulsion (:462-515):   q_i = p_i + sum_k (s_ik w_ik) n2_j / sd(sum w)
+ *                           sig_ik = exp(-|x_j - q_i|^2 L_b / 2);  dens_i = 1 + sum_k sig_ik     (all K slots, unmasked)
+ *                           W_ik = nu_ik sig_ik dens_i where not ball_ik, else 0
+ *                           rep_i = -sum_k |q_i - x_j|^2 W_ik / sd(sum W)
+ *                           g_i = -sum_k 2 (q_i - x_j) W_ik / sd(sum W);  drep_i/dp_i = g_i - sum_k w_ik n2_j <n2_j, g_i> / sd(sum w)
+ *   The bandwidth L_b / 2 is PER CLOUD: the reference's expression broadcasts an (N,) tensor against (N,P,K) and so only runs
+ *   for one cloud; per cloud is what it means.  Weights, normals and neighbour positions carry no gradient in the reference
+ *   (no_grad / detach), so a row's gradient touches its own point only: the two (N,P,3) gradient arrays ARE the backward
+ *   pass, up to a row-wise scale.  outputs: bit 0 (ISO_SURFLOSS_PROJECTION) proj_out (N,P) and, with bit 2, grad_proj_out
+ *   (N,P,3); bit 1 (ISO_SURFLOSS_REPULSION) rep_out and grad_rep_out likewise; bit 2 (ISO_SURFLOSS_GRADIENTS).  A value
+ *   is the same bits whichever other outputs are asked for.  Rows i >= L_b are written as zeros.                        */
+#define ISO_SURFLOSS_PROJECTION 1
+#define ISO_SURFLOSS_REPULSION 2
+#define ISO_SURFLOSS_GRADIENTS 4
+int iso_surfloss_mollify(const float* normals_in, const int64_t* idx, int64_t idx_row_stride, const float* dists,
+                         int64_t dists_row_stride, const int64_t* lengths, int n_clouds, int64_t p_stride, int K, float filter_scale, float inv_sigma2, int use_normal_w,
+                         float* normals_out, void* stream);
+int iso_surfloss_forward(const float* points, const float* nbr_points, const float* knn, const float* n1, const float* n2,
+                         const int64_t* idx, int64_t idx_row_stride, const float* dists, int64_t dists_row_stride,
+                         const int64_t* lengths, int n_clouds, int64_t p_stride, int K,
+                         float filter_scale, float inv_sigma2, int outputs, float* proj_out, float* rep_out,
+                         float* grad_proj_out, float* grad_rep_out, void* stream);
 
 #ifdef __cplusplus
 }

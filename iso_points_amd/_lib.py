@@ -69,6 +69,7 @@ SIGNATURES = {
     "iso_frnn_counting_sort": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _I, _P]),
     "iso_frnn_query_workspace_bytes": (_L, [_I, _L, _L]),
     "iso_frnn_query": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _L, _L, _L, _P, _L, _P]),
+    "iso_frnn_query_others": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _L, _L, _P, _L, _P]),
     "iso_frnn_gather": (_I, [_P, _P, _P, _I, _L, _L, _I, _I, _P]),
     "iso_repulse": (_I, [_P, _P, _P, _L, _P, _L, _L, _I, _P, _P]),
     "iso_upsample_candidates": (_I, [_P, _P, _L, _I, _P, _P, _P]),
@@ -165,6 +166,8 @@ SIGNATURES = {
     "iso_pfsign_normals": (_I, [_P, _P, _L, _L, _P, _P, _P, _P, _L, _P]),
     "iso_pfsign_sign": (_I, [_P, _P, _P, _P, _P, _P, _P, _F, _P, _P, _L, _L, _L, _P]),
     "iso_pfsign_pair": (_I, [_P, _P, _F, _P, _P, _P]),
+    "iso_surfloss_mollify": (_I, [_P, _P, _L, _P, _L, _P, _I, _L, _I, _F, _F, _I, _P, _P]),
+    "iso_surfloss_forward": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _I, _L, _I, _F, _F, _I, _P, _P, _P, _P, _P]),
 }
 
 class Follow(ctypes.Structure):

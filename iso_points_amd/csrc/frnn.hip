@@ -327,7 +327,9 @@ struct TopK {
   }
 };
 
-template <int KMAX>
+// OTHERS (iso_frnn_query_others, always a self query): the candidate whose original index is the query's own row is
+// passed over, so the list holds the K nearest OTHER points; OTHERS = false is the plain query, the same code as before.
+template <int KMAX, bool OTHERS = false>
 __global__ __launch_bounds__(256) void k_query(
     const float* __restrict__ points1, const int64_t* __restrict__ lengths1,
     const float* __restrict__ points2, const float* __restrict__ sorted2,
@@ -362,6 +364,7 @@ __global__ __launch_bounds__(256) void k_query(
       qx = q[0]; qy = q[1]; qz = q[2];
       row = t;
     }
+    const int own = OTHERS ? (int)row : -1;
     TopK<KMAX> best;
     best.init();
     float wd = FLT_MAX;      // current K-th best (d2, idx)
@@ -380,7 +383,7 @@ __global__ __launch_bounds__(256) void k_query(
       unfinished = rho_stop < rho_max;
       auto scan = [&](int64_t i0, int64_t i1) {
         scan_run2(s4, i0, i1, qx, qy, qz, [&](float d2, int oi) {
-          if (d2 < r2 && d2 <= wd && pair_lt(d2, oi, wd, wi)) {
+          if ((!OTHERS || oi != own) && d2 < r2 && d2 <= wd && pair_lt(d2, oi, wd, wi)) {
             best.push(d2, oi, K);
             wd = best.worst(K);
             wi = best.worst_id(K);
@@ -472,7 +475,7 @@ __device__ __forceinline__ void wave_merge(const TopK<KMAX>& best, int K, float&
   }
 }
 
-template <int KMAX>
+template <int KMAX, bool OTHERS = false>
 __global__ __launch_bounds__(64) void k_query_tail(
     const float* __restrict__ points1, const int64_t* __restrict__ lengths1,
     const float* __restrict__ points2, const float* __restrict__ sorted2,
@@ -509,6 +512,7 @@ __global__ __launch_bounds__(64) void k_query_tail(
     const QueryCell c = query_cell(g, qx, qy, qz);
     const float rho_f = ceilf(r * g.delta * 1.0011f);
     const int rho_max = (rho_f < (float)c.span) ? (int)rho_f : c.span;
+    const int own = OTHERS ? (int)row : -1;
     TopK<KMAX> best;
     best.init();
     float wd = FLT_MAX;
@@ -519,7 +523,7 @@ __global__ __launch_bounds__(64) void k_query_tail(
         for (int64_t i = i0; i < i1; ++i) {
           const float4 ca = s4[i];
           const float d2 = rec_d2(qx, qy, qz, ca);
-          if (d2 < r2) {
+          if ((!OTHERS || __float_as_int(ca.w) != own) && d2 < r2) {
             if (found < KMAX) ++found;
             if (d2 <= wd) {
               int oi = __float_as_int(ca.w);
@@ -804,5 +808,43 @@ extern "C" int iso_frnn_query(const float* points1, const int64_t* lengths1,
   else { ISO_LAUNCH_Q(32); }
 #undef ISO_LAUNCH_Q
   ISO_CHECK_LAUNCH("iso_frnn_query");
+  return ISO_OK;
+}
+
+// The K nearest OTHER points of every point of cloud 2: iso_frnn_query's self query with the query's own row left out of
+// its list.  One list size: the 32-slot list serves every K (the callers ask for the reference's 32 others).
+extern "C" int iso_frnn_query_others(const float* points2, const float* sorted2, const int32_t* sorted_idx2,
+                                     const int64_t* lengths2, const int32_t* off, const float* grid_params,
+                                     const float* radius, int K, float* dists_out, int64_t* idxs_out, float* nn_out,
+                                     int n_clouds, int64_t p2_stride, int64_t g_stride, void* workspace,
+                                     int64_t workspace_bytes, void* stream) {
+  ISO_REQUIRE(K >= 1 && K <= 32, ISO_ERR_UNSUPPORTED, "iso_frnn_query_others: K must be in [1,32], got %d", K);
+  ISO_REQUIRE(n_clouds >= 0 && p2_stride >= 0, ISO_ERR_INVALID, "iso_frnn_query_others: bad sizes");
+  if (n_clouds == 0 || p2_stride == 0) return ISO_OK;
+  ISO_REQUIRE(sorted2 && sorted_idx2 && off && grid_params && radius && dists_out && idxs_out,
+              ISO_ERR_INVALID, "iso_frnn_query_others: null pointer");
+  ISO_REQUIRE(!nn_out || points2, ISO_ERR_INVALID, "iso_frnn_query_others: nn_out needs points2");
+  ISO_REQUIRE(workspace && workspace_bytes >= iso_frnn_query_workspace_bytes(n_clouds, p2_stride, p2_stride),
+              ISO_ERR_WORKSPACE, "iso_frnn_query_others: workspace too small");
+  ISO_REQUIRE(((uintptr_t)workspace & 15) == 0, ISO_ERR_INVALID, "iso_frnn_query_others: workspace must be 16-B aligned");
+  hipStream_t s = (hipStream_t)stream;
+  int32_t* tail_count = (int32_t*)workspace;
+  int32_t* tail_list = tail_count + 64 * ((n_clouds + 63) / 64);
+  float4* xyzi = reinterpret_cast<float4*>((char*)workspace + query_ws_tail_bytes(n_clouds, p2_stride));
+  hipLaunchKernelGGL(k_zero_i32, dim3(iso_div_up(n_clouds, 64)), dim3(64), 0, s, tail_count, n_clouds);
+  pack_xyzi(sorted2, sorted_idx2, lengths2, n_clouds, p2_stride, xyzi, s);
+  int gx = iso_div_up(p2_stride, 256);
+  if (gx > 65535) gx = 65535;
+  int tail_blocks = (int)(p2_stride < 2048 ? p2_stride : 2048);
+  if (tail_blocks < 1) tail_blocks = 1;
+  const float* no_points1 = nullptr;
+  const int64_t* no_lengths1 = nullptr;
+  hipLaunchKernelGGL((k_query<32, true>), dim3(gx, n_clouds), dim3(256), 0, s, no_points1, no_lengths1, points2, sorted2,
+                     sorted_idx2, lengths2, off, grid_params, radius, K, dists_out, idxs_out, nn_out, p2_stride, p2_stride,
+                     g_stride, tail_list, tail_count, xyzi);
+  hipLaunchKernelGGL((k_query_tail<32, true>), dim3(tail_blocks, n_clouds), dim3(64), 0, s, no_points1, no_lengths1,
+                     points2, sorted2, sorted_idx2, lengths2, off, grid_params, radius, K, dists_out, idxs_out, nn_out,
+                     p2_stride, p2_stride, g_stride, tail_list, tail_count, xyzi);
+  ISO_CHECK_LAUNCH("iso_frnn_query_others");
   return ISO_OK;
 }

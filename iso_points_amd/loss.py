@@ -6,15 +6,22 @@ pytorch3d.loss.point_mesh_distance.point_face_distance (DSS/training/losses.py:5
 that loss gives the distance: point_mesh_sign / point_mesh_signed_distance / mesh_pseudonormals, an exact inside test by
 angle-weighted pseudonormals in place of the reference's raster parity (include/isopoints.h section J).
 
+The point-cloud regularisers of the splatting renderer, ProjectionLoss and RepulsionLoss (DSS/training/losses.py:149-515),
+are surface_losses and the two modules on it: one search for the 32 nearest other points, two fused normal mollifications
+and one fused sweep that returns both losses with their gradients (include/isopoints.h section K).
+
 The nearest-point search runs on the cell grid of iso_points_amd.frnn (exact, any distance), fused with the
 normal term and the per-cloud sums; the backward pass is a gather over counting-sorted index lists.  Neither
 uses float atomics: values and gradients are the same bits from run to run (include/isopoints.h section G).
 """
+import ctypes
+from collections import namedtuple
+
 import torch
 
 from . import _lib
 from . import frnn
-from .levelset_sampling import convert_pointclouds_to_tensor, host_lengths, with_host_lengths
+from .levelset_sampling import convert_pointclouds_to_tensor, host_lengths, padded_to_packed, with_host_lengths
 
 _INF = float("inf")
 
@@ -577,3 +584,262 @@ def point_mesh_signed_distance(meshes, pcls, min_triangle_area=0.0, normals=None
     d2, _, idx = _FaceDistance.apply(pts32, tr32, 0, float(min_triangle_area), seg)
     sign, _ = _sign_of(pts32.detach(), idx, tr32.detach(), verts, faces, normals, min_triangle_area)
     return sign * torch.sqrt(_eps_sqrt(d2))
+
+
+# ------------------------------------------------------------------- the point regularisers: ProjectionLoss, RepulsionLoss
+SurfaceLosses = namedtuple("SurfaceLosses", "projection repulsion normals knn")
+
+_PROJECTION, _REPULSION, _GRADIENTS = 1, 2, 4         # ISO_SURFLOSS_*
+
+
+class SurfaceKNN(namedtuple("KNN", "dists idx knn")):
+    """KNN(dists, idx, knn) of the nearest other points, as pytorch3d names the fields, plus `points`: the detached
+    (N,P,3) float32 positions the lists were built on, which stand in for `knn` (N,P,K,3) where that is None."""
+
+    def __new__(cls, dists, idx, knn=None, points=None):
+        self = super(SurfaceKNN, cls).__new__(cls, dists, idx, knn)
+        self.points = points
+        return self
+
+
+def _rows(t, K):
+    """A (N,P,>=K) tensor as the kernels read it: (tensor, row stride).  A [..., 1:] view of a wider result is taken as it
+    is; anything else is copied."""
+    N, P, st = t.shape[0], t.shape[1], t.stride()
+    if t.numel() > 0 and st[2] == 1 and st[1] >= K and (N == 1 or st[0] == P * st[1]):
+        return t, st[1]
+    t = t.contiguous()
+    return t, t.shape[2]
+
+
+def _rowptr(t):
+    """_lib.ptr for a tensor _rows has passed: its rows may be a strided view."""
+    if not t.is_cuda:
+        raise RuntimeError("iso_points_amd: tensor must live on the GPU (got %s); there is no CPU path" % t.device)
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def _mollify(normals, tree, lengths, filter_scale, inv_sigma2, use_normal_w):
+    N, P, _ = normals.shape
+    K = tree.idx.shape[2]
+    out = torch.empty_like(normals)
+    idx, idx_stride = _rows(tree.idx, K)
+    dists, d_stride = _rows(tree.dists, K)
+    p = _lib.ptr
+    _lib.call("iso_surfloss_mollify", p(normals), _rowptr(idx), idx_stride, _rowptr(dists), d_stride, p(lengths),
+              N, P, K, float(filter_scale), float(inv_sigma2), int(bool(use_normal_w)), p(out), _lib.stream())
+    return out
+
+
+class _SurfaceSweep(torch.autograd.Function):
+    """points -> (projection (N,P) or None, repulsion (N,P) or None).  Everything but `points` is a constant, as in the
+    reference (no_grad / detach), so a row's gradient touches its own point only: the forward sweep writes the two
+    per-row gradient vectors and the backward pass is a row-wise scale of them."""
+
+    @staticmethod
+    def forward(ctx, points, tree, n1, n2, lengths, filter_scale, inv_sigma2, which):
+        N, P, _ = points.shape
+        K = tree.idx.shape[2]
+        dev = points.device
+        grad = ctx.needs_input_grad[0]
+
+        def out(flag, *shape):
+            return torch.empty(shape, dtype=torch.float32, device=dev) if which & flag else None
+        proj, rep = out(_PROJECTION, N, P), out(_REPULSION, N, P)
+        g_proj = out(_PROJECTION, N, P, 3) if grad else None
+        g_rep = out(_REPULSION, N, P, 3) if grad else None
+        idx, idx_stride = _rows(tree.idx, K)
+        dists, d_stride = _rows(tree.dists, K)
+        knn = tree.knn.detach().float().contiguous() if tree.knn is not None else None
+        p = _lib.ptr
+        _lib.call("iso_surfloss_forward", p(points), p(tree.points) if knn is None else None, p(knn), p(n1), p(n2),
+                  _rowptr(idx), idx_stride, _rowptr(dists), d_stride, p(lengths), N, P, K, float(filter_scale),
+                  float(inv_sigma2), which | (_GRADIENTS if grad else 0), p(proj), p(rep), p(g_proj), p(g_rep),
+                  _lib.stream())
+        ctx.grads = (g_proj, g_rep)
+        ctx.set_materialize_grads(False)
+        return proj, rep
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, up_proj, up_rep):
+        total = None
+        for up, g in zip((up_proj, up_rep), ctx.grads):
+            if up is None or g is None:
+                continue
+            term = up.detach().float().unsqueeze(-1) * g
+            total = term if total is None else total + term
+        return total, None, None, None, None, None, None, None
+
+
+def _surface_tree(knn, pts, K_asked):
+    """A caller's tree checked against the points: SurfaceKNN with float32 dists, int64 idx."""
+    if not all(hasattr(knn, a) for a in ("idx", "dists")):
+        raise ValueError("surface_losses: knn must carry idx and dists (a KNN of knn_others or pytorch3d's)")
+    idx, dists = knn.idx, knn.dists
+    nbrs, built_on = getattr(knn, "knn", None), getattr(knn, "points", None)
+    if idx.dim() != 3 or tuple(idx.shape[:2]) != tuple(pts.shape[:2]) or tuple(dists.shape) != tuple(idx.shape):
+        raise ValueError("surface_losses: knn.idx and knn.dists must be (N, P, K) for points (N, P, 3), got %s and %s for %s"
+                         % (tuple(idx.shape), tuple(dists.shape), tuple(pts.shape)))
+    if idx.shape[2] < 1 or idx.shape[2] > 32:
+        raise ValueError("surface_losses: knn holds %d neighbours per point; the limits are [1, 32]" % idx.shape[2])
+    if nbrs is None and built_on is None:
+        raise ValueError("surface_losses: knn must carry the neighbours' positions `knn` (N, P, K, 3) or the `points` it "
+                         "was built on")
+    if nbrs is not None and tuple(nbrs.shape) != tuple(idx.shape) + (3,):
+        raise ValueError("surface_losses: knn.knn must be (N, P, K, 3)")
+    if nbrs is None and tuple(built_on.shape) != tuple(pts.shape):
+        raise ValueError("surface_losses: knn.points must have the shape of points")
+    return idx, dists, nbrs, built_on
+
+
+def surface_losses(points, normals=None, lengths=None, *, knn_k=33, filter_scale=2.0, sharpness_sigma=0.75,
+                   projection=True, repulsion=True, knn=None):
+    """The two point regularisers of the splatting renderer from one neighbour search and one pair of normal
+    mollifications: SurfaceLosses(projection, repulsion, normals, knn).
+
+    projection  (sum L_b,) packed: the squared distance of every point to the plane fitted through its neighbours
+                (ProjectionLoss.compute, DSS/training/losses.py:300-403); None when not asked for
+    repulsion   (sum L_b,) packed: minus the weighted mean squared distance from the point, moved onto that plane, to its
+                neighbours (RepulsionLoss.compute, :425-515); None when not asked for
+    normals     (N,P,3) the twice mollified normals n2 (:332, :337-342), rows beyond a cloud's length zero
+    knn         the SurfaceKNN used: the one given, or the knn_k - 1 nearest other points of every point with the detached
+                points they were found on
+
+    Both losses are differentiable w.r.t. `points`; weights, normals and neighbour positions are constants, as in the
+    reference.  `points` / `normals` are padded (N,P,3) tensors with `lengths`, or `points` is an object with
+    points_padded() / normals_padded() / num_points_per_cloud().  knn_k in [2, 33] counts the point itself, as the
+    reference's does; every cloud needs at least knn_k points.  A `knn` that is given is used with ITS distances and
+    neighbour positions (its `knn` (N,P,K,3), else the `points` it carries): a tree of an earlier step stays the tree of
+    that step, as the reference's cached knn_tree does.  The Gaussian bandwidth of the repulsion is L_b / 2 per cloud.
+    float32 throughout; the same bits from run to run, and a loss is the same bits whether or not the other is computed.
+    Clouds with duplicate points are undefined (0 / 0 in the spacing, as in the reference)."""
+    fn = "surface_losses"
+    if normals is None and hasattr(points, "normals_padded"):
+        normals = points.normals_padded()
+    pts, conv_len = convert_pointclouds_to_tensor(points)
+    if pts.dim() != 3 or pts.shape[-1] != 3:
+        raise ValueError("%s: points must be (N, P, 3), got %s" % (fn, tuple(pts.shape)))
+    if normals is None or not torch.is_tensor(normals) or tuple(normals.shape) != tuple(pts.shape):
+        raise ValueError("%s: normals must have the shape of points, %s" % (fn, tuple(pts.shape)))
+    if int(knn_k) != knn_k or not 2 <= knn_k <= 33:
+        raise ValueError("%s: knn_k must be in [2, 33] (the point itself and up to 32 others), got %r" % (fn, knn_k))
+    if not float(filter_scale) > 0.0 or not float(sharpness_sigma) > 0.0:
+        raise ValueError("%s: filter_scale and sharpness_sigma must be positive" % fn)
+    if not (projection or repulsion):
+        raise ValueError("%s: ask for the projection, the repulsion or both" % fn)
+    if lengths is None:
+        lengths = conv_len
+    lengths = torch.as_tensor(lengths)
+    host = host_lengths(lengths)              # before any reshape: the host copy rides on this very tensor
+    if len(host) != pts.shape[0]:
+        raise ValueError("%s: lengths must have one entry per cloud" % fn)
+    if any(l > pts.shape[1] or l < 0 for l in host):
+        raise ValueError("%s: lengths must lie in [0, %d]" % (fn, pts.shape[1]))
+    K = int(knn_k) - 1
+    given = _surface_tree(knn, pts, K) if knn is not None else None
+    if given is not None:
+        K = given[0].shape[2]
+    if any(l < K + 1 for l in host):
+        raise ValueError("%s: every cloud needs at least knn_k = %d points (lengths %s): below that the neighbour lists "
+                         "have unfilled slots" % (fn, K + 1, host))
+    _on_gpu(pts, normals, *([t for t in given if t is not None] if given is not None else []))
+    dev = pts.device
+    lens = lengths.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+    pts32 = pts.float().contiguous()
+    if given is None:
+        from .point_processing import knn_others
+        found = knn_others(pts32.detach(), lens, K=K)
+        tree = SurfaceKNN(found.dists, found.idx, None, pts32.detach())
+    else:
+        idx, dists, nbrs, built_on = given
+        tree = SurfaceKNN(dists.detach().float(), idx.to(torch.int64), nbrs,
+                          built_on.detach().float().contiguous() if built_on is not None else None)
+    inv_sigma2 = 1.0 / (float(sharpness_sigma) * float(sharpness_sigma))
+    n0 = normals.detach().float().contiguous()
+    n1 = _mollify(n0, tree, lens, filter_scale, inv_sigma2, False)
+    n2 = _mollify(n1, tree, lens, filter_scale, inv_sigma2, True)
+    which = (_PROJECTION if projection else 0) | (_REPULSION if repulsion else 0)
+    proj, rep = _SurfaceSweep.apply(pts32, tree, n1, n2, lens, float(filter_scale), inv_sigma2, which)
+    return SurfaceLosses(padded_to_packed(proj, host) if proj is not None else None,
+                         padded_to_packed(rep, host) if rep is not None else None, n2, tree)
+
+
+class _SurfaceLoss(torch.nn.Module):
+    """What ProjectionLoss and RepulsionLoss share: the cached neighbour tree, the keyword overrides and the reduction
+    (SurfaceLoss / BaseLoss, DSS/training/losses.py:25-62, :149-276)."""
+    _which = None
+    _rebuild_default = False
+
+    def __init__(self, reduction="mean", knn_k=33, filter_scale=2.0, sharpness_sigma=0.75):
+        super(_SurfaceLoss, self).__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("Invalid reduction method (%s)" % (reduction,))
+        self.reduction = reduction
+        self.knn_k = knn_k
+        self.filter_scale = filter_scale
+        self.sharpness_sigma = sharpness_sigma
+        self.knn_tree = None
+
+    def forward(self, point_clouds, points_filters=None, rebuild_knn=None, reduction=None, filter_scale=None,
+                sharpness_sigma=None, knn_tree=None):
+        """The loss of `point_clouds` (an object with points_padded / normals_padded / num_points_per_cloud, or a
+        (points, normals[, lengths]) tuple of padded tensors), reduced.  filter_scale,
+        sharpness_sigma and knn_tree replace the module's own from this call on, as the reference's compute() keeps them;
+        `reduction` holds for this call.  A cached tree is reused while its idx.shape[:2] matches the points, with the
+        distances and neighbour positions of the moment it was built (:312, :325, :368); rebuild_knn searches again.  A
+        cloud object with update_normals_ gets the packed mollified normals, as :222 does; tensors are never modified."""
+        if points_filters is not None:
+            raise NotImplementedError("points_filters: the reference's visibility filter reads an unbound name "
+                                      "(DSS/training/losses.py:214) and cannot run; it is not part of this package")
+        reduction = reduction or self.reduction
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("Invalid reduction method (%s)" % (reduction,))
+        if filter_scale is not None:
+            self.filter_scale = filter_scale
+        if sharpness_sigma is not None:
+            self.sharpness_sigma = sharpness_sigma
+        if knn_tree is not None:
+            self.knn_tree = knn_tree
+        if rebuild_knn is None:
+            rebuild_knn = self._rebuild_default
+        if isinstance(point_clouds, (tuple, list)):
+            if len(point_clouds) not in (2, 3):
+                raise ValueError("point_clouds: a (points, normals[, lengths]) tuple or a point-cloud object")
+            points, normals = point_clouds[0], point_clouds[1]
+            lengths = point_clouds[2] if len(point_clouds) == 3 else None
+        else:
+            points, normals, lengths = point_clouds, None, None
+        shape = tuple(convert_pointclouds_to_tensor(points)[0].shape[:2])
+        tree = self.knn_tree
+        if rebuild_knn or tree is None or tuple(tree.idx.shape[:2]) != shape:
+            tree = None
+        res = surface_losses(points, normals, lengths, knn_k=self.knn_k, filter_scale=self.filter_scale,
+                             sharpness_sigma=self.sharpness_sigma, projection=self._which == "projection",
+                             repulsion=self._which == "repulsion", knn=tree)
+        self.knn_tree = res.knn
+        if hasattr(point_clouds, "update_normals_"):
+            host = host_lengths(torch.as_tensor(point_clouds.num_points_per_cloud()))
+            point_clouds.update_normals_(padded_to_packed(res.normals, host))
+        loss = res.projection if self._which == "projection" else res.repulsion
+        if reduction == "sum":
+            return loss.sum()
+        if reduction == "mean":
+            return loss.mean()
+        return loss
+
+
+class ProjectionLoss(_SurfaceLoss):
+    """DSS/training/losses.py:282-403: the squared distance of every point to the plane fitted through its neighbours by
+    non-linear kernel regression (Oztireli et al.), per point (sum L_b,) before the reduction.  rebuild_knn defaults to
+    False: the tree of the first call is kept while the cloud's shape holds."""
+    _which = "projection"
+    _rebuild_default = False
+
+
+class RepulsionLoss(_SurfaceLoss):
+    """DSS/training/losses.py:406-515: minus the density-weighted mean squared distance from every point, projected onto its
+    local plane, to its neighbours.  rebuild_knn defaults to True.  A cached tree follows ProjectionLoss's rule (the
+    reference reads knn_tree.shape at :438, which does not exist)."""
+    _which = "repulsion"
+    _rebuild_default = True

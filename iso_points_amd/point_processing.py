@@ -5,6 +5,7 @@
   wlop                point_processing.py:35-122    FPS subsample + 3 LOP iterations
   farthest_sampling   point_processing.py:473-499   (torch_cluster.fps)
   knn_points          pytorch3d.ops.knn_points as upsample uses it (:315,:358)
+  knn_others          the K nearest other points: knn_points(K + 1)[..., 1:] without the slot of the point itself
   denoise_normals     point_processing.py:241-278   bilateral normal filter on the FRNN neighbourhood
   remove_outliers     point_processing.py:16-31     drop points whose neighbourhood is not flat (math_helper)
 
@@ -43,6 +44,40 @@ def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, return_nn=False, retur
     idxs = torch.where(pad, torch.zeros_like(idxs), idxs)
     if nn is not None:
         nn = nn  # frnn already zero-fills the padded rows
+    return _KNN(dists=dists, idx=idxs, knn=nn)
+
+
+def knn_others(points, lengths=None, K=32, return_nn=False):
+    """The K nearest OTHER points of every point of its own cloud: KNN(dists (N,P,K) squared / ascending, idx (N,P,K) int64,
+    knn (N,P,K,3) or None), the query's own row left out (iso_frnn_query_others).  On a cloud without duplicate points this
+    is knn_points(points, points, K=K + 1)[..., 1:], the "self plus K" search of the reference's losses
+    (DSS/training/losses.py:169-180), so K = 32 serves its default knn_k = 33 with the 32-slot list.  Infinite radius, the
+    grid knn_points builds; slots that cannot be filled (a cloud of fewer than K + 1 points) and rows beyond `lengths` hold
+    idx 0 / dist 0, like pytorch3d.  With duplicate points a duplicate is a neighbour at distance 0."""
+    if points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError("knn_others: points must be (N, P, 3), got %s" % (tuple(points.shape),))
+    if K < 1 or K > 32:
+        raise ValueError("K must be in [1, 32], got %d" % K)
+    if not points.is_cuda:
+        raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
+    N, P, _ = points.shape
+    dev = points.device
+    pts = points.detach().float().contiguous()
+    r = torch.full((N,), float("inf"), dtype=torch.float32, device=dev)
+    lens = frnn._as_lengths(lengths, N, P, dev)
+    dists = torch.zeros((N, P, K), dtype=torch.float32, device=dev)
+    idxs = torch.zeros((N, P, K), dtype=torch.int64, device=dev)
+    nn = torch.zeros((N, P, K, 3), dtype=torch.float32, device=dev) if return_nn else None
+    if N > 0 and P > 0:
+        grid = frnn.build_grid(pts, lens, r, points_per_cell=max(8.0, 0.75 * (K + 1)))    # as knn_points(K + 1)
+        p = _lib.ptr
+        ws_bytes = _lib.load().iso_frnn_query_workspace_bytes(N, P, P)
+        ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+        _lib.call("iso_frnn_query_others", p(pts), p(grid.sorted_points), p(grid.sorted_idx), p(lens), p(grid.off),
+                  p(grid.params), p(r), K, p(dists), p(idxs), p(nn), N, P, grid.g_stride, p(ws), ws_bytes, _lib.stream())
+        pad = idxs < 0
+        dists.masked_fill_(pad, 0.0)
+        idxs.masked_fill_(pad, 0)
     return _KNN(dists=dists, idx=idxs, knn=nn)
 
 
