@@ -1182,6 +1182,55 @@ int iso_surfloss_forward(const float* points, const float* nbr_points, const flo
                          float filter_scale, float inv_sigma2, int outputs, float* proj_out, float* rep_out,
                          float* grad_proj_out, float* grad_rep_out, void* stream);
 
+/* ----------------------------------------------------------------------
+ * L. Even sampling: Poisson-disk elimination (csrc/disk.hip)
+ *    serves the places where the reference turns a mesh into the cloud it uses and asks for an EVEN sampling:
+ *      config.py:227                    trimesh.sample.sample_surface_even: the initial iso-points of the combined model
+ *      DSS/training/trainer.py:255      sample_surface_even of the generated mesh, graded by chamfer_distance (validation)
+ *      DSS/utils/dataset.py:123         pcu.sample_mesh_poisson_disk: the ground-truth cloud
+ *    trimesh and point_cloud_utils are third-party and not part of the reference tree; bit parity with either is not
+ *    claimed.  The definition here is exact, maximal and stable under a longer draw (trimesh's one-shot degree rule is
+ *    neither maximal nor prefix-stable; pcu measures along the surface).
+ *
+ *    Definition.  Cloud n has L_n samples p_0 .. p_{L_n - 1} and a radius r_n.  Two samples CONFLICT iff d2(i, j) <= r2 with
+ *    d2 = (dx*dx + dy*dy) + dz*dz in f32 without FMA contraction (section B's expression) and r2 = r_n * r_n in f32.  Sample s
+ *    is KEPT iff no kept sample j < s conflicts with it; a sample marked invalid on entry is removed and blocks nobody:
+ *    serial dart throwing in index order.  So the kept set is an exact integer result; no two kept samples conflict; every
+ *    removed valid sample has a kept conflicting sample of lower index; and the kept set of the first k samples is the same
+ *    whether or not more samples follow.  Coordinates must be finite.
+ *
+ *    Parallel form.  One state byte per sample (UNDECIDED, KEEP, REMOVED).  A round visits every UNDECIDED s and reads the
+ *    state of every conflicting j < s: any KEEP -> REMOVED; else any UNDECIDED -> unchanged; else KEEP.  States move only
+ *    from UNDECIDED to a final value and are finalised only from final states below them, so rounds update in place, a
+ *    stale read only delays a decision, and the fixed point is the serial result whatever the launch shape or the timing
+ *    (csrc/disk.hip's header has the argument).  Every round finalises at least the lowest UNDECIDED sample of each cloud.
+ *
+ *    The grid is section B's, built on the cloud itself at this radius (make_grid_density, insert_points, scan_cells,
+ *    counting_sort): sorted_points (N,P,3), sorted_idx (N,P), off (N,g_stride), grid_params (N,8).  The device entries
+ *    enqueue on `stream` and do not synchronise.  Limit: N * P < 2^31 - 1, refused beyond.  All three calls of one
+ *    elimination share one workspace of iso_disk_workspace_bytes(N, P) bytes, 16-B aligned, untouched in between.
+ *
+ * iso_disk_begin: packs the grid's records and sets the state bytes: row i of cloud n is UNDECIDED if i < lengths[n]
+ *   (lengths NULL: P) and valid[n,i] != 0 (valid (N,P) u8, NULL: all valid), else REMOVED; zeroes the round counters.
+ * iso_disk_rounds: enqueues rounds first_round .. first_round + n_rounds - 1 (the caller counts the rounds of one
+ *   elimination from 0 over its calls; n_rounds >= 1) and then writes *left (one i32 on the device) = the number of samples
+ *   still UNDECIDED after the last of them.  A round whose predecessor left none returns at once.  radius (N) f32.
+ * iso_disk_select: the stable compaction.  sel_out (N,s_out) i32 = the indices of the first s_out kept samples of each
+ *   cloud in ascending order, -1 beyond; kept_out (N) i64 = min(number kept, s_out); mask_out (N,P) u8 = 1 where kept
+ *   (may be NULL).  A scan: integer work only, nothing order-dependent.  Valid once *left is 0.
+ * iso_disk_area_radius: radius_out[n] = (float) sqrt(A_n / (3 n_samples)), A_n the sum in f64 (fixed order) of the f32
+ *   areas (section I) of mesh n's packed faces; 0 for a mesh whose A_n is not a positive finite number.                */
+int64_t iso_disk_workspace_bytes(int n_clouds, int64_t p_stride);
+int iso_disk_begin(const float* sorted_points, const int32_t* sorted_idx, const int64_t* lengths, const uint8_t* valid,
+                   int n_clouds, int64_t p_stride, void* workspace, int64_t workspace_bytes, void* stream);
+int iso_disk_rounds(const int64_t* lengths, const int32_t* off, const float* grid_params, const float* radius,
+                    int n_clouds, int64_t p_stride, int64_t g_stride, int first_round, int n_rounds, int32_t* left,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int iso_disk_select(int n_clouds, int64_t p_stride, int64_t s_out, uint8_t* mask_out, int32_t* sel_out, int64_t* kept_out,
+                    void* workspace, int64_t workspace_bytes, void* stream);
+int iso_disk_area_radius(const float* areas, const int64_t* tris_first, const int64_t* tris_len, int n_meshes,
+                         int64_t n_tris, int64_t n_samples, float* radius_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,11 @@ SIGNATURES = {
     "iso_pfsign_pair": (_I, [_P, _P, _F, _P, _P, _P]),
     "iso_surfloss_mollify": (_I, [_P, _P, _L, _P, _L, _P, _I, _L, _I, _F, _F, _I, _P, _P]),
     "iso_surfloss_forward": (_I, [_P, _P, _P, _P, _P, _P, _L, _P, _L, _P, _I, _L, _I, _F, _F, _I, _P, _P, _P, _P, _P]),
+    "iso_disk_workspace_bytes": (_L, [_I, _L]),
+    "iso_disk_begin": (_I, [_P, _P, _P, _P, _I, _L, _P, _L, _P]),
+    "iso_disk_rounds": (_I, [_P, _P, _P, _P, _I, _L, _L, _I, _I, _P, _P, _L, _P]),
+    "iso_disk_select": (_I, [_I, _L, _L, _P, _P, _P, _P, _L, _P]),
+    "iso_disk_area_radius": (_I, [_P, _P, _P, _I, _L, _L, _P, _P]),
 }
 
 class Follow(ctypes.Structure):

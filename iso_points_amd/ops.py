@@ -6,7 +6,13 @@ One host-side seed per call, everything else counter-based inside the kernel (Ph
 sample does not depend on num_samples, on the other meshes or on a launch shape.  The backward pass is the gather over
 counting-sorted lists of the loss module: no float atomics, values and gradients are the same bits from run to run
 (include/isopoints.h section I).
+
+sample_points_from_meshes_even is the even sampling the reference takes from trimesh.sample.sample_surface_even
+(config.py:227, DSS/training/trainer.py:255) and pcu.sample_mesh_poisson_disk (DSS/utils/dataset.py:123): the same draw, three
+times as long, followed by the Poisson-disk elimination of include/isopoints.h section L.
 """
+import math
+
 import torch
 
 from . import _lib
@@ -107,6 +113,93 @@ def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, r
     if return_faces:
         out = out + (face.long(), bary)
     return out if len(out) > 1 else out[0]
+
+
+def sample_points_from_meshes_even(meshes, num_samples=10000, radius=None, return_normals=False, *, generator=None,
+                                   return_faces=False, oversample=3):
+    """An even sampling of every mesh of the batch: up to `num_samples` points no two of which are within `radius` of each
+    other, where the reference calls trimesh.sample.sample_surface_even (config.py:227, DSS/training/trainer.py:255) or
+    pcu.sample_mesh_poisson_disk (DSS/utils/dataset.py:123).  Not bit for bit theirs: the rule is exact and its own.
+
+    The call draws oversample * num_samples samples per mesh exactly as sample_points_from_meshes(meshes, oversample *
+    num_samples, generator=generator) would (one seed taken from the generator, the same bits), marks the samples without a
+    face invalid and eliminates in draw order (point_processing.remove_close: a sample is kept iff no kept earlier sample is
+    within the radius, d2 <= r * r in float32).  radius: a positive finite float, an (N,) tensor, or None for
+    sqrt(area / (3 num_samples)) per mesh from the float64 sum of the float32 face areas, computed on the device.
+
+    Returns (points (N,S,3), num_points (N,) int64[, normals (N,S,3)][, face_idx (N,S) int64, bary (N,S,3)]): the first
+    num_points[n] rows are the first kept draws of mesh n in draw order; rows beyond are zero (face_idx -1).  A mesh may
+    yield fewer than S points, a mesh without faces or without area yields none.  As both steps are prefix-stable the
+    result is a function of (seed, mesh, radius): its first rows do not depend on how many samples were drawn beyond those
+    that decided them, so a larger `oversample` changes nothing in the rows a smaller one filled.
+
+    Differentiable w.r.t. the vertices: the outputs are a torch.gather of the sampler's outputs by constant indices, each
+    draw taken at most once (the padding rows add exact zeros), so values and gradients are the same bits from run to run.
+    Host reads: the 4 bytes per batch of elimination rounds that remove_close reads, normally once.  Limit, refused
+    beyond: N * oversample * num_samples < 2^31."""
+    from .point_processing import _eliminate
+    fn = "sample_points_from_meshes_even"
+    S, over = int(num_samples), int(oversample)
+    if S < 0:
+        raise ValueError("%s: num_samples must not be negative" % fn)
+    if over < 1:
+        raise ValueError("%s: oversample must be at least 1" % fn)
+    tris, first = _packed_mesh(meshes, fn)
+    if not torch.is_tensor(first) or first.dim() != 1 or first.is_floating_point():
+        raise ValueError("%s: mesh_to_faces_packed_first_idx must be an integer tensor of shape (N,)" % fn)
+    N, T, D = first.shape[0], tris.shape[0], over * S
+    if torch.is_tensor(radius):
+        if radius.dim() != 1 or radius.shape[0] != N:
+            raise ValueError("%s: a radius tensor must be of shape (N,)" % fn)
+    elif radius is not None:
+        radius = float(radius)
+        if not (radius > 0.0 and math.isfinite(radius)):
+            raise ValueError("%s: radius must be positive and finite, got %r" % (fn, radius))
+    if T >= _ROW_LIMIT:
+        raise ValueError("%s: %d packed faces; the limit is 2^31 - 1" % (fn, T))
+    if N * D >= _ROW_LIMIT:
+        raise ValueError("%s: %d meshes x %d x %d draws; the limit is 2^31 - 1 draws in all" % (fn, N, over, S))
+    _on_gpu(tris, radius if torch.is_tensor(radius) else None)
+    dev = tris.device
+    seed = int(torch.empty((), dtype=torch.int64).random_(generator=generator))
+    if N == 0 or S == 0:
+        points = tris.new_zeros((N, S, 3), dtype=torch.float32)
+        out = (points, torch.zeros((N,), dtype=torch.int64, device=dev))
+        if return_normals:
+            out = out + (torch.zeros_like(points),)
+        if return_faces:
+            out = out + (torch.full((N, S), -1, dtype=torch.int64, device=dev), torch.zeros_like(points))
+        return out
+    first = first.to(device=dev, dtype=torch.int64).contiguous()
+    end = torch.full((1,), T, dtype=torch.int64, device=dev)
+    length = (torch.cat([first[1:], end]) - first).contiguous()
+    tris32 = tris.float().contiguous()
+    points, normals, face, bary = _MeshSample.apply(tris32, first, length, D, seed, bool(return_normals), True)
+    p = _lib.ptr
+    if radius is None:
+        areas = torch.empty((T,), dtype=torch.float32, device=dev)
+        rad = torch.empty((N,), dtype=torch.float32, device=dev)
+        _lib.call("iso_mesh_face_areas", p(tris32.detach()), T, p(areas), None, _lib.stream())
+        _lib.call("iso_disk_area_radius", p(areas), p(first), p(length), N, T, S, p(rad), _lib.stream())
+    elif torch.is_tensor(radius):
+        rad = radius.detach().to(device=dev, dtype=torch.float32).contiguous()
+    else:
+        rad = torch.full((N,), radius, dtype=torch.float32, device=dev)
+    lens = torch.full((N,), D, dtype=torch.int64, device=dev)
+    _, sel, kept, _ = _eliminate(points.detach().contiguous(), lens, rad, (face >= 0).to(torch.uint8).contiguous(), S)
+    live = sel >= 0
+    idx = sel.clamp(min=0).long()
+
+    def take(x, pad):
+        if x.dim() == 2:
+            return torch.where(live, torch.gather(x, 1, idx), x.new_full((), pad))
+        return torch.where(live[..., None], torch.gather(x, 1, idx[..., None].expand(N, S, x.shape[-1])), x.new_full((), pad))
+    out = (take(points, 0.0), kept)
+    if return_normals:
+        out = out + (take(normals, 0.0),)
+    if return_faces:
+        out = out + (take(face, -1).long(), take(bary, 0.0))
+    return out
 
 
 def mesh_face_areas_normals(verts, faces):

@@ -8,6 +8,8 @@
   knn_others          the K nearest other points: knn_points(K + 1)[..., 1:] without the slot of the point itself
   denoise_normals     point_processing.py:241-278   bilateral normal filter on the FRNN neighbourhood
   remove_outliers     point_processing.py:16-31     drop points whose neighbourhood is not flat (math_helper)
+  remove_close        Poisson-disk elimination: the step behind trimesh's sample_surface_even (config.py:227,
+                      DSS/training/trainer.py:255) and pcu.sample_mesh_poisson_disk (DSS/utils/dataset.py:123)
 
 Inputs are padded tensors (N,P,3) + lengths (pytorch3d's Pointclouds container is out of scope;
 objects exposing points_padded()/num_points_per_cloud() are accepted).  Neighbour search, the
@@ -292,4 +294,102 @@ def remove_outliers(pointclouds, neighborhood_size=16, tolerance=0.05):
     for b in range(N):
         out[b, : kept[b]] = points[b][mask[b]]
     return out, with_host_lengths(torch.tensor(kept, dtype=torch.int64, device=points.device), kept)
+
+
+# rounds of the elimination enqueued between two reads of the number of samples left open: twice the most rounds seen on
+# surface samplings at the default radius (5-8 for 900 to 90 000 samples).  A speed knob only: the result does not depend
+# on it.
+ROUNDS_PER_BATCH = 16
+
+_INDEX_LIMIT = 2 ** 31 - 1
+
+
+class _NotOnGpu(RuntimeError, ValueError):
+    """remove_close's refusal of CPU tensors: the RuntimeError the rest of the package raises, and a ValueError as every
+    other bad argument of that function."""
+
+
+def _eliminate(points, lengths, radius, valid, s_out):
+    """The elimination of include/isopoints.h section L on float32 contiguous GPU points (N,P,3), int64 lengths (N,), float32
+    radius (N,) and a uint8 mask (N,P) or None: (mask (N,P) uint8, sel (N,s_out) int32, kept (N,) int64, rounds enqueued).
+    One read of 4 bytes per ROUNDS_PER_BATCH rounds."""
+    N, P, dev = points.shape[0], points.shape[1], points.device
+    mask = torch.zeros((N, P), dtype=torch.uint8, device=dev)
+    sel = torch.full((N, s_out), -1, dtype=torch.int32, device=dev)
+    kept = torch.zeros((N,), dtype=torch.int64, device=dev)
+    if N == 0 or P == 0:
+        return mask, sel, kept, 0
+    grid = frnn.build_grid(points, lengths, radius)
+    ws_bytes = _lib.load().iso_disk_workspace_bytes(N, P)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    left = torch.empty((1,), dtype=torch.int32, device=dev)
+    p, s = _lib.ptr, _lib.stream()
+    _lib.call("iso_disk_begin", p(grid.sorted_points), p(grid.sorted_idx), p(lengths), p(valid), N, P, p(ws), ws_bytes, s)
+    batch, done = max(1, int(ROUNDS_PER_BATCH)), 0
+    while True:
+        _lib.call("iso_disk_rounds", p(lengths), p(grid.off), p(grid.params), p(radius), N, P, grid.g_stride, done, batch,
+                  p(left), p(ws), ws_bytes, s)
+        done += batch
+        if int(left.item()) == 0:
+            break
+    _lib.call("iso_disk_select", N, P, s_out, p(mask), p(sel), p(kept), p(ws), ws_bytes, s)
+    return mask, sel, kept, done
+
+
+def remove_close(points, radius, lengths=None, valid=None):
+    """Poisson-disk elimination: drop points of each cloud until no two that are left are within `radius` of each other, the
+    step behind trimesh.sample.sample_surface_even (config.py:227, DSS/training/trainer.py:255) and
+    pcu.sample_mesh_poisson_disk (DSS/utils/dataset.py:123) -- by an exact rule of its own, not bit for bit theirs.
+
+    Two points conflict iff d2 <= r2, d2 = (dx*dx + dy*dy) + dz*dz and r2 = r * r in float32.  Point s is kept iff no kept
+    point of lower index conflicts with it (serial dart throwing in index order); points beyond `lengths` or with
+    valid == 0 are removed and block nobody.  So the kept set of the first k points does not depend on the points after
+    them, and the result does not depend on a launch shape, on timing or on ROUNDS_PER_BATCH.
+
+    points (N,P,3) or an object with points_padded() (and num_points_per_cloud(), taken for `lengths` when none are given);
+    radius a positive finite float or an (N,) tensor; lengths (N,) integer in [0, P]; valid (N,P), nonzero = take part.
+    Returns (mask (N,P) bool, sel (N,P) int64: the kept indices of each cloud in ascending order, -1 beyond, kept (N,)
+    int64).  No gradient: the result is integer.
+
+    Host reads: the rounds run in batches of ROUNDS_PER_BATCH launches and the number of points still undecided (4 bytes)
+    is read after each batch; surface samplings finish inside the first batch, so a call normally reads 4 bytes back once
+    (a chain of n points, each removing the next, needs n rounds).  `lengths` on the device without a host copy cost one
+    more read for the range check."""
+    fn = "remove_close"
+    if not torch.is_tensor(points):
+        if not hasattr(points, "points_padded"):
+            raise ValueError("%s: points must be a (N, P, 3) tensor or an object with points_padded()" % fn)
+        if lengths is None and hasattr(points, "num_points_per_cloud"):
+            lengths = points.num_points_per_cloud()
+        points = points.points_padded()
+    if not torch.is_tensor(points) or points.dim() != 3 or points.shape[-1] != 3:
+        raise ValueError("%s: points must be (N, P, 3)" % fn)
+    N, P = points.shape[0], points.shape[1]
+    if torch.is_tensor(radius):
+        if radius.dim() != 1 or radius.shape[0] != N:
+            raise ValueError("%s: a radius tensor must be of shape (N,)" % fn)
+    else:
+        try:
+            radius = float(radius)
+        except (TypeError, ValueError):
+            raise ValueError("%s: radius must be a float or an (N,) tensor" % fn)
+        if not (radius > 0.0 and math.isfinite(radius)):
+            raise ValueError("%s: radius must be positive and finite, got %r" % (fn, radius))
+    if lengths is not None:
+        if not torch.is_tensor(lengths) or lengths.dim() != 1 or lengths.shape[0] != N or lengths.is_floating_point():
+            raise ValueError("%s: lengths must be an integer tensor of shape (N,)" % fn)
+        if any(l < 0 or l > P for l in host_lengths(lengths)):
+            raise ValueError("%s: lengths must lie in [0, %d]" % (fn, P))
+    if valid is not None and (not torch.is_tensor(valid) or tuple(valid.shape) != (N, P)):
+        raise ValueError("%s: valid must be of shape (N, P)" % fn)
+    if N * P >= _INDEX_LIMIT:
+        raise ValueError("%s: %d clouds x %d points; the limit is 2^31 - 2 points in all" % (fn, N, P))
+    for t in (points, valid, radius if torch.is_tensor(radius) else None):
+        if t is not None and not t.is_cuda:
+            raise _NotOnGpu("iso_points_amd: %s: tensors must be on the GPU; there is no CPU path" % fn)
+    dev = points.device
+    mask, sel, kept, _ = _eliminate(points.detach().float().contiguous(), frnn._as_lengths(lengths, N, P, dev),
+                                    frnn._as_radius(radius, N, dev),
+                                    None if valid is None else (valid != 0).to(torch.uint8).contiguous(), P)
+    return mask.bool(), sel.long(), kept
 
