@@ -434,14 +434,27 @@ int iso_ear_candidates(const float* points, const float* normals, const float* k
  * (DSS/utils/point_processing.py:473-499): per cloud n, out_idx[n, 0..n_samples[n]) =
  * start[n], then repeatedly the point farthest from the chosen set (squared f32 distances,
  * ties -> lowest index).  work: iso_farthest_point_sampling_work_floats(N, p_stride) f32 of
- * scratch.  out_idx rows are left untouched beyond n_samples[n].  Clouds of >= 8 k points
- * (p_stride) run grid-wide (cooperative launch, points held in registers), smaller ones in one
- * workgroup per cloud; the sample sequence is the same.                              */
+ * scratch.  out_idx rows are left untouched beyond n_samples[n] (n_samples[n] > length clamps
+ * to the length, start[n] clamps into [0, length), an empty cloud's row is untouched).  Device
+ * code keeps f32 denormals (the build sets no flush-to-zero flag), so the sequence is the IEEE
+ * one at every scale.  Clouds of 4 096 .. 4 194 304 points (p_stride) run grid-wide (cooperative
+ * launch, points held in registers: up to 2 097 152 points several samples per exchange, above
+ * one), smaller ones in one workgroup per cloud with the points in registers, larger ones in
+ * one workgroup walking memory; a device that refuses the cooperative launch runs one workgroup
+ * per cloud, in registers up to 8 192 points; the sample sequence is the same.
+ * iso_farthest_point_sampling_form reports the kernel a call with this p_stride takes: 0 the
+ * memory-walking kernel, 100 + PPT registers of one workgroup, 200 + PPT grid-wide with several
+ * samples per exchange, 300 + PPT grid-wide with one (PPT = points per thread), -1 for a stride
+ * outside [1, 2^31).  check_device == 0 needs no GPU; != 0 also asks the current device whether
+ * the cooperative grid can be co-resident and reports the one-workgroup form if not.
+ * Test switches, read on every call: ISO_FPS_ONE_WORKGROUP (the memory-walking kernel for every
+ * size) and ISO_FPS_NO_COOPERATIVE (behave as if the cooperative launch had been refused).  */
 int64_t iso_farthest_point_sampling_work_floats(int n_clouds, int64_t p_stride);
 int iso_farthest_point_sampling(const float* points, const int64_t* lengths,
                                 const int64_t* n_samples, const int64_t* start, int n_clouds,
                                 int64_t p_stride, int64_t out_stride, float* work,
                                 int64_t* out_idx, void* stream);
+int iso_farthest_point_sampling_form(int64_t p_stride, int check_device);
 
 /* Local frames of a K-nearest neighbourhood = estimate_pointcloud_local_coord_frames
  * (DSS/utils/mathHelper.py:43-119): per valid row (b, i < lengths[b]) with neighbours

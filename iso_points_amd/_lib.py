@@ -75,6 +75,7 @@ SIGNATURES = {
     "iso_upsample_candidates": (_I, [_P, _P, _L, _I, _P, _P, _P]),
     "iso_farthest_point_sampling_work_floats": (_L, [_I, _L]),
     "iso_farthest_point_sampling": (_I, [_P, _P, _P, _P, _I, _L, _L, _P, _P, _P]),
+    "iso_farthest_point_sampling_form": (_I, [_L, _I]),
     "iso_pca_frames_work_bytes": (_L, [_I]),
     "iso_pca_frames": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _P]),
     "iso_splat_view_flags": (_I, [_P, _P, _P, _P, _L, _I, _F, _F, _I, _P]),

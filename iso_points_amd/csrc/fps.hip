@@ -4,20 +4,24 @@
 // index).  Four kernels, same arithmetic, same result:
 //   * k_fps: one 1024-lane workgroup per cloud, min-distances in a caller workspace; an iteration costs
 //     ~16 B x len through ONE CU (3 us per sample at 5 000 points).  Kept as the plain statement of the
-//     algorithm the others are tested against (ISO_FPS_ONE_WORKGROUP=1) and for clouds beyond 4 M points.
-//   * k_fps_reg (clouds below 4 k points): one workgroup, points and
-//     min-distances in registers, two barriers and no memory access per sample: 1.3 us per sample at
-//     5 000 points.
-//   * k_fps_grid (clouds above 2 M points, up to 4 M): a cooperative launch of 256 workgroups; every
+//     algorithm the others are tested against (ISO_FPS_ONE_WORKGROUP=1), for clouds beyond 4 194 304 points,
+//     and beyond 8 192 points on a device that refuses the cooperative launch.
+//   * k_fps_reg (clouds below 4 096 points; up to 8 192 when the cooperative launch is refused): one
+//     workgroup, points and min-distances in registers, two barriers and no memory access per sample:
+//     1.3 us per sample at 5 000 points.
+//   * k_fps_grid (2 097 153 .. 4 194 304 points): a cooperative launch of 256 workgroups; every
 //     thread keeps its <= 16 points AND their min-distances in registers (nothing is read from
 //     memory inside the loop except the winner's coordinates); the workgroup maxima -- 64-bit keys
 //     (distance bits, ~index) -- meet through one store per workgroup and one polling load per lane of
 //     wave 0 (no atomics, no counter barrier: see the comment at the kernel).  One device-wide exchange
 //     (~2.2 us) per sample: 3.5-3.7 us per sample at 500 k points.
-//   * k_fps_lazy (4 k .. 2 M points): the same layout, but a workgroup publishes its FOUR
+//   * k_fps_lazy (4 096 .. 2 097 152 points): the same layout, but a workgroup publishes its FOUR
 //     largest keys and every workgroup replays the selection on the published lists for as long as its
 //     outcome is certain -- 35 samples per exchange on average at 500 k points: 0.8 us per sample
 //     (5 000 of 500 k: 18.3 -> 4.5 ms), the sequence identical sample for sample.
+// Which one a stride takes is stated once, in fps_form() below; iso_farthest_point_sampling_form() reports it.
+// Test switches, read on every call: ISO_FPS_ONE_WORKGROUP (k_fps for every size) and ISO_FPS_NO_COOPERATIVE (the
+// forms of a device that refused the first cooperative launch: k_fps_reg up to 8 192 points, k_fps above).
 #include <float.h>
 #include <stdlib.h>
 #include "iso_common.h"
@@ -212,7 +216,7 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
   return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
 }
 
-// ---- one workgroup, points in registers (clouds below 4 k points: the reference's own sizes; up to 8 k when the device
+// ---- one workgroup, points in registers (clouds below 4 096 points: the reference's own sizes; up to 8 192 when the device
 // refuses the cooperative launch of the grid-wide forms) -------------------------------------------------------------
 // k_fps walks the cloud in memory every sample (3 us per sample at 5 000 points: five dependent L2 round trips per thread,
 // a serial final reduction).  Here a thread keeps its <= 8 points and their min-distances in registers, the workgroup's
@@ -465,32 +469,101 @@ __global__ __launch_bounds__(FPS_BLOCK) void k_fps_lazy(const float* __restrict_
   }
 }
 
-template <int PPT>
-hipError_t launch_fps_lazy(int nb, const float* p, const int64_t* lengths, const int64_t* n_samples,
-                           const int64_t* start, int n, int64_t p_stride, FpsCtlLazy* ctl, int64_t* out, hipStream_t s) {
-  void* args[] = {(void*)&p, (void*)&lengths, (void*)&n_samples, (void*)&start, (void*)&n, (void*)&p_stride,
-                  (void*)&ctl, (void*)&out};
-  return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&k_fps_lazy<PPT>), dim3(nb), dim3(FPS_BLOCK), args,
-                                    0, s);
-}
-
-template <int PPT>
-hipError_t launch_fps_grid(int nb, const float* p, const int64_t* lengths, const int64_t* n_samples,
-                           const int64_t* start, int n, int64_t p_stride, FpsCtl* ctl, int64_t* out, hipStream_t s) {
-  void* args[] = {(void*)&p, (void*)&lengths, (void*)&n_samples, (void*)&start, (void*)&n, (void*)&p_stride,
-                  (void*)&ctl, (void*)&out};
-  return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(&k_fps_grid<PPT>), dim3(nb), dim3(FPS_BLOCK), args,
-                                    0, s);
-}
-
 constexpr int64_t kFpsGridMin = 4096;     // below: one workgroup (k_fps_reg) is faster (2 500 points: 1.1 against 1.4 us per sample; 5 000: 1.3 against 1.2)
+constexpr int64_t kFpsLazyMax = (int64_t)kFpsLazyGrid * FPS_BLOCK * 16;   // 2 097 152: above, the lists of k_fps_lazy do not fit
+constexpr int64_t kFpsGridMax = (int64_t)kFpsMaxGrid * FPS_BLOCK * 16;    // 4 194 304: above, k_fps
+constexpr int64_t kFpsRegMax = (int64_t)FPS_BLOCK * 8;                    // 8 192: one workgroup's registers
 constexpr int kFpsCtlFloats = (sizeof(FpsCtlLazy) > sizeof(FpsCtl) ? sizeof(FpsCtlLazy) : sizeof(FpsCtl)) / 4;   // control block at the end of the workspace
+
+// ---- the dispatch: THE statement of which kernel a stride takes (iso_farthest_point_sampling launches through it,
+// iso_farthest_point_sampling_form reports it) ----------------------------------------------------------------------
+// form = family + points per thread: 0 k_fps, 100 + PPT k_fps_reg<PPT>, 200 + PPT k_fps_lazy<PPT>, 300 + PPT k_fps_grid<PPT>
+constexpr int kFormWalk = 0, kFormReg = 100, kFormLazy = 200, kFormGrid = 300;
+struct FpsForm { int code; int nb; };     // nb: workgroups of the cooperative grid (0 for the one-workgroup forms)
+
+int fps_round_ppt(int64_t ppt, int most) {
+  int r = 1;
+  while (r < ppt && r < most) r *= 2;
+  return r;
+}
+
+// cooperative = false: the device refused the grid (or ISO_FPS_NO_COOPERATIVE): registers up to 8 k points, k_fps above
+FpsForm fps_form(int64_t p_stride, bool one_workgroup, bool cooperative) {
+  if (one_workgroup) return {kFormWalk, 0};
+  if (cooperative && p_stride >= kFpsGridMin && p_stride <= kFpsGridMax) {
+    // grid-wide form, cloud after cloud: k_fps_lazy with one point per thread, i.e. as many workgroups as the cloud fills,
+    // up to 128 -- the exchange is shared by many samples, more lists make longer runs (24 k points: 13.9 ms at 4 points
+    // per thread, 10.1 at 1); above 128 x 1024 x 16 points k_fps_grid on 256 workgroups.  (k_fps_grid measured 2.8 us per
+    // sample up to 50 k points, 5.0 at 500 k, 7.1 at 1 M -- the barrier's atomic round trips, not the arithmetic; fewer,
+    // fatter workgroups are not faster.)
+    const bool use_lazy = p_stride <= kFpsLazyMax;
+    const int64_t nb_max = use_lazy ? kFpsLazyGrid : kFpsMaxGrid;
+    int64_t nb = (p_stride + FPS_BLOCK - 1) / FPS_BLOCK;
+    nb = nb < 2 ? 2 : (nb > nb_max ? nb_max : nb);
+    const int64_t ppt = (p_stride + nb * FPS_BLOCK - 1) / (nb * FPS_BLOCK);
+    // more than 128 x 1024 x 16 = 256 x 1024 x 8 points on 256 workgroups: 9 .. 16 points per thread
+    if (!use_lazy) return {kFormGrid + 16, (int)nb};
+    return {kFormLazy + fps_round_ppt(ppt, 16), (int)nb};
+  }
+  if (p_stride <= kFpsRegMax) return {kFormReg + fps_round_ppt((p_stride + FPS_BLOCK - 1) / FPS_BLOCK, 8), 0};
+  return {kFormWalk, 0};
+}
+
+const void* fps_cooperative_kernel(int code) {
+  switch (code) {
+    case kFormLazy + 1: return reinterpret_cast<const void*>(&k_fps_lazy<1>);
+    case kFormLazy + 2: return reinterpret_cast<const void*>(&k_fps_lazy<2>);
+    case kFormLazy + 4: return reinterpret_cast<const void*>(&k_fps_lazy<4>);
+    case kFormLazy + 8: return reinterpret_cast<const void*>(&k_fps_lazy<8>);
+    case kFormLazy + 16: return reinterpret_cast<const void*>(&k_fps_lazy<16>);
+    case kFormGrid + 16: return reinterpret_cast<const void*>(&k_fps_grid<16>);
+  }
+  return nullptr;
+}
+
+// both cooperative kernels take the same argument list (the control block by pointer)
+hipError_t launch_fps_cooperative(FpsForm f, const float* p, const int64_t* lengths, const int64_t* n_samples,
+                                  const int64_t* start, int n, int64_t p_stride, void* ctl, int64_t* out, hipStream_t s) {
+  void* args[] = {(void*)&p, (void*)&lengths, (void*)&n_samples, (void*)&start, (void*)&n, (void*)&p_stride,
+                  (void*)&ctl, (void*)&out};
+  return hipLaunchCooperativeKernel(fps_cooperative_kernel(f.code), dim3(f.nb), dim3(FPS_BLOCK), args, 0, s);
+}
+
+template <int PPT>
+void launch_fps_reg(int n_clouds, const float* points, const int64_t* lengths, const int64_t* n_samples,
+                    const int64_t* start, int64_t p_stride, int64_t out_stride, int64_t* out_idx, hipStream_t st) {
+  hipLaunchKernelGGL(k_fps_reg<PPT>, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths, n_samples, start, p_stride,
+                     out_stride, out_idx);
+}
+
+// (the switches are read on every call: the tests set and clear them around single calls)
+bool fps_env(const char* name) { return getenv(name) != nullptr; }
 
 }  // namespace
 
 extern "C" int64_t iso_farthest_point_sampling_work_floats(int n_clouds, int64_t p_stride) {
   if (n_clouds < 0 || p_stride < 0) return 0;
   return (int64_t)n_clouds * p_stride + kFpsCtlFloats + 2;
+}
+
+extern "C" int iso_farthest_point_sampling_form(int64_t p_stride, int check_device) {
+  if (p_stride < 1 || p_stride >= (1ll << 31)) return -1;
+  const bool one_workgroup = fps_env("ISO_FPS_ONE_WORKGROUP");
+  FpsForm f = fps_form(p_stride, one_workgroup, !fps_env("ISO_FPS_NO_COOPERATIVE"));
+  if (check_device && f.nb > 0) {
+    // can the nb workgroups of 1024 be co-resident on the current device?  (what the cooperative launch asks)
+    int dev = 0, coop = 0, cus = 0, per_cu = 0;
+    bool ok = hipGetDevice(&dev) == hipSuccess &&
+              hipDeviceGetAttribute(&coop, hipDeviceAttributeCooperativeLaunch, dev) == hipSuccess && coop != 0 &&
+              hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+              hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fps_cooperative_kernel(f.code), FPS_BLOCK, 0) == hipSuccess &&
+              (int64_t)per_cu * cus >= f.nb;
+    if (!ok) {
+      (void)hipGetLastError();
+      f = fps_form(p_stride, one_workgroup, false);
+    }
+  }
+  return f.code;
 }
 
 extern "C" int iso_farthest_point_sampling(const float* points, const int64_t* lengths,
@@ -504,37 +577,18 @@ extern "C" int iso_farthest_point_sampling(const float* points, const int64_t* l
               "iso_farthest_point_sampling: null pointer");
   ISO_REQUIRE(p_stride < (1ll << 31), ISO_ERR_UNSUPPORTED, "iso_farthest_point_sampling: cloud too large");
   hipStream_t st = (hipStream_t)stream;
-  // (the tests run the memory-walking kernel as the reference: read on every call)
-  const bool one_workgroup = getenv("ISO_FPS_ONE_WORKGROUP") != nullptr;
-  if (p_stride >= kFpsGridMin && p_stride <= (int64_t)256 * FPS_BLOCK * 16 && !one_workgroup) {
-    // grid-wide form, cloud after cloud: k_fps_lazy with one point per thread, i.e. as many workgroups as the cloud fills,
-    // up to 128 -- the exchange is shared by many samples, more lists make longer runs (24 k points: 13.9 ms at 4 points
-    // per thread, 10.1 at 1); above 128 x 1024 x 16 points k_fps_grid on 256 workgroups.  (k_fps_grid measured 2.8 us per
-    // sample up to 50 k points, 5.0 at 500 k, 7.1 at 1 M -- the barrier's atomic round trips, not the arithmetic; fewer,
-    // fatter workgroups are not faster.)
-    const bool use_lazy = p_stride <= (int64_t)kFpsLazyGrid * FPS_BLOCK * 16;
-    const int64_t nb_max = use_lazy ? kFpsLazyGrid : kFpsMaxGrid;
-    int64_t nb = (p_stride + FPS_BLOCK - 1) / FPS_BLOCK;
-    nb = nb < 2 ? 2 : (nb > nb_max ? nb_max : nb);
-    const int64_t ppt = (p_stride + nb * FPS_BLOCK - 1) / (nb * FPS_BLOCK);
+  // test switches: ISO_FPS_ONE_WORKGROUP runs the memory-walking kernel (the reference of the other forms),
+  // ISO_FPS_NO_COOPERATIVE the forms a device takes that refuses the cooperative grid
+  const bool one_workgroup = fps_env("ISO_FPS_ONE_WORKGROUP");
+  FpsForm f = fps_form(p_stride, one_workgroup, !fps_env("ISO_FPS_NO_COOPERATIVE"));
+  if (f.nb > 0) {
     // (8-byte slots: the control block starts at the next 8-byte boundary; kFpsCtlFloats leaves room for it)
-    FpsCtl* ctl = reinterpret_cast<FpsCtl*>(((uintptr_t)(work + (int64_t)n_clouds * p_stride) + 7) & ~(uintptr_t)7);
+    void* ctl = reinterpret_cast<void*>(((uintptr_t)(work + (int64_t)n_clouds * p_stride) + 7) & ~(uintptr_t)7);
     bool refused = false;
     for (int n = 0; n < n_clouds; ++n) {
       (void)hipMemsetAsync(ctl, 0, kFpsCtlFloats * 4, st);
-      const float* p = points + (int64_t)n * p_stride * 3;
-      int64_t* out = out_idx + (int64_t)n * out_stride;
-      hipError_t e;
-      if (use_lazy) {
-        FpsCtlLazy* cl = reinterpret_cast<FpsCtlLazy*>(ctl);
-        if (ppt <= 1) e = launch_fps_lazy<1>((int)nb, p, lengths, n_samples, start, n, p_stride, cl, out, st);
-        else if (ppt <= 2) e = launch_fps_lazy<2>((int)nb, p, lengths, n_samples, start, n, p_stride, cl, out, st);
-        else if (ppt <= 4) e = launch_fps_lazy<4>((int)nb, p, lengths, n_samples, start, n, p_stride, cl, out, st);
-        else if (ppt <= 8) e = launch_fps_lazy<8>((int)nb, p, lengths, n_samples, start, n, p_stride, cl, out, st);
-        else e = launch_fps_lazy<16>((int)nb, p, lengths, n_samples, start, n, p_stride, cl, out, st);
-      } else {        // more than 128 x 1024 x 16 = 256 x 1024 x 8 points on 256 workgroups: 9 .. 16 points per thread
-        e = launch_fps_grid<16>((int)nb, p, lengths, n_samples, start, n, p_stride, ctl, out, st);
-      }
+      const hipError_t e = launch_fps_cooperative(f, points + (int64_t)n * p_stride * 3, lengths, n_samples, start, n,
+                                                  p_stride, ctl, out_idx + (int64_t)n * out_stride, st);
       if (e != hipSuccess) {
         (void)hipGetLastError();
         ISO_REQUIRE(n == 0, ISO_ERR_LAUNCH, "iso_farthest_point_sampling: cooperative launch failed: %s",
@@ -544,20 +598,18 @@ extern "C" int iso_farthest_point_sampling(const float* points, const int64_t* l
       }
     }
     if (!refused) { ISO_CHECK_LAUNCH("iso_farthest_point_sampling"); return ISO_OK; }
-    // the device cannot co-schedule the grid (first cloud refused): the one-workgroup form below
+    // the device cannot co-schedule the grid (first cloud refused): the one-workgroup forms
+    f = fps_form(p_stride, one_workgroup, false);
   }
-  if (p_stride <= (int64_t)FPS_BLOCK * 8 && !one_workgroup) {
-    // the cloud fits one workgroup's registers
-    const int64_t ppt = (p_stride + FPS_BLOCK - 1) / FPS_BLOCK;
-    if (ppt <= 1) hipLaunchKernelGGL(k_fps_reg<1>, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths, n_samples, start, p_stride, out_stride, out_idx);
-    else if (ppt <= 2) hipLaunchKernelGGL(k_fps_reg<2>, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths, n_samples, start, p_stride, out_stride, out_idx);
-    else if (ppt <= 4) hipLaunchKernelGGL(k_fps_reg<4>, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths, n_samples, start, p_stride, out_stride, out_idx);
-    else hipLaunchKernelGGL(k_fps_reg<8>, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths, n_samples, start, p_stride, out_stride, out_idx);
-    ISO_CHECK_LAUNCH("iso_farthest_point_sampling");
-    return ISO_OK;
+  switch (f.code) {
+    case kFormReg + 1: launch_fps_reg<1>(n_clouds, points, lengths, n_samples, start, p_stride, out_stride, out_idx, st); break;
+    case kFormReg + 2: launch_fps_reg<2>(n_clouds, points, lengths, n_samples, start, p_stride, out_stride, out_idx, st); break;
+    case kFormReg + 4: launch_fps_reg<4>(n_clouds, points, lengths, n_samples, start, p_stride, out_stride, out_idx, st); break;
+    case kFormReg + 8: launch_fps_reg<8>(n_clouds, points, lengths, n_samples, start, p_stride, out_stride, out_idx, st); break;
+    default:
+      hipLaunchKernelGGL(k_fps, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths, n_samples, start, p_stride,
+                         out_stride, work, out_idx);
   }
-  hipLaunchKernelGGL(k_fps, dim3(n_clouds), dim3(FPS_BLOCK), 0, st, points, lengths,
-                     n_samples, start, p_stride, out_stride, work, out_idx);
   ISO_CHECK_LAUNCH("iso_farthest_point_sampling");
   return ISO_OK;
 }

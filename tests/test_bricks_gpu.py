@@ -35,8 +35,13 @@ def _clouds():
 CLOUDS = _clouds()
 
 
-@pytest.mark.parametrize("name", sorted(CLOUDS))
-@pytest.mark.parametrize("knn_k", [8, 4, 12])
+# the full cloud list at the list sizes the callers use, then every other K + 1 in 2..13 on a reduced list, so that each of
+# k_brick_resample<8|10|12|16> (K + 1 in 2..5 | 9 | 6..8 | 10..13) runs on both sides of its boundaries
+_FUSED_CASES = [(k, n) for n in sorted(CLOUDS) for k in (8, 4, 12)] + \
+    [(k, n) for k in (1, 5, 6, 7, 9, 10, 11) for n in ("sphere300", "sphere5000", "duplicates", "lattice", "clump")]
+
+
+@pytest.mark.parametrize("knn_k,name", _FUSED_CASES, ids=["%d-%s" % c for c in _FUSED_CASES])
 def test_resample_fused_equals_standalone(dev, name, knn_k):
     from iso_points_amd import _lib, frnn
     from iso_points_amd.bricks import BrickGrid, resample_fused

@@ -79,6 +79,33 @@ def test_duplicates_and_ties_lower_index_first(dev):
     _cmp(dev, p, p, None, None, 8, 0.4, same=True)
 
 
+_LIST_SIZE_CLOUDS = {}
+
+
+def _list_size_clouds():
+    """2 000 sphere points, 40 of them exact copies of others, and a ragged second cloud (made once)."""
+    if not _LIST_SIZE_CLOUDS:
+        p = torch.cat([sphere_cloud(2000, seed=61), sphere_cloud(2000, seed=62)], dim=0)
+        p[:, 1000:1040] = p[:, 300:340]
+        _LIST_SIZE_CLOUDS["p"] = p
+        _LIST_SIZE_CLOUDS["len"] = torch.tensor([2000, 1234])
+    return _LIST_SIZE_CLOUDS["p"], _LIST_SIZE_CLOUDS["len"]
+
+
+@pytest.mark.parametrize("K", [1, 4, 5, 8, 9, 10, 11, 16, 17, 32])
+def test_list_sizes_across_kernel_instances(dev, K):
+    """iso_frnn_query picks k_query<4|8|10|16|32> from K: both sides of 4/5, 8/9, 10/11, 16/17, and the ends 1 and 32, on a
+    cloud with exact duplicates (ties at d2 = 0 and beyond) and a ragged batch.  Radius 0.12: a 2 000-point unit sphere
+    has ~7 neighbours within it on average (2000 * pi r^2 / 4 pi), the 1 234-point cloud ~4.5, so rows are short of K
+    from K = 8 on (-1 padding) and full for K = 1."""
+    p, lens = _list_size_clouds()
+    d, i, _, _ = _cmp(dev, p, p, lens, lens, K, 0.12, same=True)
+    assert (i[1, 1234:] == -1).all()
+    if K >= 16:
+        assert (i[0, :, -1] == -1).any() and (d[i == -1] == -1).all()
+    assert (i[..., 0][:, :1234] >= 0).all()
+
+
 def test_degenerate_clouds(dev):
     from iso_points_amd import frnn
     one = torch.zeros(1, 1, 3)

@@ -79,7 +79,7 @@ def test_fps(dev):
 
 
 def test_fps_small_clouds_in_registers(dev, monkeypatch):
-    """clouds below 8 k points take k_fps_reg (points and min-distances in registers, no memory access per sample): the
+    """clouds below 4 096 points take k_fps_reg (points and min-distances in registers, no memory access per sample): the
     memory-walking kernel's sequence on a ragged batch, a lattice (massive distance ties), duplicates sampled past
     exhaustion, and a non-zero start."""
     from iso_points_amd.point_processing import farthest_sampling
@@ -99,7 +99,7 @@ def test_fps_small_clouds_in_registers(dev, monkeypatch):
 
 
 def test_fps_grid_wide_form(dev, monkeypatch):
-    """clouds of >= 8 k points take the cooperative grid-wide kernel: same sample sequence as the
+    """clouds of >= 4 096 points take the cooperative grid-wide kernels: same sample sequence as the
     oracle and as the one-workgroup kernel, ragged batch, duplicated points (ties -> lowest index)."""
     O = _O()
     from iso_points_amd.point_processing import farthest_sampling

@@ -220,3 +220,29 @@ def classify_chain_outliers(O, model, pts, gpu_stage1, gpu_final, knn_k=8, tol=5
     counts["detail"] = [(i, float(ef[i]), float(e1[i]), float(dmoved[i] / scale), max(float(e1[j]) for j in (set(i_o[i, :knn_k + 1].tolist()) | set(i_g[i].tolist())) - {-1}))
                         for i in left[:8]]
     return counts, left
+
+
+# ---- farthest-point sampling: the definition in float64 ---------------------------------------------------------------
+FPS_F64_SLACK = 2.0 ** -20
+
+
+def fps_float64_deficit(points, seq):
+    """A sample sequence against the float64 statement of farthest-point sampling.  With D_s(i) the float64 squared distance
+    of point i (its float32 coordinates, exact in float64) to the nearest of seq[:s], every seq[s], s >= 1, must be a
+    maximum of D_s up to float32 rounding: D_s(seq[s]) >= (1 - 2^-20) max D_s.  A float32 squared distance carries at most
+    four roundings (<= 2^-22 relative), so the bound leaves a factor 4.  Returns the worst relative deficit
+    max_s (1 - D_s(seq[s]) / max D_s) (0 when every choice is the float64 maximum; a zero maximum demands a zero distance
+    and counts as deficit 1 otherwise)."""
+    p = np.asarray(points.detach().cpu().numpy() if torch.is_tensor(points) else points, dtype=np.float64)
+    seq = [int(i) for i in seq]
+    mind = np.full((p.shape[0],), np.inf)
+    worst = 0.0
+    for s, c in enumerate(seq):
+        if s:
+            top = mind.max()
+            if top > 0:
+                worst = max(worst, 1.0 - mind[c] / top)
+            elif mind[c] != 0:
+                worst = 1.0
+        mind = np.minimum(mind, ((p - p[c]) ** 2).sum(-1))
+    return worst
