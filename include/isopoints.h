@@ -471,6 +471,35 @@ int iso_pca_frames(const float* points, const int64_t* lengths, const int64_t* i
                    int64_t max_points, int K, int disambiguate, void* work, float* curvature_out,
                    float* frames_out, void* stream);
 
+/* iso_pca_frames_backward: the gradient of iso_pca_frames w.r.t. the points = what autograd gives the
+ * reference through DSS/utils/mathHelper.py:43-119 (kNN gather, torch_batch_svd's backward).  Held
+ * constant: the index rows, the ascending order, the clamp at 0 and the two signs of the sign rule (the
+ * cloud mean only enters a comparison and carries no gradient).  With curvature / frames the forward's own
+ * outputs (l, V) and grad_curvature (N,P,3), grad_frames (N,P,3,3) the incoming gradients (either may be
+ * NULL = zeros), per valid row i:
+ *   disambiguate: gn = g_V[:,0] + z x g_V[:,1], gz = g_V[:,2] + g_V[:,1] x n, gv = (gn, 0, gz) against the
+ *                 saved columns (n, n x z, z) -- G below is even in every column's sign; else gv = g_V;
+ *   S_ab = (v_a.gv_b - v_b.gv_a) / (2 (l_b - l_a)), G_i = V (diag(g_l) + S) V^T;
+ *   grad_points_out[t] = sum over the slots (i,j) with idx[i,j] = t, in ascending (i,j), of
+ *                        (2/K) G_i (x_t - m_i),   m_i = the neighbourhood mean with the forward's bits.
+ * Where the formula is undefined: a pair with |l_b - l_a| <= 2e-5 l_max gives S_ab = 0 (the tolerance the
+ * forward's eigenvalues are judged by; below it the sign of the gap is not determined); a row with
+ * l_max = 0 therefore gives G = 0; an eigenvalue that is 0 in `curvature` (clamped, or exactly 0) passes no
+ * g_l; rows i >= lengths[b] give and receive nothing and their incoming gradients are never read (NaN
+ * included).  Indices are clamped into the cloud as the forward clamps them.
+ * Launches: the adjoint (one lane per row: G_i, m_i, the row's targets as int32), the counting sort of
+ * the P*K slots by target (integer atomics, iso_prefix_sum), and the sum: a target in at most 64 slots
+ * sorts its list and sums it in its own lane; longer lists take one wave each (sorted up to 1024 slots,
+ * beyond that a strided scan of the slots) and one butterfly.  No float atomics: two runs give the same
+ * bits.  Limit: N * P * K < 2^31 - 1.  work: iso_pca_frames_backward_work_bytes(N, P, K), 16-B aligned;
+ * the size helper needs no GPU.                                                                        */
+int64_t iso_pca_frames_backward_work_bytes(int n_clouds, int64_t max_points, int K);
+int iso_pca_frames_backward(const float* points, const int64_t* lengths, const int64_t* idx,
+                            int n_clouds, int64_t max_points, int K, int disambiguate,
+                            const float* curvature, const float* frames,
+                            const float* grad_curvature, const float* grad_frames, void* work,
+                            int64_t work_bytes, float* grad_points_out, void* stream);
+
 /* ------------------------------------------------------------------------
  * D. EWA surface splatting
  *    replaces SurfaceSplatting (DSS/core/rasterizer.py:103-661), the pybind module

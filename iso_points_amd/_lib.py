@@ -78,6 +78,8 @@ SIGNATURES = {
     "iso_farthest_point_sampling_form": (_I, [_L, _I]),
     "iso_pca_frames_work_bytes": (_L, [_I]),
     "iso_pca_frames": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _P]),
+    "iso_pca_frames_backward_work_bytes": (_L, [_I, _L, _I]),
+    "iso_pca_frames_backward": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _P, _P, _L, _P, _P]),
     "iso_splat_view_flags": (_I, [_P, _P, _P, _P, _L, _I, _F, _F, _I, _P]),
     "iso_compact_rows": (_I, [_P, _P, _P, _P, _L, _L, _I, _P]),
     "iso_splat_vrk_h": (_I, [_P, _P, _P, _P, _P, _I, _L, _P]),

@@ -60,17 +60,13 @@ __device__ __forceinline__ void order_pair(float (&l)[3], float (&v)[3][3]) {
   }
 }
 
-// Neighbourhood mean, centred covariance (1/K) sum (x_j - m)(x_j - m)^T, cyclic Jacobi, eigenvalues clamped at 0 and sorted
-// ascending with their eigenvectors (column c of v belongs to l[c]; signs as Jacobi leaves them).  cloud: the cloud's
-// first point; row: the K neighbour indices of the query (the point itself included); len: points in the cloud.
-__device__ __forceinline__ void pca_neighbourhood_eig(const float* __restrict__ cloud, const int64_t* __restrict__ row, int K,
-                                                      int64_t len, float (&l)[3], float (&v)[3][3]) {
-  const float inv_k = 1.0f / (float)K;
-  // pass 1: neighbourhood mean (pt_mean, :84), accumulated relative to the first neighbour: the sums stay small next to
-  // the coordinates (a cloud far from the origin loses no bits to them), and K exact duplicates give m = x_0 exactly, so
-  // their covariance is exactly 0 (remove_outliers then sees the reference's 0 / 0).  An index outside [0, len) is
-  // clamped into the cloud: kNN never returns one for a valid row of a cloud longer than K, and the clamp keeps every
-  // read inside the points tensor.
+// Neighbourhood mean (pt_mean, :84), accumulated relative to the first neighbour: the sums stay small next to the
+// coordinates (a cloud far from the origin loses no bits to them), and K exact duplicates give m = x_0 exactly, so their
+// covariance is exactly 0 (remove_outliers then sees the reference's 0 / 0).  An index outside [0, len) is clamped into
+// the cloud: kNN never returns one for a valid row of a cloud longer than K, and the clamp keeps every read inside the
+// points tensor.  The backward pass (pca_backward.hip) centres on the same bits.
+__device__ __forceinline__ void pca_neighbourhood_mean(const float* __restrict__ cloud, const int64_t* __restrict__ row, int K,
+                                                       int64_t len, float inv_k, float& mx, float& my, float& mz) {
   const float* x0 = cloud + min(max(row[0], (int64_t)0), len - 1) * 3;
   const float ox = x0[0], oy = x0[1], oz = x0[2];
   float sx = 0.0f, sy = 0.0f, sz = 0.0f;
@@ -82,7 +78,20 @@ __device__ __forceinline__ void pca_neighbourhood_eig(const float* __restrict__ 
     sy += x[1] - oy;
     sz += x[2] - oz;
   }
-  const float mx = ox + sx * inv_k, my = oy + sy * inv_k, mz = oz + sz * inv_k;
+  mx = ox + sx * inv_k;
+  my = oy + sy * inv_k;
+  mz = oz + sz * inv_k;
+}
+
+// Neighbourhood mean, centred covariance (1/K) sum (x_j - m)(x_j - m)^T, cyclic Jacobi, eigenvalues clamped at 0 and sorted
+// ascending with their eigenvectors (column c of v belongs to l[c]; signs as Jacobi leaves them).  cloud: the cloud's
+// first point; row: the K neighbour indices of the query (the point itself included); len: points in the cloud.
+__device__ __forceinline__ void pca_neighbourhood_eig(const float* __restrict__ cloud, const int64_t* __restrict__ row, int K,
+                                                      int64_t len, float (&l)[3], float (&v)[3][3]) {
+  const float inv_k = 1.0f / (float)K;
+  // pass 1: the mean
+  float mx, my, mz;
+  pca_neighbourhood_mean(cloud, row, K, len, inv_k, mx, my, mz);
   // pass 2: centred products (central_diff, :87); the second read of the K neighbours hits cache
   float cxx = 0.0f, cxy = 0.0f, cxz = 0.0f, cyy = 0.0f, cyz = 0.0f, czz = 0.0f;
 #pragma unroll 4

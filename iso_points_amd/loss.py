@@ -8,7 +8,9 @@ angle-weighted pseudonormals in place of the reference's raster parity (include/
 
 The point-cloud regularisers of the splatting renderer, ProjectionLoss and RepulsionLoss (DSS/training/losses.py:149-515),
 are surface_losses and the two modules on it: one search for the 32 nearest other points, two fused normal mollifications
-and one fused sweep that returns both losses with their gradients (include/isopoints.h section K).
+and one fused sweep that returns both losses with their gradients (include/isopoints.h section K).  The third, NormalLoss
+(:86-102), compares the points' normals with the PCA normals of math_helper and reaches the positions through the
+local-frame kernel's backward (iso_pca_frames_backward).
 
 The nearest-point search runs on the cell grid of iso_points_amd.frnn (exact, any distance), fused with the
 normal term and the per-cloud sums; the backward pass is a gather over counting-sorted index lists.  Neither
@@ -843,3 +845,72 @@ class RepulsionLoss(_SurfaceLoss):
     reference reads knn_tree.shape at :438, which does not exist)."""
     _which = "repulsion"
     _rebuild_default = True
+
+
+# ------------------------------------------------------------------------------------ the third point regulariser: NormalLoss
+class _Padded(object):
+    """A (points, lengths) pair in the shape the estimators take a cloud object."""
+
+    def __init__(self, points, lengths):
+        self._points, self._lengths = points, lengths
+
+    def points_padded(self):
+        return self._points
+
+    def num_points_per_cloud(self):
+        return self._lengths
+
+
+class NormalLoss(torch.nn.Module):
+    """DSS/training/losses.py:86-102: 1 - |cos| between every point's normal and the PCA normal of its K-neighbourhood
+    (math_helper.estimate_pointcloud_normals), per valid point (sum L_b,) packed before the reduction; the cosine is
+    torch.nn.functional.cosine_similarity's, eps = 1e-8.  Gradients reach the normals through torch and the point
+    positions through the local-frame kernel's backward (iso_pca_frames_backward: the neighbour index, the eigenvalue
+    order and the signs are constants; math_helper.pca_frames states the rules).  neighborhood_size <= 32."""
+
+    def __init__(self, reduction="mean", neighborhood_size=16):
+        super(NormalLoss, self).__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("Invalid reduction method (%s)" % (reduction,))
+        self.reduction = reduction
+        self.neighborhood_size = neighborhood_size
+
+    def forward(self, point_clouds, neighborhood_size=None, reduction=None):
+        """The loss of `point_clouds`: an object with points_padded / normals_padded / num_points_per_cloud, or a
+        (points, normals[, lengths]) tuple of padded tensors.  neighborhood_size and reduction hold for this call."""
+        from .math_helper import estimate_pointcloud_normals
+        reduction = reduction or self.reduction
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("Invalid reduction method (%s)" % (reduction,))
+        if neighborhood_size is None:
+            neighborhood_size = self.neighborhood_size
+        if isinstance(point_clouds, (tuple, list)):
+            if len(point_clouds) not in (2, 3):
+                raise ValueError("point_clouds: a (points, normals[, lengths]) tuple or a point-cloud object")
+            points, normals = point_clouds[0], point_clouds[1]
+            lengths = point_clouds[2] if len(point_clouds) == 3 else None
+        else:
+            points, normals, lengths = point_clouds, None, None
+            if hasattr(point_clouds, "normals_padded"):
+                normals = point_clouds.normals_padded()
+        pts, conv_len = convert_pointclouds_to_tensor(points)
+        if pts.dim() != 3 or pts.shape[-1] != 3:
+            raise ValueError("NormalLoss: points must be (N, P, 3), got %s" % (tuple(pts.shape),))
+        if normals is None or not torch.is_tensor(normals) or tuple(normals.shape) != tuple(pts.shape):
+            raise ValueError("NormalLoss: normals must have the shape of points, %s" % (tuple(pts.shape),))
+        if lengths is None:
+            lengths = conv_len
+        lengths = torch.as_tensor(lengths)
+        host = host_lengths(lengths)              # before any reshape: the host copy rides on this very tensor
+        if len(host) != pts.shape[0] or any(l > pts.shape[1] or l < 0 for l in host):
+            raise ValueError("NormalLoss: lengths must hold one count in [0, %d] per cloud" % pts.shape[1])
+        _on_gpu(pts, normals)
+        lengths = with_host_lengths(lengths.reshape(-1).to(device=pts.device, dtype=torch.int64), host)
+        normals_ref = estimate_pointcloud_normals(_Padded(pts, lengths), neighborhood_size=neighborhood_size)
+        loss = 1 - torch.nn.functional.cosine_similarity(padded_to_packed(normals, host),
+                                                         padded_to_packed(normals_ref, host)).abs()
+        if reduction == "sum":
+            return loss.sum()
+        if reduction == "mean":
+            return loss.mean()
+        return loss

@@ -280,12 +280,14 @@ def remove_outliers(pointclouds, neighborhood_size=16, tolerance=0.05):
     cloud's length (point_processing.py:16-31).  Returns the kept points compacted per cloud, in order, as
     (points_padded (N, max kept, 3), num_points (N,)), the way upsample / wlop return.  The ratio is the reference's plain
     division: in a neighbourhood of exact duplicates it is 0 / 0 = NaN and the point is dropped, as in the reference.
-    Same limits as the estimator: neighborhood_size <= 32, no backward."""
+    Same limit as the estimator: neighborhood_size <= 32.  The mask is a selection and is computed under no_grad, so points
+    that require grad build no graph for it; the kept rows are an ordinary index of `points`."""
     from .math_helper import estimate_pointcloud_local_coord_frames
     points, num_points = convert_pointclouds_to_tensor(pointclouds)
     # only the eigenvalues are read: the sign rule does not change them
-    variance, _ = estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size=neighborhood_size,
-                                                         disambiguate_directions=False)
+    with torch.no_grad():
+        variance, _ = estimate_pointcloud_local_coord_frames(pointclouds, neighborhood_size=neighborhood_size,
+                                                             disambiguate_directions=False)
     N, P = points.shape[0], points.shape[1]
     inside = torch.arange(P, device=points.device)[None, :] < num_points.to(points.device)[:, None]
     mask = (variance[..., 0] / torch.sum(variance, dim=-1) < tolerance) & inside
