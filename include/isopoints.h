@@ -166,7 +166,23 @@ int iso_siren_sdf_grad_coded(const float* pts, float* sdf_out, float* grad_out,
  * folded into the weights.  raw = for l = 0..n_layers: W_l (row-major [out][in]) then b_l.
  * hidden 256 / 512 with n_freq <= 6 run on the fp16 matrix cores at f32 accuracy (two fp16 parts
  * per operand under exact power-of-two scales, as iso_siren_set_gemm_mode(1)); ISO_IDR_GEMM=f32 in
- * the environment, hidden 128 and wider encodings use the f32 matrix cores.                     */
+ * the environment, hidden 128 and wider encodings use the f32 matrix cores.
+ *
+ * iso_idr_set_gemm_mode: 1 (the default) = split fp16 where it applies, 0 = the f32 matrix cores for every shape; any other
+ *   value is ISO_ERR_INVALID.  The initial value is 0 when ISO_IDR_GEMM=f32 is in the environment.  The mode may change
+ *   between two calls on the same packed buffer and workspace: both hold what either form needs.
+ * iso_idr_step_form (host only, no GPU): the step kernel a call with this shape takes under the current mode, by the
+ *   predicates the launch itself uses.  value_only = 0: iso_project_idr and iso_idr_sdf_grad with grad_out; value_only = 1:
+ *   iso_trace_idr and iso_idr_sdf_grad with grad_out = NULL.  NT = hidden / 16, D0 = 3 + 6 n_freq:
+ *     400 + NT  k_idr_step_x16<hidden, ., false>   hidden 256 / 512, D0 <= 39 (n_freq <= 6), mode 1, value_only = 0
+ *     500 + NT  k_idr_step_x16<hidden, ., true>    the same, value_only = 1
+ *     200 + NT  k_idr_step_fs<NT, false>           otherwise: hidden 256 / 512, D0 <= 48 (n_freq <= 7), value_only = 0
+ *     300 + NT  k_idr_step_fs<NT, true>            otherwise: D0 <= 48, value_only = 1 (hidden 128 included)
+ *     100 + NT  k_idr_step<NT> (staged)            otherwise: hidden 128 with value_only = 0, and every D0 > 48 (n_freq >= 8)
+ *     -1        a shape the entry points refuse (ISO_ERR_UNSUPPORTED)                                                   */
+int iso_idr_set_gemm_mode(int mode);
+int iso_idr_get_gemm_mode(void);
+int iso_idr_step_form(int hidden, int n_layers, int skip_layer, int n_freq, int value_only);
 int64_t iso_idr_raw_floats(int hidden, int n_layers, int skip_layer, int n_freq);
 int64_t iso_idr_packed_floats(int hidden, int n_layers);
 int iso_idr_pack_weights(const float* raw, float* packed, int hidden, int n_layers,

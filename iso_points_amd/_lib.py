@@ -39,6 +39,9 @@ SIGNATURES = {
     "iso_project_siren_counts_offset": (_L, [_L, _I, _I]),
     "iso_project_siren": (_I, [_P, _P, _P, _P, _L, _P, _I, _I, _F, _F, _I, _F, _P, _L, _P]),
     "iso_siren_sdf_grad": (_I, [_P, _P, _P, _L, _P, _I, _I, _F, _F, _P, _L, _P]),
+    "iso_idr_set_gemm_mode": (_I, [_I]),
+    "iso_idr_get_gemm_mode": (_I, []),
+    "iso_idr_step_form": (_I, [_I, _I, _I, _I, _I]),
     "iso_idr_raw_floats": (_L, [_I, _I, _I, _I]),
     "iso_idr_packed_floats": (_L, [_I, _I]),
     "iso_idr_pack_weights": (_I, [_P, _P, _I, _I, _I, _I, _P]),

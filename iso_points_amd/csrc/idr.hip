@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256, 1) void k_idr_step(IdrArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Feature-split form (the default; idr_launch keeps the staged kernel above for H = 128 gradients and wide encodings).
+// Feature-split form (the f32 default; idr_form keeps the staged kernel above for H = 128 gradients and wide encodings).
 //
 // Same idea as siren_x3.hip, with the f32 matrix cores: a workgroup holds the activations of
 // P = 64 points (NB = 4 point tiles of 16) in LDS in the B-operand layout, act[q][n][lane][4]
@@ -261,11 +261,12 @@ __global__ __launch_bounds__(256, 1) void k_idr_step(IdrArgs a) {
 // MFMAs.  A q-chunk is TW*NB*4 = 128 MFMAs (4096 cycles) per wave for 8 weight loads and 4 LDS reads
 // per lane, which ride behind the MFMAs.  The positional encoding and its derivative are
 // evaluated once per tile into a small LDS table.
+constexpr int kIdrFsEncRows = 48;                        // D0 <= 48 (F <= 7) here; wider encodings use the staged kernel
 template <int NT>
 struct IdrFs {
   static constexpr int NB = 4, P = 16 * NB, NW = 4, TW = NT / NW;
   static constexpr size_t kActBytes = (size_t)NT * NB * 1024;
-  static constexpr int kEncRows = 48;                    // D0 <= 48 (F <= 7) here; wider encodings use the staged kernel
+  static constexpr int kEncRows = kIdrFsEncRows;
   static constexpr size_t kEncBytes = (size_t)2 * kEncRows * P * sizeof(float);     // value + derivative
   static constexpr size_t kRedBytes = (size_t)NW * P * 16;
   static constexpr size_t kLds = kActBytes + kEncBytes + kRedBytes;
@@ -566,14 +567,7 @@ void idr_launch_fs(const IdrArgs& a, int blocks, hipStream_t st) {
 }
 
 template <int NT>
-void idr_launch(const IdrArgs& a, int blocks, hipStream_t st) {
-  // H = 128 leaves only 32 MFMAs per q-chunk and wave: the staged kernel is 7 % faster there
-  // (value-only evaluations always take it where it exists: the staged kernel has no forward-only form)
-  if ((NT >= 16 || a.fwd_only) && a.s.D0 <= IdrFs<NT>::kEncRows) {
-    if (a.fwd_only) idr_launch_fs<NT, true>(a, blocks, st);
-    else idr_launch_fs<NT, false>(a, blocks, st);
-    return;
-  }
+void idr_launch_staged(const IdrArgs& a, int blocks, hipStream_t st) {
   const size_t lds = (size_t)(5 * NT * 256) * sizeof(float);
   static bool attr_done = false;
   if (!attr_done) {
@@ -584,19 +578,53 @@ void idr_launch(const IdrArgs& a, int blocks, hipStream_t st) {
   hipLaunchKernelGGL(k_idr_step<NT>, dim3(blocks), dim3(256), lds, st, a);
 }
 
-int idr_dispatch(const IdrArgs& a, int blocks, hipStream_t st) {
-  switch (a.s.H / 16) {
-    case 8: idr_launch<8>(a, blocks, st); return 0;
-    case 16: idr_launch<16>(a, blocks, st); return 0;
-    case 32: idr_launch<32>(a, blocks, st); return 0;
-    default: return -1;
-  }
-}
-
 bool idr_shape_ok(int H, int n_layers, int skip, int F) {
   const int D0 = 3 + 6 * F;
   return (H == 128 || H == 256 || H == 512) && n_layers >= 2 && n_layers <= 12 && F >= 0 && F <= 10 &&
          D0 <= 63 && (skip < 0 || (skip >= 1 && skip < n_layers)) && H > D0;
+}
+
+// 1 = split-fp16 kernel (idr_x16.hip) where idr_x16_supported: H = 256 / 512 with encodings of <= 39 slots; 0 = the f32-MFMA
+// kernels of this file for every shape.  Default 1; ISO_IDR_GEMM=f32 in the environment selects 0 at load time.
+int g_idr_gemm_mode = -1;
+int idr_gemm_mode() {
+  if (g_idr_gemm_mode < 0) {
+    const char* e = getenv("ISO_IDR_GEMM");
+    g_idr_gemm_mode = (e && e[0] == 'f') ? 0 : 1;
+  }
+  return g_idr_gemm_mode;
+}
+
+// The ONE place that decides which kernel a call takes (iso_idr_step_form reports it, idr_launch_form launches it):
+//   100 + NT  k_idr_step<NT>            200 + NT  k_idr_step_fs<NT, false>      300 + NT  k_idr_step_fs<NT, true>
+//   400 + NT  k_idr_step_x16<16 NT, ., false>                                   500 + NT  k_idr_step_x16<16 NT, ., true>
+//   -1        a shape idr_shape_ok refuses
+int idr_form(int H, int n_layers, int skip, int F, bool value_only) {
+  if (!idr_shape_ok(H, n_layers, skip, F)) return -1;
+  const int NT = H / 16, D0 = 3 + 6 * F;
+  if (idr_gemm_mode() == 1 && idr_x16_supported(H, n_layers, skip, F)) return (value_only ? 500 : 400) + NT;
+  // H = 128 leaves only 32 MFMAs per q-chunk and wave: the staged kernel is 7 % faster there
+  // (value-only evaluations always take the feature-split form where it exists: the staged kernel has no forward-only form)
+  if ((NT >= 16 || value_only) && D0 <= kIdrFsEncRows) return (value_only ? 300 : 200) + NT;
+  return 100 + NT;
+}
+
+int idr_launch_form(int form, const IdrArgs& a, int blocks, int64_t n, hipStream_t st) {
+  // (the staged kernel serves both; every other form was chosen for the value_only the arguments must carry)
+  const bool value_form = (form >= 300 && form < 400) || form >= 500;
+  if (form >= 200 && value_form != (a.fwd_only != 0)) return -1;
+  switch (form) {
+    case 108: idr_launch_staged<8>(a, blocks, st); return 0;
+    case 116: idr_launch_staged<16>(a, blocks, st); return 0;
+    case 132: idr_launch_staged<32>(a, blocks, st); return 0;
+    case 216: idr_launch_fs<16, false>(a, blocks, st); return 0;
+    case 232: idr_launch_fs<32, false>(a, blocks, st); return 0;
+    case 308: idr_launch_fs<8, true>(a, blocks, st); return 0;
+    case 316: idr_launch_fs<16, true>(a, blocks, st); return 0;
+    case 332: idr_launch_fs<32, true>(a, blocks, st); return 0;
+    case 416: case 432: case 516: case 532: return idr_x16_launch(&a, n, st);
+    default: return -1;
+  }
 }
 
 IdrShape mk_shape(int H, int n_layers, int skip, int F) { return IdrShape{H, n_layers, skip, F, 3 + 6 * F}; }
@@ -612,18 +640,19 @@ extern "C" int64_t iso_idr_raw_floats(int hidden, int n_layers, int skip_layer, 
   IdrShape s = mk_shape(hidden, n_layers, skip_layer, n_freq);
   return idr_raw_off(s, n_layers + 1);
 }
-// The split-fp16 kernel (idr_x16.hip) serves H = 256 / 512 with encodings of <= 39 slots; ISO_IDR_GEMM=f32 in
-// the environment keeps the f32-MFMA kernels of this file for every shape.
-static bool idr_use_x16(int H, int n_layers, int skip, int F) {
-  static int forced = -1;
-  if (forced < 0) {
-    const char* e = getenv("ISO_IDR_GEMM");
-    forced = (e && e[0] == 'f') ? 1 : 0;
-  }
-  return !forced && idr_x16_supported(H, n_layers, skip, F);
+extern "C" int iso_idr_set_gemm_mode(int mode) {
+  ISO_REQUIRE(mode == 0 || mode == 1, ISO_ERR_INVALID, "iso_idr_set_gemm_mode: mode must be 0 (f32 MFMA) or 1 (split fp16)");
+  g_idr_gemm_mode = mode;
+  return ISO_OK;
 }
 
-// (the packed buffer always has room for the split-fp16 images: its size may not depend on the environment)
+extern "C" int iso_idr_get_gemm_mode(void) { return idr_gemm_mode(); }
+
+extern "C" int iso_idr_step_form(int hidden, int n_layers, int skip_layer, int n_freq, int value_only) {
+  return idr_form(hidden, n_layers, skip_layer, n_freq, value_only != 0);
+}
+
+// (the packed buffer always has room for the split-fp16 images: its size depends neither on the environment nor on the mode)
 extern "C" int64_t iso_idr_packed_floats(int hidden, int n_layers) {
   return idr_total(hidden, n_layers) + idr_x16_floats(hidden, n_layers);
 }
@@ -679,9 +708,13 @@ static int idr_run(const float* pts_in, float* pts_out, float* normals_out, uint
   int32_t* counts = idxB + n;
   int64_t tiles = (n + 63) / 64;
   int blocks = (int)(tiles < kIdrBlocks ? tiles : kIdrBlocks);
-  const bool x16 = idr_use_x16(hidden, n_layers, skip_layer, n_freq);
-  auto run = [&](const IdrArgs& args) { return x16 ? idr_x16_launch(&args, n, st) : idr_dispatch(args, blocks, st); };
+  // value only: tracing, and an evaluation without grad_out (the Newton loop needs the gradient)
+  const bool value_only = trace || (eval_only && !grad_out);
+  const int form = idr_form(hidden, n_layers, skip_layer, n_freq, value_only);
+  const bool x16 = form >= 400;
+  auto run = [&](const IdrArgs& args) { return idr_launch_form(form, args, blocks, n, st); };
   IdrArgs a;
+  a.fwd_only = value_only ? 1 : 0;
   a.packed = packed; a.stash = stash; a.n = n; a.s = mk_shape(hidden, n_layers, skip_layer, n_freq);
   a.beta = beta; a.tol = tol;
   if (eval_only) {
@@ -689,7 +722,6 @@ static int idr_run(const float* pts_in, float* pts_out, float* normals_out, uint
     a.sdf_out = sdf_out; a.grad_out = grad_out;
     a.idx_in = nullptr; a.count_in = nullptr; a.idx_out = nullptr; a.count_out = nullptr;
     a.do_move = 0; a.eval_only = 1;
-    a.fwd_only = grad_out ? 0 : 1;
     if (x16 && idr_dynamic_tiles_enabled()) {            // one tile counter, zeroed ahead of the launch
       hipLaunchKernelGGL(k_idr_zero, dim3(1), dim3(64), 0, st, counts + 64, 1);
       a.tile_ctr = counts + 64;
@@ -700,7 +732,7 @@ static int idr_run(const float* pts_in, float* pts_out, float* normals_out, uint
     hipLaunchKernelGGL(k_idr_zero, dim3(2), dim3(64), 0, st, counts, 128);
     if (trace) {                         // levelset_sampling.py:764,790: active above 0.1 tol, valid up to tol
       a.dirs = trace->dirs; a.alpha = trace->alpha; a.bound = trace->bound;
-      a.tol = 0.1f * tol; a.tol_valid = tol; a.fwd_only = 1;
+      a.tol = 0.1f * tol; a.tol_valid = tol;
     }
     for (int it = 0; it <= max_iters; ++it) {
       a.pts = pts_out; a.normals = normals_out; a.mask = mask_out; a.sdf_out = trace ? sdf_out : nullptr; a.grad_out = nullptr;

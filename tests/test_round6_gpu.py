@@ -44,14 +44,29 @@ def test_siren_step_repeat_stress_1m(dev, gemm_mode):
     _assert_repeats(run, 20, "SIREN 4x256 projection of 1 M points")
 
 
+@pytest.fixture(params=["split16", "f32"])
+def idr_gemm_mode(request):
+    """Both ways of forming the IDR hidden-layer products (include/isopoints.h: iso_idr_set_gemm_mode)."""
+    from iso_points_amd import _lib
+    before = _lib.load().iso_idr_get_gemm_mode()
+    _lib.call("iso_idr_set_gemm_mode", 1 if request.param == "split16" else 0)
+    yield request.param
+    _lib.call("iso_idr_set_gemm_mode", before)
+
+
 @pytest.mark.parametrize("H,NL,skip,P,reps", [(512, 8, (4,), 1000000, 20), (256, 4, (2,), 1000000, 20)])
-def test_idr_step_repeat_stress_1m(dev, H, NL, skip, P, reps, gemm_mode):
-    """k_idr_step_x16<512,2,*> / <256,3,*> (up to 100 spilled VGPRs; f32 mode: k_idr_step<16>, 232) at 1 M points."""
+def test_idr_step_repeat_stress_1m(dev, H, NL, skip, P, reps, idr_gemm_mode):
+    """k_idr_step_x16<512,2,false> / <256,3,false> (up to 100 spilled VGPRs) at 1 M points; in the f32 mode
+    (iso_idr_set_gemm_mode(0): the SIREN switch does not reach this path) the same shapes take k_idr_step_fs<32,false> /
+    <16,false>, which spill nothing."""
     O = _O()
+    from iso_points_amd import _lib
     from iso_points_amd.levelset_sampling import UniformProjection, full_lengths
+    form = _lib.load().iso_idr_step_form(H, NL, skip[0], 6, 0)
+    assert form == (400 if idr_gemm_mode == "split16" else 200) + H // 16
     torch.manual_seed(1)
     m = O.IdrSDF(hidden_size=H, n_layers=NL, skip_in=skip, num_frequencies=6).to(dev)
-    if gemm_mode == "f32" and H == 512:
+    if idr_gemm_mode == "f32" and H == 512:
         P, reps = 250000, 8              # the f32-MFMA kernel is 3x slower: the same pin on a quarter of the cloud
     pts = (sphere_cloud(P, seed=4) * 0.6).to(dev)
     proj = UniformProjection()
@@ -118,11 +133,17 @@ def test_bandwidth_two_views_repeat_stress(dev):
     views = torch.stack([look_at_view(3.0, 20.0, 180.0 * i) for i in range(n_views)]).to(dev).contiguous()
     ss = SurfaceSplatting(raster_settings=PointsRasterizationSettings(image_size=64))
     mask, cnt = view_mask(pts, nrm, views)
+    # h is written where the point is renderable in the view and UNTOUCHED elsewhere (bricks.py: splat_h_fused; the two
+    # views face each other, so most (view, point) pairs are not): those entries are whatever the allocator's block held
+    # and take no part in the comparison -- every written entry does, bit for bit, and must lie inside h's clamp
+    seen = torch.stack([(mask >> v) & 1 for v in range(n_views)]).bool()
+    assert 0.2 < seen.float().mean().item() < 0.8
 
     def run():
         grid = BrickGrid(P, dev).build(pts, nrm, payload=mask, radius=ss.frnn_radius, cell_scale=H_CELL_SCALE)
         h = splat_h_fused(grid, mask, cnt, n_views)
-        return (h.clone(),)
+        assert bool(((h[seen] >= 5e-5) & (h[seen] <= 0.01)).all())
+        return (torch.where(seen, h, torch.zeros_like(h)),)
     _assert_repeats(run, 10, "fused bandwidth, two views")
 
 
