@@ -1289,6 +1289,59 @@ int iso_disk_select(int n_clouds, int64_t p_stride, int64_t s_out, uint8_t* mask
 int iso_disk_area_radius(const float* areas, const int64_t* tris_first, const int64_t* tris_len, int n_meshes,
                          int64_t n_tris, int64_t n_samples, float* radius_out, void* stream);
 
+/* ----------------------------------------------------------------------
+ * M. Mesh rasterisation: faces, depth and barycentrics per pixel (csrc/mesh_raster.hip)
+ *    serves the places where the reference renders a ground-truth mesh through pytorch3d's MeshRasterizer:
+ *      scripts/create_mvr_data_from_mesh.py:143-216   every synthetic training set: MeshRasterizer(faces_per_pixel=5,
+ *                                                     blur_radius=0) -> HardFlatShader -> RGBA, mask, dense depth
+ *      DSS/training/losses.py:550-578                 SignedDistanceLoss: four depth layers at 256 x 256
+ *      tests/test_data.py, tests/test_dvr_camera.py   the reference's own tests
+ *    = pytorch3d.renderer.mesh.rasterize_meshes at blur_radius = 0 (nothing else is ever passed), no backward pass.
+ *
+ *    Inputs, as rasterize_meshes has them after its transform: face_verts (F,3,3) f32 packed over N meshes, x and y in NDC
+ *    (+X left, +Y up), z the view-space depth; first_idx (N) / num_faces (N) i64, first_idx non-decreasing (packed order);
+ *    a square image of side S; K = faces_per_pixel in 1..8.
+ *
+ *    The rule (float32, no FMA contraction, IEEE division; tests/mesh_raster_oracle.py states it in float64 and float32).
+ *    Centre of output row r, column c: X = 1 - (2c+1)/S, Y = 1 - (2r+1)/S (pytorch3d's PixToNdc with its x/y flip).
+ *    edge(a, b; q) = (qx - ax)(by - ay) - (qy - ay)(bx - ax), in this difference form.  area = edge(v0, v1; v2).
+ *    A face is skipped if |area| <= 1e-8, if its largest z is < 0, if any of its nine numbers is not finite, or if
+ *    cull_backfaces is set and area < 0 (area > 0 is counter-clockwise in the displayed image).
+ *    w0 = edge(v1, v2; p) / area, w1 = edge(v2, v0; p) / area, w2 = edge(v0, v1; p) / area; the pixel is inside iff all
+ *    three are > 0 (strict: a centre exactly on a shared edge belongs to neither face, as in pytorch3d).
+ *    b = w; with perspective_correct t = (w0 z1 z2, w1 z0 z2, w2 z0 z1), b = t / ((t0 + t1) + t2).
+ *    pz = (b0 z0 + b1 z1) + b2 z2; the pair is skipped if pz < 0 or pz is not finite.
+ *    dist = -(smallest squared distance in NDC xy from p to the segments v0v1, v0v2, v1v2; a segment shorter than
+ *    1e-4 (l2 <= 1e-8) counts as its second end point).
+ *    Per pixel the K smallest pairs by the total order (pz, packed face index) ascending: equal depth goes to the lower
+ *    index.  pix_to_face (N,S,S,K) i64, zbuf (N,S,S,K), bary (N,S,S,K,3), dists (N,S,S,K) f32; an empty slot holds -1 in
+ *    all four.  Every pixel of every mesh is written.
+ *    Deviations from pytorch3d: no 1e-8 added to the denominators (area, t0 + t1 + t2) -- those faces and pairs are skipped
+ *    instead; NaN / inf faces are skipped; no max_faces_per_bin -- a tile's face list has no capacity and cannot overflow.
+ *
+ *    Three passes around one caller-side read of the pair total, the shape of the splat forward (section D):
+ *      iso_meshraster_count  : tile_cnt (N*T*T i32, zero on entry, T = iso_splat_tiles_per_side(S)) += faces whose clamped
+ *                               bounding box touches the 16x16 tile; integer atomics only;
+ *      caller                 : iso_splat_tile_offsets(tile_cnt, tile_off, tile_cursor, N*T*T + 1), total = tile_off[N*T*T],
+ *                               allocate pairs (i32, >= total);
+ *      iso_meshraster_fill   : the same walk, face indices into pairs; the order inside a tile's list is arbitrary and the
+ *                               result does not depend on it;
+ *      iso_meshraster_pixels : one 256-lane workgroup per tile, one pixel per lane, the tile's faces staged through LDS
+ *                               256 at a time, the K nearest (pz, id) of the pixel in registers.  Compiled for K = 1, 4
+ *                               and 8 (iso_meshraster_form); another K runs on the next form up and writes its first K.
+ *    Refused with an error code, nothing launched: K outside 1..8, S < 1, N * S * S * K >= 2^31, F >= 2^31, negative
+ *    sizes, null pointers where work exists.  N = 0, F = 0 and meshes without faces are not errors (pixels hold -1).
+ *    (The entries are iso_meshraster_*, in one word: the prefix iso_mesh_ is section I's, the mesh sampler's.)        */
+int iso_meshraster_form(int faces_per_pixel);
+int iso_meshraster_count(const float* face_verts, const int64_t* first_idx, const int64_t* num_faces, int n_meshes,
+                          int64_t n_faces, int image_size, int cull_backfaces, int32_t* tile_cnt, void* stream);
+int iso_meshraster_fill(const float* face_verts, const int64_t* first_idx, const int64_t* num_faces, int n_meshes,
+                         int64_t n_faces, int image_size, int cull_backfaces, int32_t* tile_cursor, const int32_t* tile_off,
+                         int32_t* pairs, int64_t pair_capacity, void* stream);
+int iso_meshraster_pixels(const float* face_verts, int n_meshes, int64_t n_faces, int image_size, int faces_per_pixel,
+                           int perspective_correct, const int32_t* tile_off, const int32_t* pairs, int64_t pair_capacity,
+                           int64_t* pix_to_face, float* zbuf, float* bary, float* dists, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -179,6 +179,10 @@ SIGNATURES = {
     "iso_disk_rounds": (_I, [_P, _P, _P, _P, _I, _L, _L, _I, _I, _P, _P, _L, _P]),
     "iso_disk_select": (_I, [_I, _L, _L, _P, _P, _P, _P, _L, _P]),
     "iso_disk_area_radius": (_I, [_P, _P, _P, _I, _L, _L, _P, _P]),
+    "iso_meshraster_form": (_I, [_I]),
+    "iso_meshraster_count": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P]),
+    "iso_meshraster_fill": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _L, _P]),
+    "iso_meshraster_pixels": (_I, [_P, _I, _L, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P]),
 }
 
 class Follow(ctypes.Structure):

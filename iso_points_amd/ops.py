@@ -17,6 +17,8 @@ import torch
 
 from . import _lib
 from .loss import _on_gpu, _packed_mesh
+from .mesh_raster import (Fragments, MeshRasterizer, RasterizationSettings, hard_flat_shading,  # noqa: F401
+                          rasterize_meshes, render_views)
 
 _ROW_LIMIT = 2 ** 31
 
