@@ -16,6 +16,8 @@
 //   iso_splat_band_return   the band's per-record results of the backward pass (fixed-point z sum, visible flag)
 //                           back into the slots the records arrived in; the reverse all-to-all; the owner adds them
 //                           to its rows (iso_splat_band_merge) -- integer adds: order-independent.
+//   iso_splat_repack        the all-gather form of the exchange: every rank's whole block of front-end rows -> the
+//                           global packed rows (at the end of this file).
 //
 // Nothing here reads a size on the host: capacities are fixed (cap_pair records per ordered pair of ranks), counts
 // travel in the headers, an overflow sets a flag the caller checks when convenient.
@@ -40,7 +42,7 @@ __device__ __forceinline__ void band_of(int d, int world, int ty, int& b, int& e
   e = b + base + (d < rem ? 1 : 0);
 }
 
-// bit d set: band d lists this row (the binning pass's test: splat.hip k_bin_lds)
+// bit d set: band d lists this row (the binning pass's test: splat_raster.hip k_bin_lds)
 __device__ __forceinline__ unsigned long long band_mask(float x, float y, float z, float rx, float ry, const Frame& F, int world) {
   if (!(z >= 0.f)) return 0ull;
   int x0, x1, y0, y1;
@@ -459,5 +461,78 @@ extern "C" int iso_splat_band_merge(const int64_t* back, const int32_t* sent_row
                      reinterpret_cast<const long long*>(back), sent_row, seg_base, n_views, cap_pair,
                      reinterpret_cast<long long*>(acc_own), vis_own);
   ISO_CHECK_LAUNCH("iso_splat_band_merge");
+  return ISO_OK;
+}
+
+namespace {
+
+// packed global rows (view-major, then rank, then the rank's own order) from the all-gathered per-rank
+// blocks: block s = 12 arrays of `cap` rows (ndc 3, ellipse 3, radii 2, scaler 1, features 3) as written
+// by iso_splat_front into one buffer; counts (world, 8) = the ranks' num_points per view.
+__global__ __launch_bounds__(256) void k_repack_records(const float* __restrict__ gathered, int64_t cap, int world,
+                                                        int n_views, const int32_t* __restrict__ counts, float cutoffC,
+                                                        int64_t max_rows, float* __restrict__ ndc, float* __restrict__ ellipse,
+                                                        float* __restrict__ cutoff, float* __restrict__ radii,
+                                                        float* __restrict__ scaler, float* __restrict__ feat) {
+  const int s = blockIdx.y, v = blockIdx.z;
+  int64_t g0 = 0, l0 = 0;                       // first global row of (v, s); first local row of view v in block s
+  for (int vv = 0; vv < n_views; ++vv)
+    for (int ss = 0; ss < world; ++ss) {
+      const int c = counts[ss * 8 + vv];
+      if (vv < v || (vv == v && ss < s)) g0 += c;
+      if (ss == s && vv < v) l0 += c;
+    }
+  int64_t n = counts[s * 8 + v];
+  if (l0 + n > cap) n = cap > l0 ? cap - l0 : 0;      // the sender's buffer overflowed (flagged by the host side)
+  if (g0 + n > max_rows) n = max_rows > g0 ? max_rows - g0 : 0;   // ... and so the packed arrays would
+  const float* blk = gathered + (int64_t)s * 12 * cap;
+  // every field of the (view, rank) block is one contiguous run in both layouts: flat, coalesced copies
+  const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, step = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t j = t0; j < 3 * n; j += step) {
+    ndc[g0 * 3 + j] = blk[l0 * 3 + j];
+    ellipse[g0 * 3 + j] = blk[3 * cap + l0 * 3 + j];
+    feat[g0 * 3 + j] = blk[9 * cap + l0 * 3 + j];
+  }
+  for (int64_t j = t0; j < 2 * n; j += step) radii[g0 * 2 + j] = blk[6 * cap + l0 * 2 + j];
+  for (int64_t j = t0; j < n; j += step) {
+    scaler[g0 + j] = blk[8 * cap + l0 + j];
+    cutoff[g0 + j] = cutoffC;
+  }
+}
+
+// first_idx / num_points of the global packed layout and of this rank's own rows in it
+__global__ void k_repack_offsets(const int32_t* __restrict__ counts, int world, int n_views, int rank, int64_t max_rows,
+                                 int64_t* __restrict__ first_g, int64_t* __restrict__ num_g,
+                                 int64_t* __restrict__ first_own, int64_t* __restrict__ num_own) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  int64_t run = 0;
+  for (int v = 0; v < n_views; ++v) {
+    first_g[v] = run < max_rows ? run : max_rows;
+    for (int s = 0; s < world; ++s) {
+      const int64_t c = counts[s * 8 + v];
+      if (s == rank) { first_own[v] = run < max_rows ? run : max_rows; num_own[v] = run + c <= max_rows ? c : (max_rows > run ? max_rows - run : 0); }
+      run += c;
+    }
+    num_g[v] = (run < max_rows ? run : max_rows) - first_g[v];      // rows beyond max_rows do not exist (overflow: flagged)
+  }
+}
+}  // namespace
+
+extern "C" int iso_splat_repack(const float* gathered, int64_t capacity, int world, int rank, int n_views,
+                                const int32_t* counts, float cutoff, int64_t max_rows, float* ndc_out,
+                                float* ellipse_out, float* cutoff_out, float* radii_out, float* scaler_out,
+                                float* features_out, int64_t* first_idx_out, int64_t* num_pts_out,
+                                int64_t* own_first_out, int64_t* own_num_out, void* stream) {
+  ISO_REQUIRE(gathered && counts && world >= 1 && rank >= 0 && rank < world && n_views >= 1 && n_views <= 8 &&
+                  capacity >= 0 && ndc_out && ellipse_out && cutoff_out && radii_out && scaler_out && features_out &&
+                  first_idx_out && num_pts_out && own_first_out && own_num_out,
+              ISO_ERR_INVALID, "iso_splat_repack: bad arguments");
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(k_repack_offsets, dim3(1), dim3(64), 0, s, counts, world, n_views, rank, max_rows, first_idx_out,
+                     num_pts_out, own_first_out, own_num_out);
+  int gx = iso_div_up(max_rows > 0 ? 3 * max_rows / (world * n_views) + 1 : 1, 256); if (gx > 256) gx = 256;
+  hipLaunchKernelGGL(k_repack_records, dim3(gx, world, n_views), dim3(256), 0, s, gathered, capacity, world, n_views, counts,
+                     cutoff, max_rows, ndc_out, ellipse_out, cutoff_out, radii_out, scaler_out, features_out);
+  ISO_CHECK_LAUNCH("iso_splat_repack");
   return ISO_OK;
 }

@@ -2,8 +2,9 @@
 // (negative) squared distance to the face's outline -- pytorch3d.renderer.mesh.rasterize_meshes at blur_radius = 0, the
 // only way the reference calls it (include/isopoints.h section M has the rule and the call sites).
 //
-// The splat raster's skeleton (splat.hip) with another inside test: faces are binned into 16x16-pixel tiles by a
-// count -> iso_splat_tile_offsets -> fill counting sort over their clamped bounding boxes (integer atomics only), and one
+// The splat raster's skeleton (splat_raster.hip) and its K-best list (kbest.h) with another inside test: faces are
+// binned into 16x16-pixel tiles by a count -> iso_splat_tile_offsets -> fill counting sort over their clamped bounding
+// boxes (integer atomics only), and one
 // 256-lane workgroup per tile streams the tile's face list through LDS in 256-face chunks -- every lane reads the same
 // LDS words, a broadcast -- while each lane keeps the K nearest (pz, face) pairs of its own pixel in registers.  The
 // order of a tile's list is whatever the fill's atomics made it; the K-best rule is the total order (pz, face index), so
@@ -19,6 +20,7 @@
 //     face's vertices in the epilogue -- the same instructions on the same operands.
 #include <float.h>
 #include "iso_common.h"
+#include "kbest.h"
 
 #pragma clang fp contract(off)
 
@@ -101,35 +103,6 @@ __global__ __launch_bounds__(256) void k_mesh_bin(const float* __restrict__ face
   }
 }
 
-// ---------------------------------------------------------------- the K nearest (pz, id) of a pixel
-// PixK::push_zi of splat.hip: depths are >= +0 and never NaN, so their float order is the order of their bit patterns as
-// unsigned integers; three integer compares per level whose masks go straight into the selects.
-template <int KMAX>
-struct FaceK {
-  float z[KMAX];
-  int id[KMAX];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) { z[j] = FLT_MAX; id[j] = 0x7fffffff; }
-  }
-  __device__ __forceinline__ void push_zi(float cz, int ci) {
-    const unsigned cu = __float_as_uint(cz);
-    bool m[KMAX];
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) {
-      const unsigned zu = __float_as_uint(z[j]);
-      m[j] = (cu < zu) | ((cu == zu) & (ci < id[j]));
-    }
-#pragma unroll
-    for (int j = KMAX - 1; j >= 1; --j) {
-      z[j] = m[j - 1] ? z[j - 1] : (m[j] ? cz : z[j]);
-      id[j] = m[j - 1] ? id[j - 1] : (m[j] ? ci : id[j]);
-    }
-    z[0] = m[0] ? cz : z[0];
-    id[0] = m[0] ? ci : id[0];
-  }
-};
-
 // w -> b -> pz of an inside pixel (e_i the edge functions, already of the area's sign).  false: the pair is skipped.
 __device__ __forceinline__ bool pair_depth(float e0, float e1, float e2, float area, float z0, float z1, float z2, int persp,
                                            float& b0, float& b1, float& b2, float& pz) {
@@ -174,7 +147,7 @@ __global__ __launch_bounds__(256) void k_mesh_raster(const float* __restrict__ f
   const int c = tx * MTILE + lx, r = ty * MTILE + ly;
   const bool in_image = c < S && r < S;
   const float px = pix_centre(c, S), py = pix_centre(r, S);
-  FaceK<KMAX> best;
+  KBest<KMAX, false> best;           // the K nearest (pz, face): depths are >= +0 and never NaN (pair_depth, then + 0.0f)
   best.init();
   const int64_t off = tile_off[tile];
   int cnt = tile_off[tile + 1] - tile_off[tile];
@@ -211,9 +184,9 @@ __global__ __launch_bounds__(256) void k_mesh_raster(const float* __restrict__ f
         const float4 z = s_z[k];
         float b0, b1, b2, pz;
         if (!pair_depth(e0, e1, e2, area, z.x, z.y, z.z, persp, b0, b1, b2, pz)) continue;
-        pz += 0.0f;                                    // -0 -> +0: push_zi orders depths by their bit patterns
+        pz += 0.0f;                                    // -0 -> +0: push_masked orders depths by their bit patterns
         const int id = __float_as_int(b.w);
-        if (pz < best.z[KMAX - 1] || (pz == best.z[KMAX - 1] && id < best.id[KMAX - 1])) best.push_zi(pz, id);
+        if (pz < best.z[KMAX - 1] || (pz == best.z[KMAX - 1] && id < best.id[KMAX - 1])) best.push_masked(pz, id, KMAX);
       }
     }
   }

@@ -1,4 +1,5 @@
-// Image frame, tile size and the pixel range of a splat's bounding box: shared by the raster pipeline (splat.hip)
+// Image frame, tile size and the pixel range of a splat's bounding box: shared by the raster pipeline (splat_raster.hip,
+// splat_bins.hip and splat_backward.hip)
 // and the band exchange of the N-rank path (band.hip) -- a record is sent to a band exactly when the binning pass of
 // that band would list it.
 #pragma once

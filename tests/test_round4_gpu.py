@@ -233,6 +233,44 @@ def test_rasterize_fine_of_coarse_is_splat_points(dev, S, bin_size, P, K):
         _C._rasterize_coarse(pts, rad, first, num, S, bin_size, 3)
 
 
+@pytest.mark.parametrize("N", [1, 2])
+def test_deep_list_render_is_forward_composite_and_mark(dev, N):
+    """points_per_pixel = 40 (above 32: k_raster_deep, the lists live in the output rows) with compositing and visible
+    marking: iso_splat_render_visible -- raster, image and flags in one kernel -- against iso_splat_forward, then
+    iso_splat_composite, then iso_splat_mark_visible, bit for bit (the fused epilogue performs the same operations in
+    the same order).  The sizes of the coarse / fine case above."""
+    from iso_points_amd import _lib
+    from iso_points_amd.rasterizer import PointFragments, _C, composite
+    from splat_util import random_splats
+    S, P, K = 48, 4000, 40
+    sc = random_splats(P, N=N, seed=S + P + N)
+    args = [sc[k].to(dev) for k in ("ndc", "ellipse", "cutoff", "radii", "first", "num")]
+    g = torch.Generator().manual_seed(N)
+    scal = (torch.rand(P, generator=g) + 0.1).to(dev)
+    feat = torch.rand(P, 3, generator=g).to(dev)
+    depth = {}
+    # depths span 3.3: the usual threshold cuts most of a list (dropped slots become -1), the wide one cuts nothing
+    for thres in (0.05, 5.0):
+        ref = _C.splat_points(*args, thres, S, K)
+        idx = ref[0]
+        assert idx.shape == (N, S, S, K)
+        depth[thres] = (idx >= 0).sum(-1)
+        vis_ref = torch.zeros((P,), dtype=torch.uint8, device=dev)
+        _lib.call("iso_splat_mark_visible", _lib.ptr(idx), N * S * S, K, _lib.ptr(vis_ref), _lib.stream())
+        assert 0 < int(vis_ref.sum()) < P
+        for norm in (True, False):
+            vis = torch.zeros((P,), dtype=torch.uint8, device=dev)
+            got = _C.splat_points(*args, thres, S, K, composite_with=(scal, feat, norm, 1e-4), mark_visible=vis)
+            for a, b, name in zip(got[:4], ref, ("idx", "zbuf", "qvalue", "occupancy")):
+                assert torch.equal(a, b), name
+            want = composite(PointFragments(ref[0], ref[1], ref[2], None, ref[3]), scal, feat, norm_weighted=norm)
+            assert torch.equal(got[4], want), "image, norm_weighted=%s" % norm
+            assert torch.equal(vis, vis_ref), "visible flags"
+    # the case is not trivial: ~3 (two clouds) or ~6 splats cover a pixel on average, so some list is several deep, and
+    # the cut removes entries
+    assert int(depth[5.0].max()) > 4 and bool((depth[0.05] < depth[5.0]).any())
+
+
 def _h_fused_vs_standalone(dev, pts, nrm, n_views, cell_scale=None, image_size=64):
     """splat_h_fused against the K = 7 query of each filtered view cloud + vrk_h (rasterizer.py:256-300 of the
     reference); returns the grid header."""
