@@ -112,6 +112,15 @@ int iso_siren_set_tail_from(int first_tail_iteration);
  * the default.  Results do not depend on it. */
 int iso_siren_set_drawn_tiles(int on);
 int iso_idr_set_drawn_tiles(int on);
+/* Form of the split-fp16 gradient step at hidden size 256.  1 (the default): four waves per workgroup, one per SIMD with
+ * 512 registers each, the derivative stash of the reverse sweep held in LDS and registers -- for n_hidden 2 and 3; every
+ * other shape, forward-only evaluation, latent-coded networks (iso_*_siren_coded) and the f32 mode keep their kernels.  0: eight waves, the stash in global memory
+ * (the workspace keeps room for it either way).  Results do not depend on it, bit for bit.
+ * iso_siren_step_form_used: the form that serves a gradient step of this shape (coded != 0: of a coded network) as
+ * things are set now. */
+int iso_siren_set_step_form(int form);
+int iso_siren_get_step_form(void);
+int iso_siren_step_form_used(int hidden, int n_hidden, int coded);
 /* step-kernel launches one iso_project_siren call with these arguments issues (max_iters + 1 without the tail) */
 int iso_siren_step_launches(int hidden, int n_hidden, int max_iters);
 /* scratch for the per-wave activation-derivative stash */

@@ -368,6 +368,21 @@ extern "C" int iso_siren_set_drawn_tiles(int on) {
   return ISO_OK;
 }
 
+// Form of the split-fp16 gradient step at hidden size 256 (siren_x3.hip): 0 = eight waves per workgroup, the derivative
+// stash in global memory; 1 (the default) = four waves of 512 registers, the stash in LDS and registers, for two and
+// three hidden layers -- other shapes, forward-only calls, latent-coded networks and the f32 mode keep their kernels.
+// Results do not depend on it.
+extern "C" int iso_siren_set_step_form(int form) {
+  ISO_REQUIRE(form == 0 || form == 1, ISO_ERR_INVALID, "iso_siren_set_step_form: 0 (eight waves, global stash) or 1 (four waves, stash on chip)");
+  siren_x3_set_step_form(form);
+  return ISO_OK;
+}
+extern "C" int iso_siren_get_step_form(void) { return siren_x3_get_step_form(); }
+// the form that serves a gradient step of this shape as things are set now (0 also where the split-fp16 kernels do not run)
+extern "C" int iso_siren_step_form_used(int hidden, int n_hidden, int coded) {
+  return use_x3(hidden, n_hidden) && siren_x3_on_chip(hidden, n_hidden, false, coded != 0) ? 1 : 0;
+}
+
 // One evaluation of a list whose length only the device knows: for the H = 256 gradient kernels the list is cut at
 // siren_split_point into 96-point and 32-point tiles, both served by one launch of k_siren_step_x3_both (per-point
 // results do not depend on the tile shape); everything else is one launch of one shape.

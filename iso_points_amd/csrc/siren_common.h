@@ -114,6 +114,10 @@ bool siren_x3_supported(int H, int L);
 int64_t siren_x3_stash_floats(int H, int L);
 void siren_x3_pack(const float* raw, float* packed, int H, int L, hipStream_t s);
 int siren_x3_launch(const SirenCodedArgs& a, int H, int64_t n_upper, hipStream_t s);
+// step form of the H = 256 gradient kernels: 0 = eight waves, global derivative stash; 1 = four waves, stash on chip
+void siren_x3_set_step_form(int form);
+int siren_x3_get_step_form();
+bool siren_x3_on_chip(int H, int L, bool fwd_only, bool coded);           // does form 1 serve this call (as set now)?
 int siren_x3_tail_blocks();                                               // workgroups of the Newton-tail launch
 int siren_x3_launch_tail(const SirenCodedArgs& a, int H, hipStream_t s);  // H = 256 only
 // ---- the point-stationary form of the H = 256 step (tools/experiments/siren_ps, not part of this library) -------

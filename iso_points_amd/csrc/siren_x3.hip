@@ -33,6 +33,9 @@
 //     time (shapes with more than 8 groups per lane park them in LDS first).
 //   * reverse sweep: same GEMM on the transposed image; w*cos(w z) comes back from the
 //     per-lane global stash (written in the forward sweep by the same lane).
+//   * the on-chip form (x3_step_body with LT > 0; iso_siren_set_step_form, the default for H = 256 with two or three
+//     hidden layers): four waves, one per SIMD with 512 registers, two output tiles each; the layers are expanded at
+//     compile time and the stash is LDS + a register array -- nothing of it leaves the CU.  Bit-identical results.
 #include <stdlib.h>
 #include <type_traits>
 #include "siren_common.h"
@@ -169,7 +172,10 @@ __global__ void k_siren_pack_f16(const float* __restrict__ raw, float* __restric
 }
 
 // ---- the step kernel -------------------------------------------------------------------------
-template <int H, int NW, int NB>
+// RP: head / gradient partial sums a wave hands to the final reduction.  RP > 1 is the on-chip form of four waves: one
+// partial per 32-feature output tile, as the eight-wave form has them; there the `red` region holds the exchange of the
+// adjoint maxima only, and the final reduction goes through the LDS part of the stash, which is dead by then.
+template <int H, int NW, int NB, int RP = 1>
 struct X3Shape {
   static constexpr int NS = H / 16;        // K-steps of a hidden layer
   static constexpr int NTO = H / 32;       // output tiles
@@ -178,7 +184,7 @@ struct X3Shape {
   static constexpr int NG = SL * NB;       // 8-value groups per lane
   static constexpr int P = 32 * NB;        // points per workgroup
   static constexpr size_t kActBytes = (size_t)NS * NB * kAP * 1024;
-  static constexpr size_t kRedBytes = (size_t)NW * P * 16;
+  static constexpr size_t kRedBytes = RP > 1 ? (size_t)2 * P * NW * 4 : (size_t)NW * P * 16;
   static constexpr size_t kPtsBytes = (size_t)P * 16;                 // the tile's points, for the reverse sweep's layer 0
   // LDS-resident part of the derivative stash: the first LG of the NG groups per lane of stash slot 0 (written by
   // hidden layer 0, read back last of all by reverse stage 1 -- the longest-lived slot) stay in the CU; 2 KiB per
@@ -190,6 +196,7 @@ struct X3Shape {
   // consumed on the spot): L - 1 slots in use, one kept for L = 1
   static constexpr int64_t kStashPerWg(int L) { return (int64_t)NW * (L > 1 ? L : 1) * NG * 512; }  // floats
   static_assert(NTO % NW == 0 && TW >= 1, "features must split evenly over the waves");
+  static_assert(RP == 1 || (size_t)NW * LG * 2048 >= (size_t)NW * RP * P * 16, "the final reduction fits the LDS stash");
 };
 
 // the layer-0 biases of K-step s for lane half h (features x3_feat(s, 8h + e), e = 0..7: 16 s + 8 (e >> 2) + 4h + (e & 3))
@@ -208,10 +215,20 @@ __device__ __forceinline__ void x3_code_bias8(const float* table, int row, int s
 // CODED: layer 0's bias is row code_of[idx] of the per-code table a.code_bias (SirenCodedArgs, natural feature order) instead of
 // the .w slot of the W0 image, in the forward sweep and where reverse stage 0 forms z0 again; the expression is the same,
 // so a coded evaluation equals the uncoded one of the network whose b0 is that row, bit for bit
-template <int H, int NW, int NB, bool FWD, bool CODED>
+// LT > 0: the ON-CHIP form (iso_siren_set_step_form; gradient kernels of LT hidden layers, a.L == LT).  The layer loops
+// are expanded with the layer a compile-time constant, so every stash index is static and the part of the derivative
+// stash that does not fit LDS is a register array from the forward activation that writes it to the reverse stage that
+// reads it: no global stash access.  Built for four waves (one per SIMD, 512 registers each): a wave owns TW = 2 output
+// tiles and keeps the head / gradient partial sums of each apart (RP = TW), accumulated in the order the eight-wave
+// form uses for the wave that owns that tile alone, so the final reduction adds the same eight numbers in the same
+// order and a point's result is that of the eight-wave form bit for bit.
+template <int H, int NW, int NB, bool FWD, bool CODED, int LT = 0>
 __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::type& a, const int bid, const int nblk,
                                              const int sid) {
-  using S = X3Shape<H, NW, NB>;
+  constexpr bool RS = LT > 0;                        // register stash
+  constexpr int RP = RS ? (H / 32) / NW : 1;
+  static_assert(!RS || !FWD, "the on-chip form is a gradient kernel");
+  using S = X3Shape<H, NW, NB, RP>;
   constexpr int NS = S::NS, NTO = S::NTO, TW = S::TW, SL = S::SL, NG = S::NG, P = S::P;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   u32x4* act = reinterpret_cast<u32x4*>(smem_raw);
@@ -230,8 +247,8 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
   // be scheduled between the MFMAs (tools/siren_stress.py: every repeat differs; the same source
   // with one workgroup per CU, and the 8-wave H = 256 build over 60 chaotic-weight repeats, are
   // bit-stable).  Cause not found yet, so that shape keeps the loads in front of the MFMA block.
-  constexpr bool IL = (NW == 8);
-  const int L = a.L;
+  constexpr bool IL = (NW == 8) || RS;     // (RS: one workgroup per CU)
+  const int L = RS ? LT : a.L;
   const float* X = a.packed + x3_base(H, L);
   // wave-uniform bases (SGPRs) + small per-lane offsets: no 64-bit per-lane pointers are kept live
   const f32x4* W0u = reinterpret_cast<const f32x4*>(X) + SL * w * 16;       // + h*8 + ...
@@ -241,6 +258,9 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
   f32x4* stash = reinterpret_cast<f32x4*>(a.stash) +
                  ((int64_t)sid * NW + w) * (int64_t)(L > 1 ? L : 1) * NG * 128;   // + lane
   f32x4* lst = reinterpret_cast<f32x4*>(smem_raw + S::kActBytes + S::kRedBytes + S::kPtsBytes) + w * (LG * 128) + lane;
+  // [NW * RP][P] partial sums of the final reduction.  RS: in the LDS stash -- last read by reverse stage 1, before the
+  // barrier that ends it; written again by hidden layer 0 of the next tile, two barriers after the epilogue that reads this.
+  f32x4* redf = RS ? reinterpret_cast<f32x4*>(smem_raw + S::kActBytes + S::kRedBytes + S::kPtsBytes) : red;
 
   // weight images of this wave: forward / transposed image of hidden layer l (two fp16 parts)
   constexpr int FP = 2, BP = 2;
@@ -259,6 +279,14 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
       const float m = __builtin_fmaxf(amax[n], __shfl_xor(amax[n], 32));
       if (h == 0) redm[(buf * P + 32 * n + j) * NW + w] = m;
     }
+  };
+  // RS: the lane offset of a GEMM stage's operand addresses, opaque per stage.  With the layers expanded every weight
+  // address is invariant over the tile loop; left visible, lane + image + K-step offsets are hoisted out of it as
+  // 64-bit per-lane pointers, one pair of registers per K-step and image, and spilled.
+  auto stage_lane = [&]() __attribute__((always_inline)) {
+    int v = lane;
+    if constexpr (RS) asm volatile("" : "+v"(v));
+    return v;
   };
   u32x4 A[4][TW][3];                     // weight-fragment pipeline, carried across stages
   x3_prefetch_a<kAD, TW, NTO, FP>(A, fwd_img(0), 0, lane);
@@ -372,21 +400,27 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
     __syncthreads();
 
     f32x16 acc[TW][NB];
-    float fpart[NB];
+    // RS: slots 0 .. LT-2 of the derivative stash, the groups that are not in LDS (static indices only: registers)
+    f32x4 rst[RS && LT > 1 ? LT - 1 : 1][RS ? NG : 1][2];
+    float fpart[RP][NB];
 #pragma unroll
-    for (int n = 0; n < NB; ++n) fpart[n] = 0.f;
+    for (int r = 0; r < RP; ++r)
+#pragma unroll
+      for (int n = 0; n < NB; ++n) fpart[r][n] = 0.f;
     // ---- hidden layers, forward --------------------------------------------------------------
-    for (int l = 0; l < L; ++l) {
+    auto fwd_layer = [&](auto lc) __attribute__((always_inline)) {
+      const int l = lc;                     // (an integral_constant in the on-chip form)
+      const int gl = stage_lane();
       const float* lay = a.packed + x3_off_layer(H, L, l);
       const u32x4* img = fwd_img(l);
       const float zscale = fwd_scale(l);             // the accumulators hold zscale * (W h + b)
       const float w_in = a.wh / zscale;              // exact: zscale is a power of two
       if (l + 1 < L || FWD) {
         // the next stage is a forward one again (layer l+1, or layer 0 of the next tile)
-        gemm_x3<kAD, TW, NB, NTO, NS, kBias, IL, FP, FP>(img, lay, act + lane, acc, w, 0, A,
-                                                         l + 1 < L ? fwd_img(l + 1) : fwd_img(0), 0, lane, zscale);
+        gemm_x3<kAD, TW, NB, NTO, NS, kBias, IL, FP, FP>(img, lay, act + gl, acc, w, 0, A,
+                                                         l + 1 < L ? fwd_img(l + 1) : fwd_img(0), 0, gl, zscale);
       } else {
-        gemm_x3<kAD, TW, NB, NTO, NS, kBias, IL, FP, BP>(img, lay, act + lane, acc, w, 0, A, rev_img(L - 1), 0, lane,
+        gemm_x3<kAD, TW, NB, NTO, NS, kBias, IL, FP, BP>(img, lay, act + gl, acc, w, 0, A, rev_img(L - 1), 0, gl,
                                                          zscale);
       }
       __syncthreads();                      // both teams have read this team's K-half
@@ -410,6 +444,9 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
           const float f0 = (wl0.x * hv[0] + wl0.y * hv[1]) + (wl0.z * hv[2] + wl0.w * hv[3]);
           const float f1 = (wl1.x * hv[4] + wl1.y * hv[5]) + (wl1.z * hv[6] + wl1.w * hv[7]);
           fp += f0 + f1;
+          // (RS: with the layers expanded the sum has one use, far below, and would be sunk there with the operands of
+          // all its groups kept live: 150 registers)
+          if constexpr (RS) asm volatile("" : "+v"(fp));
           if constexpr (FWD) return;
 #pragma unroll
           for (int e = 0; e < 4; ++e) { hv[e] = wl0[e] * sv[e]; hv[4 + e] = wl1[e] * sv[4 + e]; }
@@ -426,6 +463,11 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
             if (k < LG && lds_slot) {
               lst[(k * 2 + 0) * 64] = (f32x4){sv[0], sv[1], sv[2], sv[3]};
               lst[(k * 2 + 1) * 64] = (f32x4){sv[4], sv[5], sv[6], sv[7]};
+            } else if constexpr (RS) {
+              if constexpr (LT > 1) {
+                rst[l < LT - 1 ? l : 0][k][0] = (f32x4){sv[0], sv[1], sv[2], sv[3]};
+                rst[l < LT - 1 ? l : 0][k][1] = (f32x4){sv[4], sv[5], sv[6], sv[7]};
+              }
             } else {
               st_l[(k * 2 + 0) * 64 + lane] = (f32x4){sv[0], sv[1], sv[2], sv[3]};
               st_l[(k * 2 + 1) * 64 + lane] = (f32x4){sv[4], sv[5], sv[6], sv[7]};
@@ -436,8 +478,8 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
         split8_f16(hv, p0, p1);
         own[(k * kAP + 0) * 64] = p0; own[(k * kAP + 1) * 64] = p1;
       };
-      if constexpr (NG <= 8) {
-        // few enough values per lane to walk the accumulators with static indices
+      if constexpr (NG <= 8 || RS) {
+        // few enough values per lane to walk the accumulators with static indices (RS: 12 groups, and registers for them)
 #pragma unroll
         for (int t = 0; t < TW; ++t)
 #pragma unroll
@@ -447,7 +489,7 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
               float zz[8];
 #pragma unroll
               for (int e = 0; e < 8; ++e) zz[e] = acc[t][n][8 * p + e];
-              act_group((2 * t + p) * NB + n, n, 2 * t + p, zz, fpart[n]);
+              act_group((2 * t + p) * NB + n, n, 2 * t + p, zz, fpart[RS ? t : 0][n]);
               __builtin_amdgcn_sched_barrier(0);     // one group at a time: bounds register pressure
             }
       } else {
@@ -476,17 +518,27 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
             float zz[8];
 #pragma unroll
             for (int e = 0; e < 8; ++e) zz[e] = z[n][e >> 2][e & 3];
-            act_group(sl * NB + n, n, sl, zz, fpart[n]);
+            act_group(sl * NB + n, n, sl, zz, fpart[0][n]);
           }
         }
       }
       if constexpr (!FWD) { if (top) put_amax(0); }
       __syncthreads();                      // the next layer's inputs are complete
+    };
+    if constexpr (RS) {
+      static_assert(LT <= 3, "layers are expanded by hand");
+      fwd_layer(std::integral_constant<int, 0>());
+      if constexpr (LT > 1) fwd_layer(std::integral_constant<int, 1>());
+      if constexpr (LT > 2) fwd_layer(std::integral_constant<int, 2>());
+    } else {
+      for (int l = 0; l < L; ++l) fwd_layer(l);
     }
     // ---- hidden layers, reverse --------------------------------------------------------------
-    float gx[NB], gy[NB], gz[NB];
+    float gx[RP][NB], gy[RP][NB], gz[RP][NB];
 #pragma unroll
-    for (int n = 0; n < NB; ++n) gx[n] = gy[n] = gz[n] = 0.f;
+    for (int r = 0; r < RP; ++r)
+#pragma unroll
+      for (int n = 0; n < NB; ++n) gx[r][n] = gy[r][n] = gz[r][n] = 0.f;
     int mbuf = 0;                             // exchange buffer that holds max |a_l| of the adjoint in LDS
     // max_k |a_l[k][p]| of this lane's points (written before the barrier that ended the last stage)
     auto get_amax = [&](float (&Mp)[NB]) {
@@ -499,7 +551,9 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
       }
     };
     // stages l = L-1 .. 1: a_{l-1} = (W_l^T a_l) * w cos(w z_{l-1}), the derivative from the stash
-    for (int l = FWD ? 0 : L - 1; l >= 1; --l) {
+    auto rev_stage = [&](auto lc) __attribute__((always_inline)) {
+      const int l = lc;
+      const int gl = stage_lane();
       const u32x4* img = rev_img(l);
       const f32x4* st_l = stash + (int64_t)(l - 1) * NG * 128;      // reverse stage l reads slot l - 1
       f32x4 sv[NG][2];
@@ -508,6 +562,8 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
         for (int k = 0; k < NG; ++k) {
           if (k < LG && l == 1) {
             sv[k][0] = lst[(k * 2) * 64]; sv[k][1] = lst[(k * 2 + 1) * 64];
+          } else if constexpr (RS) {
+            if constexpr (LT > 1) { sv[k][0] = rst[l - 1 < LT - 1 ? l - 1 : 0][k][0]; sv[k][1] = rst[l - 1 < LT - 1 ? l - 1 : 0][k][1]; }
           } else {
             sv[k][0] = st_l[(k * 2) * 64 + lane]; sv[k][1] = st_l[(k * 2 + 1) * 64 + lane];
           }
@@ -515,7 +571,7 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
       };
       float Mp[NB];
       get_amax(Mp);
-      gemm_x3<kAD, TW, NB, NTO, NS, kZero, IL, BP, BP>(img, nullptr, act + lane, acc, w, 0, A, rev_img(l - 1), 0, lane);
+      gemm_x3<kAD, TW, NB, NTO, NS, kZero, IL, BP, BP>(img, nullptr, act + gl, acc, w, 0, A, rev_img(l - 1), 0, gl);
       ld_stash();                             // w cos(w z) of the layer below
       __syncthreads();
       // split-fp16 reverse: the accumulators hold 2^s_l * bscale[p] * (W_l^T a_l); the scale comes out
@@ -548,6 +604,7 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
             u32x4 p0, p1;
             split8_f16(av, p0, p1, nscale[n]);
             own[(k * kAP + 0) * 64] = p0; own[(k * kAP + 1) * 64] = p1;
+            if constexpr (RS) __builtin_amdgcn_sched_barrier(0);     // one group at a time, as in the forward walk
           }
         }
 #pragma unroll
@@ -555,13 +612,20 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
       put_amax(mbuf ^ 1);
       mbuf ^= 1;
       __syncthreads();
+    };
+    if constexpr (RS) {
+      if constexpr (LT > 2) rev_stage(std::integral_constant<int, 2>());
+      if constexpr (LT > 1) rev_stage(std::integral_constant<int, 1>());
+    } else {
+      for (int l = FWD ? 0 : L - 1; l >= 1; --l) rev_stage(l);
     }
     // stage 0: d sdf / d x = W_0^T [ (W_1^T a_1) * w0 cos(w0 z_0) ] -- z_0 = W_0 x + b_0 is formed again from the point
     // (three FMAs; the same expression on the same operands as in the forward sweep) instead of being stashed
     if constexpr (!FWD) {
+      const int gl = stage_lane();
       int drawn = 0;
       if (dyn && tid == 0) drawn = draw_base + atomicAdd(a.tile_ctr, 1);
-      gemm_x3<kAD, TW, NB, NTO, NS, kZero, IL, BP, FP>(rev_img(0), nullptr, act + lane, acc, w, 0, A, fwd_img(0), 0, lane);
+      gemm_x3<kAD, TW, NB, NTO, NS, kZero, IL, BP, FP>(rev_img(0), nullptr, act + gl, acc, w, 0, A, fwd_img(0), 0, gl);
       if (dyn && tid == 0) s_next_tile = drawn;
       __syncthreads();
       next_tile = dyn ? (int64_t)s_next_tile : tile + nblk;
@@ -598,9 +662,9 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
               const float av = (acc[t][n][8 * p + e] * inv[n]) * cv[e];
-              gx[n] += wv[e].x * av;
-              gy[n] += wv[e].y * av;
-              gz[n] += wv[e].z * av;
+              gx[RS ? t : 0][n] += wv[e].x * av;
+              gy[RS ? t : 0][n] += wv[e].y * av;
+              gz[RS ? t : 0][n] += wv[e].z * av;
             }
             __builtin_amdgcn_sched_barrier(0);     // one group at a time: bounds register pressure
           }
@@ -613,12 +677,14 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
     }
     // ---- reduce head + gradient over the lane halves and the waves -----------------------------
 #pragma unroll
+    for (int r = 0; r < RP; ++r)
+#pragma unroll
     for (int n = 0; n < NB; ++n) {
-      float f = fpart[n] + __shfl_xor(fpart[n], 32);
-      float x = gx[n] + __shfl_xor(gx[n], 32);
-      float y = gy[n] + __shfl_xor(gy[n], 32);
-      float z = gz[n] + __shfl_xor(gz[n], 32);
-      if (h == 0) red[w * P + 32 * n + j] = (f32x4){f, x, y, z};
+      float f = fpart[r][n] + __shfl_xor(fpart[r][n], 32);
+      float x = gx[r][n] + __shfl_xor(gx[r][n], 32);
+      float y = gy[r][n] + __shfl_xor(gy[r][n], 32);
+      float z = gz[r][n] + __shfl_xor(gz[r][n], 32);
+      if (h == 0) redf[(RP * w + r) * P + 32 * n + j] = (f32x4){f, x, y, z};
     }
     // (the thread / lane ids are made opaque here: everything derived from them -- LDS addresses,
     // the rank mask of the compaction -- is recomputed per tile instead of being kept live, and
@@ -642,10 +708,10 @@ __device__ __forceinline__ void x3_step_body(const typename SirenArgsOf<CODED>::
     {
       const int64_t slot = slot0 + tile * P + tid_e;
       if (tid_e < P && slot < count) {
-        f32x4 r = red[tid_e];
+        f32x4 r = redf[tid_e];
 #pragma unroll
-        for (int ww = 1; ww < NW; ++ww) {
-          const f32x4 q = red[ww * P + tid_e];
+        for (int ww = 1; ww < NW * RP; ++ww) {
+          const f32x4 q = redf[ww * P + tid_e];
           r.x += q.x; r.y += q.y; r.z += q.z; r.w += q.w;
         }
         const float f = r.x + bL;
@@ -709,6 +775,41 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(typename S
   }
 }
 
+// The on-chip form (x3_step_body, LT > 0) of the two kernels above: four waves, LT hidden layers, no global stash.
+// (Kernels of their own, not more parameters of the two above: those keep their names and their machine code.)
+constexpr int kOcNW = 4;
+template <int H, int NB, int MINB, bool CODED, int LT>
+__global__ __launch_bounds__(64 * kOcNW, MINB) void k_siren_step_x3_oc(typename SirenArgsOf<CODED>::type a) {
+  x3_step_body<H, kOcNW, NB, false, CODED, LT>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
+}
+// (k_siren_step_x3_both, without the stash regions; a function of its own taking the argument block by reference: written
+// into the kernel, the same text reserves 68 bytes of scratch per lane that no instruction uses)
+template <int H, int NB, bool CODED, int LT>
+__device__ __forceinline__ void x3_both_oc(const typename SirenArgsOf<CODED>::type& a) {
+  const bool big = (int)blockIdx.x < a.big_blocks;
+  const int small_blocks = (int)gridDim.x - a.big_blocks;
+  if (big) {
+    typename SirenArgsOf<CODED>::type b = a;
+    b.split = 1;
+    x3_step_body<H, kOcNW, NB, false, CODED, LT>(b, (int)blockIdx.x, a.big_blocks, (int)blockIdx.x);
+  }
+  if (!big || a.tile_ctr != nullptr) {
+    if (big) __syncthreads();
+    typename SirenArgsOf<CODED>::type b = a;
+    b.split = 2;
+    if (a.tile_ctr) b.tile_ctr = a.tile_ctr + 1;
+    const bool joint = a.tile_ctr != nullptr;
+    b.draw_first = joint ? 1 : 0;
+    const int bid = big ? small_blocks + (int)blockIdx.x : (int)blockIdx.x - a.big_blocks;
+    const int nblk = joint ? small_blocks + a.big_blocks : small_blocks;
+    x3_step_body<H, kOcNW, 1, false, CODED, LT>(b, bid, nblk, big ? 0 : bid);
+  }
+}
+template <int H, int NB, int MINB, bool CODED, int LT>
+__global__ __launch_bounds__(64 * kOcNW, MINB) void k_siren_step_x3_both_oc(typename SirenArgsOf<CODED>::type a) {
+  x3_both_oc<H, NB, CODED, LT>(a);
+}
+
 // The Newton tail in ONE launch (levelset_sampling.py:306-341: the reference leaves its loop when nothing is active; a
 // launch per iteration issued all T + 1 of them, the late ones for a few hundred points or none).  Iteration it_first
 // is taken from the list the previous launch left, dealt out tile by tile (32 points) as always; but a workgroup puts
@@ -748,38 +849,48 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_tail_x3(typename SirenA
   if (threadIdx.x == 0) { cnts[0] = 0; cnts[1] = 0; }
 }
 
-template <int H, int NW, int NB, int MINB, bool FWD, bool CODED>
+// LT > 0: the on-chip form of LT hidden layers (NW = kOcNW)
+template <int H, int NW, int NB, int MINB, bool FWD, bool CODED, int LT = 0>
 int launch_x3(const typename SirenArgsOf<CODED>::type& a, int64_t n_upper, hipStream_t s) {
-  using S = X3Shape<H, NW, NB>;
+  using S = X3Shape<H, NW, NB, (LT > 0 ? (H / 32) / NW : 1)>;
+  static_assert(LT == 0 || (NW == kOcNW && !FWD), "the on-chip form: four waves, gradient kernels");
+  static_assert(S::kLds <= 163840, "LDS of a gfx950 CU");
+  void (*kern)(typename SirenArgsOf<CODED>::type);
+  if constexpr (LT > 0) kern = &k_siren_step_x3_oc<H, NB, MINB, CODED, LT>;
+  else kern = &k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::kLds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::kLds);
     attr_done = true;
   }
   const int64_t tiles = (n_upper + S::P - 1) / S::P;
   const int64_t cap = 256 * MINB;
   const int blocks = (int)(tiles < cap ? (tiles < 1 ? 1 : tiles) : cap);
-  hipLaunchKernelGGL((k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>), dim3(blocks), dim3(64 * NW), S::kLds, s, a);
+  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NW), S::kLds, s, a);
   return 0;
 }
 
-template <int H, int NW, int NB, int MINB, bool CODED>
+template <int H, int NW, int NB, int MINB, bool CODED, int LT = 0>
 int launch_x3_both(typename SirenArgsOf<CODED>::type a, int64_t n_upper, hipStream_t s) {
-  using SB = X3Shape<H, NW, NB>;
-  using SS = X3Shape<H, NW, 1>;
+  constexpr int RP = LT > 0 ? (H / 32) / NW : 1;
+  using SB = X3Shape<H, NW, NB, RP>;
+  using SS = X3Shape<H, NW, 1, RP>;
+  static_assert(LT == 0 || NW == kOcNW, "the on-chip form: four waves");
   constexpr size_t lds = SB::kLds > SS::kLds ? SB::kLds : SS::kLds;
+  static_assert(lds <= 163840, "LDS of a gfx950 CU");
+  void (*kern)(typename SirenArgsOf<CODED>::type);
+  if constexpr (LT > 0) kern = &k_siren_step_x3_both_oc<H, NB, MINB, CODED, LT>;
+  else kern = &k_siren_step_x3_both<H, NW, NB, MINB, CODED>;
   static bool attr_done = false;
   if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step_x3_both<H, NW, NB, MINB, CODED>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_done = true;
   }
   const int64_t cap = 256 * MINB;
   const int64_t tb = (n_upper + SB::P - 1) / SB::P, ts = (n_upper + SS::P - 1) / SS::P;
   a.big_blocks = (int)(tb < cap ? (tb < 1 ? 1 : tb) : cap);
   const int small_blocks = (int)(ts < cap ? (ts < 1 ? 1 : ts) : cap);
-  hipLaunchKernelGGL((k_siren_step_x3_both<H, NW, NB, MINB, CODED>), dim3(a.big_blocks + small_blocks), dim3(64 * NW), lds, s, a);
+  hipLaunchKernelGGL(kern, dim3(a.big_blocks + small_blocks), dim3(64 * NW), lds, s, a);
   return 0;
 }
 
@@ -830,8 +941,29 @@ int siren_x3_launch_tail(const SirenCodedArgs& a, int H, hipStream_t s) {
   return a.code_bias ? launch_tail<true>(a, s) : launch_tail<false>(a, s);     // (false: the SirenArgs part)
 }
 
+// Step form (iso_siren_set_step_form): 1, the default, runs the H = 256 gradient kernels of two and three hidden layers
+// in the on-chip form (x3_step_body, LT > 0); 0 runs the eight-wave kernels with the global stash everywhere.
+// The coded kernels keep the eight-wave form: their on-chip build is one register short (the allocator parks a lane
+// index in an accumulator register, which the code object counts as a spill), and the library ships no new spills.
+static int g_step_form = 1;
+void siren_x3_set_step_form(int form) { g_step_form = form; }
+int siren_x3_get_step_form() { return g_step_form; }
+bool siren_x3_on_chip(int H, int L, bool fwd_only, bool coded) {
+  return g_step_form == 1 && H == 256 && (L == 2 || L == 3) && !fwd_only && !coded;
+}
+
 template <bool CODED>
 static int launch_any(const typename SirenArgsOf<CODED>::type& a, int H, int64_t n_upper, hipStream_t s) {
+  if constexpr (!CODED) {
+    if (siren_x3_on_chip(H, a.L, a.fwd_only != 0, false)) {
+      if (a.split == 3) {
+        return a.L == 3 ? launch_x3_both<256, kOcNW, kNB256, kMinB256, false, 3>(a, n_upper, s)
+                        : launch_x3_both<256, kOcNW, kNB256, kMinB256, false, 2>(a, n_upper, s);
+      }
+      return a.L == 3 ? launch_x3<256, kOcNW, kNB256, kMinB256, false, false, 3>(a, n_upper, s)
+                      : launch_x3<256, kOcNW, kNB256, kMinB256, false, false, 2>(a, n_upper, s);
+    }
+  }
   if (a.split == 3 && H == 256 && !a.fwd_only) return launch_x3_both<256, kNW256, kNB256, kMinB256, CODED>(a, n_upper, s);
   if (a.fwd_only) {
     if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, true, CODED>(a, n_upper, s);

@@ -1,5 +1,5 @@
 """Keep iso_siren_sdf_grad (the bench's dominant kernel) busy for SECONDS on 1 M points; prints ms per evaluation pass.
-usage: [ISO_SIREN_GEMM=f32] python tools/siren_loop.py [SECONDS] [P]"""
+usage: [ISO_SIREN_GEMM=f32] [ISO_EVAL_STEP_FORM=0|1] python tools/siren_loop.py [SECONDS] [P]"""
 import os
 import sys
 import time
@@ -17,6 +17,8 @@ torch.manual_seed(0)
 m = Siren(hidden_size=256, n_layers=3).to(dev)
 if os.environ.get("ISO_SIREN_GEMM") == "f32":
     _lib.call("iso_siren_set_gemm_mode", 0)
+if os.environ.get("ISO_EVAL_STEP_FORM") is not None:
+    _lib.call("iso_siren_set_step_form", int(os.environ["ISO_EVAL_STEP_FORM"]))
 g = torch.Generator().manual_seed(0)
 pts = torch.nn.functional.normalize(torch.randn(P, 3, generator=g), dim=-1).to(dev).contiguous()
 ps = PackedSiren(m, dev)

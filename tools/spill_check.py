@@ -17,6 +17,11 @@ MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 def kernels(lib):
     """[(kernel name, vgpr_spill_count, sgpr_spill_count, private_segment_fixed_size)] of all code objects in lib"""
+    return [k[:4] for k in kernel_resources(lib)]
+
+
+def kernel_resources(lib):
+    """kernels() with the static LDS size behind it: (..., group_segment_fixed_size)"""
     out = []
     with tempfile.TemporaryDirectory() as d:
         fat = os.path.join(d, "fat.bin")
@@ -36,7 +41,7 @@ def kernels(lib):
             notes = subprocess.run([LLVM + "/llvm-readelf", "--notes", co], stdout=subprocess.PIPE, text=True).stdout
             cur = {}
             for line in notes.splitlines():
-                m = re.match(r"\s*-?\s*\.(name|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s*(\S+)", line)
+                m = re.match(r"\s*-?\s*\.(name|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size|group_segment_fixed_size):\s*(\S+)", line)
                 if not m:
                     continue
                 key, val = m.group(1), m.group(2)
@@ -46,7 +51,7 @@ def kernels(lib):
                 if key == "vgpr_spill_count":           # the last of a kernel's fields we need (alphabetical order of the notes)
                     if "name" in cur:
                         out.append((cur.get("name"), int(val), int(cur.get("sgpr_spill_count", 0)),
-                                    int(cur.get("private_segment_fixed_size", 0))))
+                                    int(cur.get("private_segment_fixed_size", 0)), int(cur.get("group_segment_fixed_size", 0))))
                     cur = {}
     return out
 

@@ -21,7 +21,7 @@ def per_kernel(path, counter):
 def main():
     f, w = per_kernel(sys.argv[1], "FETCH_SIZE"), per_kernel(sys.argv[2], "WRITE_SIZE")
     res = {}
-    for names, key in ((("k_siren_step_x3_both<256, 8, 3", "k_siren_step_x3<256, 8, 3"), "k_siren_step_x3"), (("k_siren_step<",), "k_siren_step")):
+    for names, key in ((("k_siren_step_x3_both_oc<256, 3", "k_siren_step_x3_both<256, 8, 3", "k_siren_step_x3<256, 8, 3"), "k_siren_step_x3"), (("k_siren_step<",), "k_siren_step")):
         ks = [k for name in names for k in f if name in k]
         if not ks:
             continue
