@@ -379,6 +379,13 @@ extern "C" int iso_splat_zbuf_backward(const int32_t* idx, const float* grad_zbu
 // the exactly rounded sum (error <= 2^-44 max|grad| per term), bit-stable from run to run.
 struct ZScale { unsigned max_bits; int exp2; };
 
+// |x| as ordered bits; a NaN or an Inf counts as 0: it poisons the points that receive it (z_scatter_one) and must not
+// set the scale of all the others (on top of the maximum it leaves the exponent 0: every other sum rounds to an integer)
+__device__ __forceinline__ unsigned z_mag(unsigned bits) {
+  bits &= 0x7fffffffu;
+  return bits < 0x7f800000u ? bits : 0u;
+}
+
 __device__ void z_absmax_body(const float* __restrict__ gz, int64_t n, ZScale* __restrict__ zs, int block, int nblocks) {
   __shared__ unsigned sm[4];
   unsigned m = 0u;
@@ -388,19 +395,19 @@ __device__ void z_absmax_body(const float* __restrict__ gz, int64_t n, ZScale* _
   int64_t i = (int64_t)block * blockDim.x + threadIdx.x;
   for (; i + 3 * stride < n4; i += 4 * stride) {                    // four requests in flight
     const uint4 v0 = g4[i], v1 = g4[i + stride], v2 = g4[i + 2 * stride], v3 = g4[i + 3 * stride];
-    const unsigned a = max(max(v0.x & 0x7fffffffu, v0.y & 0x7fffffffu), max(v0.z & 0x7fffffffu, v0.w & 0x7fffffffu));
-    const unsigned b = max(max(v1.x & 0x7fffffffu, v1.y & 0x7fffffffu), max(v1.z & 0x7fffffffu, v1.w & 0x7fffffffu));
-    const unsigned c = max(max(v2.x & 0x7fffffffu, v2.y & 0x7fffffffu), max(v2.z & 0x7fffffffu, v2.w & 0x7fffffffu));
-    const unsigned d = max(max(v3.x & 0x7fffffffu, v3.y & 0x7fffffffu), max(v3.z & 0x7fffffffu, v3.w & 0x7fffffffu));
+    const unsigned a = max(max(z_mag(v0.x), z_mag(v0.y)), max(z_mag(v0.z), z_mag(v0.w)));
+    const unsigned b = max(max(z_mag(v1.x), z_mag(v1.y)), max(z_mag(v1.z), z_mag(v1.w)));
+    const unsigned c = max(max(z_mag(v2.x), z_mag(v2.y)), max(z_mag(v2.z), z_mag(v2.w)));
+    const unsigned d = max(max(z_mag(v3.x), z_mag(v3.y)), max(z_mag(v3.z), z_mag(v3.w)));
     m = max(m, max(max(a, b), max(c, d)));
   }
   for (; i < n4; i += stride) {
-    const uint4 v = g4[i];                                          // |x| as ordered bits (NaN/Inf on top)
-    const unsigned a = max(v.x & 0x7fffffffu, v.y & 0x7fffffffu), b = max(v.z & 0x7fffffffu, v.w & 0x7fffffffu);
+    const uint4 v = g4[i];
+    const unsigned a = max(z_mag(v.x), z_mag(v.y)), b = max(z_mag(v.z), z_mag(v.w));
     m = max(m, max(a, b));
   }
   for (int64_t t = n4 * 4 + (int64_t)block * blockDim.x + threadIdx.x; t < n; t += stride)
-    m = max(m, __float_as_uint(gz[t]) & 0x7fffffffu);
+    m = max(m, z_mag(__float_as_uint(gz[t])));
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
   if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = m;
