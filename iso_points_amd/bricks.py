@@ -6,6 +6,10 @@ The cycle's two neighbour searches run here:
   splat_h_fused    K = 7 bandwidth of SurfaceSplatting._get_per_point_info, rasterizer.py:367-386,
                    for all views of the cloud in one pass
 `frnn.frnn_grid_points` stays the general neighbour API.
+
+The kernels (csrc/): bricks.hip builds the grid, bricks_resample.hip and bricks_h.hip hold the two searches (what they
+share: bricks_stage.h, bricks_walk.h), bricks_halo.hip the N-rank halo exchange; the view mask that splat_h_fused reads
+is the set-up stage's (splat.hip).
 """
 import torch
 

@@ -85,9 +85,9 @@ BrickWs bricks_carve(void* ws, int64_t n_max);
 //           copies packed into four lines still cost 7 us of a 12 us projection, 256 lines 5 us (23 k atomics).  So a
 //           workgroup first LOOKS at its copy (a plain load: possibly stale, i.e. smaller, which only costs an atomic
 //           that was not needed) and adds only what would grow it -- a few hundred atomics per pass instead of 23 k.
-//           Filled by k_brick_bbox or by a projection launch (follow.h), turned into the header by the count pass of
-//           the build that follows (every workgroup decodes it for itself: no launch, no grid-wide wait in between),
-//           cleared by that build's offsets pass.
+//           Filled by k_brick_bbox (bricks.hip) or by a projection launch (follow.h), turned into the header by the count
+//           pass of the build that follows (k_brick_count in bricks.hip; every workgroup decodes it for itself: no launch,
+//           no grid-wide wait in between), cleared by that build's offsets pass.
 constexpr int kStickyAt = 16, kMagicAt = 38, kArriveAt = 40, kBoxAt = 64, kBoxCopies = 16, kBoxStride = 32,
               kCounterInts = kBoxAt + kBoxCopies * kBoxStride;
 constexpr int kBrickMagic = 0x1b71c5;

@@ -17,26 +17,13 @@
 #pragma once
 #include <float.h>
 #include "iso_common.h"
+#include "topk.h"      // pair_lt, wave_argmin: the (d2, index) order
 
 #pragma clang fp contract(off)
 
 namespace {
 
 constexpr int kRingCap = 2;   // shells a lane walks alone beyond its first; an open query then goes to a whole wave
-
-__device__ __forceinline__ bool pair_lt(float d1, int i1, float d2, int i2) {
-  return d1 < d2 || (d1 == d2 && i1 < i2);
-}
-
-// the smallest (d, i) pair of the wave, in every lane
-__device__ __forceinline__ void wave_argmin(float& d, int& i) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float od = __shfl_xor(d, o);
-    const int oi = __shfl_xor(i, o);
-    if (pair_lt(od, oi, d, i)) { d = od; i = oi; }
-  }
-}
 
 struct Grid3 {
   float mnx, mny, mnz, delta, cell;   // origin, cells per unit length, cell size

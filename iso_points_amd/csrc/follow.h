@@ -1,9 +1,10 @@
 // Side work of a kernel that writes FINAL point positions (include/isopoints.h: iso_follow): what the next stages of the
 // iso-point cycle would otherwise do in passes of their own over the points just written --
-//   * bounding box of the result -> the PENDING BOX of a brick workspace (bricks.h): replaces k_brick_bbox /
-//     iso_points_bbox; the header is made from it by the count pass of iso_bricks_build_pending;
+//   * bounding box of the result -> the PENDING BOX of a brick workspace (bricks.h): replaces k_brick_bbox (bricks.hip) /
+//     iso_points_bbox; the header is made from it by the count pass of iso_bricks_build_pending (bricks.hip);
 //   * renderable mask per point + the number of renderable points per 256-point tile and view: replaces
-//     k_view_mask_chunks (splat.hip; same expressions); the scan rides in that build's count launch (chunk_scan_job).
+//     k_view_mask_chunks (splat.hip, next to k_view_flags and k_view_mask; same expressions); the scan rides in that
+//     build's count launch (chunk_scan_job in bricks.hip).
 // No grid-wide hand-over inside the launch: a workgroup only adds to accumulators / writes its own tile's words.
 // Reference: UniformProjection._create_tree (levelset_sampling.py:110-140, bbox of the cloud);
 // SurfaceSplatting._filter_points_with_invalid_depth / backface culling (DSS/core/rasterizer.py:184-254).
@@ -18,7 +19,11 @@ struct FollowArgs {                     // device-side form of iso_follow
   int32_t* mask_out; int32_t* tile_cnt; int n_tiles;
 };
 
-BrickWs bricks_carve(void* ws, int64_t n_max);
+// front workspace (iso_splat_front_workspace_bytes): [chunk table 8 x (n_chunks + 1) ints][tile table 8 x (4 n_chunks + 4) ints]
+static inline int32_t* front_tile_table(void* front_ws, int64_t n_points) {
+  const int64_t n_chunks = (n_points + 1023) / 1024;
+  return (int32_t*)front_ws + 8 * (n_chunks + 1);
+}
 
 // host: validate *f for a launch over n points and translate it
 static inline int follow_args(const iso_follow& f, int64_t n, bool have_normals, const char* who, FollowArgs& a) {
@@ -35,7 +40,7 @@ static inline int follow_args(const iso_follow& f, int64_t n, bool have_normals,
     a.n_views = f.n_views;
     a.mask_out = f.mask_out;
     a.n_tiles = (int)(((n + kFollowTile - 1) / kFollowTile + 3) / 4 * 4);   // row stride of the table: a multiple of four (= 4 n_chunks)
-    a.tile_cnt = (int32_t*)f.front_ws + 8 * ((n + 1023) / 1024 + 1);       // behind the chunk table (front_tile_table)
+    a.tile_cnt = front_tile_table(f.front_ws, n);                          // behind the chunk table
   }
   return ISO_OK;
 }
@@ -67,7 +72,7 @@ struct FollowState {
     int m = 0;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
-      if (v < a.n_views) {                                  // the expressions of k_view_mask_chunks (splat.hip)
+      if (v < a.n_views) {                                  // the expressions of k_view_mask / k_view_mask_chunks (splat.hip)
         const float zv = ((x * vz[v][0] + y * vz[v][1]) + z * vz[v][2]) + vz[v][3];
         bool ok = (zv >= a.znear) && (zv <= a.zfar);
         if (a.backface) ok = ok && (((nx * vz[v][0] + ny * vz[v][1]) + nz * vz[v][2]) < 0.f);

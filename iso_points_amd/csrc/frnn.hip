@@ -293,40 +293,7 @@ __global__ __launch_bounds__(SCAN_BLOCK) void k_scan_final(
   }
 }
 
-// ---- query ----------------------------------------------------------------
-template <int KMAX>
-struct TopK {
-  float d[KMAX];
-  int id[KMAX];
-  __device__ __forceinline__ void init() {
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) { d[j] = FLT_MAX; id[j] = 0x7fffffff; }
-  }
-  // keep the K smallest (d, id) pairs in ascending order
-  __device__ __forceinline__ void push(float cd, int ci, int K) {
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) {
-      if (j < K && pair_lt(cd, ci, d[j], id[j])) {
-        float td = d[j]; int ti = id[j];
-        d[j] = cd; id[j] = ci;
-        cd = td; ci = ti;
-      }
-    }
-  }
-  __device__ __forceinline__ float worst(int K) const {
-    float w = FLT_MAX;
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) if (j == K - 1) w = d[j];
-    return w;
-  }
-  __device__ __forceinline__ int worst_id(int K) const {
-    int w = 0x7fffffff;
-#pragma unroll
-    for (int j = 0; j < KMAX; ++j) if (j == K - 1) w = id[j];
-    return w;
-  }
-};
-
+// ---- query (the per-lane list: TopK<KMAX> of topk.h) ------------------------
 // OTHERS (iso_frnn_query_others, always a self query): the candidate whose original index is the query's own row is
 // passed over, so the list holds the K nearest OTHER points; OTHERS = false is the plain query, the same code as before.
 template <int KMAX, bool OTHERS = false>
@@ -442,6 +409,7 @@ __global__ __launch_bounds__(256) void k_query(
 // distance is obtained by K rounds of a wave-wide arg-min over the lanes' list heads, and the
 // same stopping rule as k_query is applied; the final K results come out of the same merge --
 // identical (d2, idx) order, so the output does not depend on which kernel served a query.
+// (wave_merge3 of bricks_resample.hip is the same merge with an emit call: written on top of it, k_query_tail<*> compiled differently.)
 template <int KMAX>
 __device__ __forceinline__ void wave_merge(const TopK<KMAX>& best, int K, float& kth, float* drow,
                                            int64_t* irow, float* nnrow, const float* pts2, int lane) {

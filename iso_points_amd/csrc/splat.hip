@@ -425,7 +425,47 @@ __global__ __launch_bounds__(256) void k_mask_chunk_count(const int32_t* __restr
   if (threadIdx.x < n_views) chunk_cnt[threadIdx.x * n_chunks + blockIdx.x] = s_cnt[threadIdx.x];
 }
 
-// The renderable mask of rasterizer.py:184-254 (k_view_mask in bricks.hip: same expressions) AND the chunk counts
+// ---- renderable flags of every point for up to 8 views (rasterizer.py:184-254) --------------------
+// (the bit-mask form of k_view_flags: what the fused bandwidth kernel of bricks_h.hip reads)
+__global__ __launch_bounds__(256) void k_view_mask(const float* __restrict__ pts, const float* __restrict__ nrm,
+                                                   const float* __restrict__ views, int n_views, int64_t n,
+                                                   float znear, float zfar, int backface,
+                                                   int32_t* __restrict__ mask, int32_t* __restrict__ view_count) {
+  __shared__ int s_cnt[8];
+  if (threadIdx.x < 8) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  int local[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float x = pts[i * 3], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+    float nx = 0.f, ny = 0.f, nz = 0.f;
+    if (backface) { nx = nrm[i * 3]; ny = nrm[i * 3 + 1]; nz = nrm[i * 3 + 2]; }
+    int m = 0;
+#pragma unroll
+    for (int v = 0; v < 8; ++v) {
+      if (v < n_views) {
+        const float* V = views + v * 16;                    // row-vector convention: p_view = [p,1] @ V
+        const float zv = ((x * V[2] + y * V[6]) + z * V[10]) + V[14];
+        bool ok = (zv >= znear) && (zv <= zfar);
+        if (backface) ok = ok && (((nx * V[2] + ny * V[6]) + nz * V[10]) < 0.f);
+        if (ok) { m |= 1 << v; ++local[v]; }
+      }
+    }
+    mask[i] = m;
+  }
+#pragma unroll
+  for (int v = 0; v < 8; ++v) {
+    if (v < n_views) {
+      int c = local[v];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+      if ((threadIdx.x & 63) == 0 && c) atomicAdd(&s_cnt[v], c);
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < n_views && s_cnt[threadIdx.x]) atomicAdd(&view_count[threadIdx.x], s_cnt[threadIdx.x]);
+}
+
+// The renderable mask of rasterizer.py:184-254 (k_view_mask above: same expressions) AND the chunk counts
 // in one pass: a workgroup owns the kChunk consecutive points the front end's workgroup of the same index will own.
 __global__ __launch_bounds__(256) void k_view_mask_chunks(const float* __restrict__ pts, const float* __restrict__ nrm,
                                                           const float* __restrict__ views, int n_views, int64_t P,
@@ -841,6 +881,21 @@ extern "C" int iso_splat_front(const float* points, const float* normals, const 
                        features_from_normals, o);
   }
   ISO_CHECK_LAUNCH("iso_splat_front");
+  return ISO_OK;
+}
+
+extern "C" int iso_splat_view_mask(const float* points, const float* normals, const float* views, int n_views,
+                                   int64_t n, float znear, float zfar, int backface_culling, int32_t* mask_out,
+                                   int32_t* view_count_out, void* stream) {
+  ISO_REQUIRE(n >= 0 && n_views >= 1 && n_views <= 8, ISO_ERR_UNSUPPORTED, "iso_splat_view_mask: 1..8 views per call");
+  ISO_REQUIRE(views && mask_out && view_count_out && (points || n == 0) && (normals || !backface_culling),
+              ISO_ERR_INVALID, "iso_splat_view_mask: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  iso_zero_words(view_count_out, 8, s);
+  if (n > 0)
+    hipLaunchKernelGGL(k_view_mask, dim3(iso_stream_grid(n, 256 * 4)), dim3(256), 0, s, points, normals, views, n_views,
+                       n, znear, zfar, backface_culling, mask_out, view_count_out);
+  ISO_CHECK_LAUNCH("iso_splat_view_mask");
   return ISO_OK;
 }
 

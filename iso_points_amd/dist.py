@@ -3,14 +3,15 @@ backend "nccl" = RCCL over xGMI; "gloo" works too and is what the CPU / one-GPU 
 
 The reference has no distributed layer; this is the design SURVEY 8(e) / the north star
 ask for.  The cloud is sharded by SPACE: the ranks hold consecutive x-slabs (balanced by point count;
-`slab_order`), i.e. contiguous ranges of the brick-sorted order of csrc/bricks.hip, and the global
+`slab_order`), i.e. contiguous ranges of the brick-sorted order of csrc/bricks.hip (the halo
+exchange between slabs: csrc/bricks_halo.hip), and the global
 point order is rank-major, so every index the single-GPU cycle produces keeps its meaning.
 
   stage                          partition                        exchange (per cycle)
   -----------------------------  -------------------------------  -------------------------------------------
   Newton projection (T=10, T=3)  own points                       none
   FRNN tree + repulsion          own points; neighbours = own     all-gather of 8-float bounding boxes, then ONE
-   (fused, csrc/bricks.hip)      bricks + imported halo cells     all-gather of the halo cells (points + normals +
+   (fused, bricks_resample.hip)  bricks + imported halo cells     all-gather of the halo cells (points + normals +
                                                                   ids of the points within one fine cell of
                                                                   another slab: 32 B each)
   renderable mask, K=7           own points; halo as above        boxes + per-view counts (64 B), halo cells

@@ -508,7 +508,7 @@ class UniformProjection(LevelSetProjection):
         points, projection_result, idx, inv_sigma, P = points_init, None, None, None, points_init.shape[1]
         for sample_iter in range(sample_iters):
             if sample_iter == 0 and fused:
-                # tree + repulsion in one kernel on the brick grid (csrc/bricks.hip); the neighbour lists are
+                # tree + repulsion in one kernel on the brick grid (csrc/bricks_resample.hip); the neighbour lists are
                 # only materialised when a later iteration re-uses them (:262-266) or the caller asks for them
                 from . import bricks
                 grid = getattr(self, "_grid", None)          # the workspace (a few hundred MB at 1 M points, cleared once)
