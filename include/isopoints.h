@@ -121,6 +121,17 @@ int iso_idr_set_drawn_tiles(int on);
 int iso_siren_set_step_form(int form);
 int iso_siren_get_step_form(void);
 int iso_siren_step_form_used(int hidden, int n_hidden, int coded);
+/* Which step kernel serves a call of this shape as the GEMM mode and the step form are set now (host only, nothing is
+ * launched).  value_only != 0: sphere tracing, or iso_siren_sdf_grad without grad_out; coded != 0: an iso_*_siren_coded entry.
+ *   100 + H/16  k_siren_step<H/16, coded>                      mode 0; or H = 64; or n_hidden = 0
+ *   200 + H/16  k_siren_step_x3<H, ., ., ., true, coded>       mode 1, H = 128 / 256, n_hidden 1..8, value only
+ *   308         k_siren_step_x3<128, 4, 3, 1, false, coded>    mode 1, H = 128, n_hidden 1..8, gradient
+ *   416         k_siren_step_x3_both<256, 8, 3, 1, coded>      mode 1, H = 256, n_hidden 1..8, gradient, unless 516
+ *   516         k_siren_step_x3_both_oc<256, 3, 1, false, L>   mode 1, step form 1, H = 256, n_hidden 2 / 3, gradient, uncoded
+ *   -1          H not 64 / 128 / 256 or n_hidden outside 0..8
+ * The Newton tail (iso_siren_set_tail_from) and the drawn tiles (iso_siren_set_drawn_tiles) go with 416 and 516 alone;
+ * iso_siren_step_form_used is "the gradient step's code is 516". */
+int iso_siren_step_kernel(int hidden, int n_hidden, int value_only, int coded);
 /* step-kernel launches one iso_project_siren call with these arguments issues (max_iters + 1 without the tail) */
 int iso_siren_step_launches(int hidden, int n_hidden, int max_iters);
 /* scratch for the per-wave activation-derivative stash */

@@ -36,6 +36,7 @@ SIGNATURES = {
     "iso_siren_set_step_form": (_I, [_I]),
     "iso_siren_get_step_form": (_I, []),
     "iso_siren_step_form_used": (_I, [_I, _I, _I]),
+    "iso_siren_step_kernel": (_I, [_I, _I, _I, _I]),
     "iso_siren_step_launches": (_I, [_I, _I, _I]),
     "iso_siren_pack_weights": (_I, [_P, _P, _I, _I, _P]),
     "iso_project_siren_workspace_bytes": (_L, [_L, _I, _I]),

@@ -1,5 +1,5 @@
-// Shared pieces of the fused-MLP kernels (siren.hip, idr.hip): accurate sin/cos and the
-// LDS-staged f32 MFMA layer pass.  See siren.hip for the data-layout story.
+// Shared pieces of the fused-MLP kernels (siren_f32.hip, idr.hip): accurate sin/cos and the
+// LDS-staged f32 MFMA layer pass.  See siren_f32.hip for the data-layout story.
 #pragma once
 #include "iso_common.h"
 

@@ -1,5 +1,5 @@
-// Shared between siren.hip (f32-MFMA step kernel, packing, C ABI) and siren_x3.hip (the
-// split-fp16 MFMA step kernel): argument block and the layout of the packed weight buffer.
+// Shared between siren.hip (C ABI, siren_form, the iteration driver), siren_f32.hip (f32-MFMA step kernel, its packing)
+// and siren_x3.hip (the split-fp16 MFMA step kernels): argument block and the layout of the packed weight buffer.
 #pragma once
 #include "iso_common.h"
 
@@ -32,12 +32,12 @@ struct SirenArgs {
   // split != 0 (H = 256 step kernels): 96-point tiles for the slots [0, siren_split_point(count)) (split = 1) and 32-point
   // tiles for the rest (split = 2), so that the last, partly filled round of the persistent grid costs a 32-point tile time
   // instead of a 96-point one
-  int split = 0;             // 3: both in one launch (k_siren_step_x3_both, which runs 1 and 2 itself)
+  int split = 0;             // 3: both in one launch (written by launch_x3_both; k_siren_step_x3_both runs 1 and 2 itself)
   int big_blocks = 0;        // split = 3: workgroups of the 96-point-tile shape (set by the launcher)
   // Newton tail (k_siren_tail_x3): ONE launch runs iterations it_first .. it_last; a workgroup keeps the survivors of
   // its own tiles in a private pair of lists and iterates them alone -- no launch, no grid-wide step per iteration
   int32_t* tail_lists = nullptr;   // [blocks][2][tail_cap] private survivor lists
-  int32_t* tail_counts = nullptr;  // [blocks][2] their lengths (zero on entry of the launch: cleared by k_zero_counts' sibling)
+  int32_t* tail_counts = nullptr;  // [blocks][2] their lengths (zero on entry of the launch: cleared by k_siren_zero)
   int32_t* iter_counts = nullptr;  // counts[it] of the projection (diagnostics: points evaluated by iteration it)
   int tail_cap = 0, it_first = 0, it_last = 0;
   // k_siren_step_x3_both: two counters (96-point tiles, 32-point tiles), ZERO when the launch starts; null: static tile
@@ -69,7 +69,7 @@ __host__ __device__ inline int64_t siren_split_point(int64_t count) {
   return (rem + small - 1) / small <= 2 ? full : count;
 }
 
-// ---- packed weight buffer, f32 section (siren.hip) ---------------------------------------
+// ---- packed weight buffer, f32 section (siren_f32.hip) ------------------------------------
 // [W0img 4*H][WLimg H][bL,pad 4][ per hidden layer: bias H | FW H*H | BW H*H ]
 __host__ __device__ inline int64_t off_w0(int H) { (void)H; return 0; }
 __host__ __device__ inline int64_t off_wl(int H) { return 4 * (int64_t)H; }
@@ -109,15 +109,15 @@ __host__ __device__ inline int64_t x16_off_layer(int H, int L, int l) { return x
 __host__ __device__ inline int64_t x16_off_bw(int H, int L, int l) { return x16_off_layer(H, L, L) + (int64_t)l * H * H; }
 __host__ __device__ inline int64_t siren_packed_total(int H, int L) { return x16_off_bw(H, L, L); }
 
-// ---- siren_x3.hip entry points -----------------------------------------------------------
+// ---- siren_f32.hip entry points (siren_form's codes 1xx) -----------------------------------
+void siren_f32_pack(const float* raw, float* packed, int H, int L, hipStream_t s);
+int64_t siren_f32_stash_floats(int H, int L);
+int siren_f32_launch(const SirenCodedArgs& a, int H, int64_t n, hipStream_t s);   // k_siren_step<H / 16, coded>
+// ---- siren_x3.hip entry points (siren_form's codes 2xx .. 5xx) -----------------------------
 bool siren_x3_supported(int H, int L);
 int64_t siren_x3_stash_floats(int H, int L);
 void siren_x3_pack(const float* raw, float* packed, int H, int L, hipStream_t s);
-int siren_x3_launch(const SirenCodedArgs& a, int H, int64_t n_upper, hipStream_t s);
-// step form of the H = 256 gradient kernels: 0 = eight waves, global derivative stash; 1 = four waves, stash on chip
-void siren_x3_set_step_form(int form);
-int siren_x3_get_step_form();
-bool siren_x3_on_chip(int H, int L, bool fwd_only, bool coded);           // does form 1 serve this call (as set now)?
+int siren_x3_launch(int form, const SirenCodedArgs& a, int64_t n_upper, hipStream_t s);   // -1: no kernel of that code
 int siren_x3_tail_blocks();                                               // workgroups of the Newton-tail launch
 int siren_x3_launch_tail(const SirenCodedArgs& a, int H, hipStream_t s);  // H = 256 only
 // ---- the point-stationary form of the H = 256 step (tools/experiments/siren_ps, not part of this library) -------

@@ -1,7 +1,7 @@
 // Fused SIREN SDF + gradient evaluation and Newton step with the hidden-layer GEMMs on the
 // 16-bit matrix cores at f32 accuracy (v_mfma_f32_32x32x16_f16 / _bf16, gfx950).
 //
-// Reference semantics are those of siren.hip (Siren.forward DSS/models/common.py:140-165 under
+// Reference semantics are those of siren_f32.hip (Siren.forward DSS/models/common.py:140-165 under
 // autograd.grad in UniformProjection._compute_sdf_and_grad, levelset_sampling.py:142-170, iterated
 // by _project_points :313-342); this file only changes how the H x H products are formed.
 //
@@ -15,7 +15,7 @@
 // kernel.  (The file started with an exact three-way bf16 cut, six products -- hence the x3 in the names; that
 // form and the overlap experiments built on it are in tools/experiments/ and in the history.)
 //
-// Work decomposition (differs from siren.hip: weights are NOT staged through LDS)
+// Work decomposition (differs from siren_f32.hip: weights are NOT staged through LDS)
 //   * one workgroup = P = 32*NB points (NB = 3), NW = 8 waves (two per SIMD; NW = 4 also builds).
 //   * the OUTPUT features of a layer are split across the waves (wave w owns tiles
 //     TW*w .. TW*w+TW-1 of 32 features): each weight element is needed by exactly one wave,
@@ -775,13 +775,9 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_step_x3_both(typename S
   }
 }
 
-// The on-chip form (x3_step_body, LT > 0) of the two kernels above: four waves, LT hidden layers, no global stash.
-// (Kernels of their own, not more parameters of the two above: those keep their names and their machine code.)
+// The on-chip form (x3_step_body, LT > 0) of the kernel above: four waves, LT hidden layers, no global stash.
+// (A kernel of its own, not more parameters of the one above: that keeps its name and its machine code.)
 constexpr int kOcNW = 4;
-template <int H, int NB, int MINB, bool CODED, int LT>
-__global__ __launch_bounds__(64 * kOcNW, MINB) void k_siren_step_x3_oc(typename SirenArgsOf<CODED>::type a) {
-  x3_step_body<H, kOcNW, NB, false, CODED, LT>(a, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.x);
-}
 // (k_siren_step_x3_both, without the stash regions; a function of its own taking the argument block by reference: written
 // into the kernel, the same text reserves 68 bytes of scratch per lane that no instruction uses)
 template <int H, int NB, bool CODED, int LT>
@@ -849,15 +845,11 @@ __global__ __launch_bounds__(64 * NW, MINB) void k_siren_tail_x3(typename SirenA
   if (threadIdx.x == 0) { cnts[0] = 0; cnts[1] = 0; }
 }
 
-// LT > 0: the on-chip form of LT hidden layers (NW = kOcNW)
-template <int H, int NW, int NB, int MINB, bool FWD, bool CODED, int LT = 0>
+template <int H, int NW, int NB, int MINB, bool FWD, bool CODED>
 int launch_x3(const typename SirenArgsOf<CODED>::type& a, int64_t n_upper, hipStream_t s) {
-  using S = X3Shape<H, NW, NB, (LT > 0 ? (H / 32) / NW : 1)>;
-  static_assert(LT == 0 || (NW == kOcNW && !FWD), "the on-chip form: four waves, gradient kernels");
+  using S = X3Shape<H, NW, NB>;
   static_assert(S::kLds <= 163840, "LDS of a gfx950 CU");
-  void (*kern)(typename SirenArgsOf<CODED>::type);
-  if constexpr (LT > 0) kern = &k_siren_step_x3_oc<H, NB, MINB, CODED, LT>;
-  else kern = &k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>;
+  void (*kern)(typename SirenArgsOf<CODED>::type) = &k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>;
   static bool attr_done = false;
   if (!attr_done) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::kLds);
@@ -870,6 +862,7 @@ int launch_x3(const typename SirenArgsOf<CODED>::type& a, int64_t n_upper, hipSt
   return 0;
 }
 
+// LT > 0: the on-chip form of LT hidden layers (NW = kOcNW)
 template <int H, int NW, int NB, int MINB, bool CODED, int LT = 0>
 int launch_x3_both(typename SirenArgsOf<CODED>::type a, int64_t n_upper, hipStream_t s) {
   constexpr int RP = LT > 0 ? (H / 32) / NW : 1;
@@ -889,6 +882,7 @@ int launch_x3_both(typename SirenArgsOf<CODED>::type a, int64_t n_upper, hipStre
   const int64_t cap = 256 * MINB;
   const int64_t tb = (n_upper + SB::P - 1) / SB::P, ts = (n_upper + SS::P - 1) / SS::P;
   a.big_blocks = (int)(tb < cap ? (tb < 1 ? 1 : tb) : cap);
+  a.split = 3;                 // (as SirenArgs documents it; the kernel gives each of its two shapes its own 1 / 2)
   const int small_blocks = (int)(ts < cap ? (ts < 1 ? 1 : ts) : cap);
   hipLaunchKernelGGL(kern, dim3(a.big_blocks + small_blocks), dim3(64 * NW), lds, s, a);
   return 0;
@@ -941,43 +935,27 @@ int siren_x3_launch_tail(const SirenCodedArgs& a, int H, hipStream_t s) {
   return a.code_bias ? launch_tail<true>(a, s) : launch_tail<false>(a, s);     // (false: the SirenArgs part)
 }
 
-// Step form (iso_siren_set_step_form): 1, the default, runs the H = 256 gradient kernels of two and three hidden layers
-// in the on-chip form (x3_step_body, LT > 0); 0 runs the eight-wave kernels with the global stash everywhere.
-// The coded kernels keep the eight-wave form: their on-chip build is one register short (the allocator parks a lane
-// index in an accumulator register, which the code object counts as a spill), and the library ships no new spills.
-static int g_step_form = 1;
-void siren_x3_set_step_form(int form) { g_step_form = form; }
-int siren_x3_get_step_form() { return g_step_form; }
-bool siren_x3_on_chip(int H, int L, bool fwd_only, bool coded) {
-  return g_step_form == 1 && H == 256 && (L == 2 || L == 3) && !fwd_only && !coded;
-}
-
+// The launch switch of siren_form's codes 2xx .. 5xx (siren.hip: the one place that decides; the table is there).
+// The on-chip form (516) exists uncoded only: the coded build is one register short (the allocator parks a lane index in
+// an accumulator register, which the code object counts as a spill), and the library ships no new spills.  The H = 256
+// gradient kernel of ONE tile shape (k_siren_step_x3<256, ., ., ., false, .>) is not built: every such call is a 416 / 516.
 template <bool CODED>
-static int launch_any(const typename SirenArgsOf<CODED>::type& a, int H, int64_t n_upper, hipStream_t s) {
-  if constexpr (!CODED) {
-    if (siren_x3_on_chip(H, a.L, a.fwd_only != 0, false)) {
-      if (a.split == 3) {
-        return a.L == 3 ? launch_x3_both<256, kOcNW, kNB256, kMinB256, false, 3>(a, n_upper, s)
-                        : launch_x3_both<256, kOcNW, kNB256, kMinB256, false, 2>(a, n_upper, s);
+static int launch_form(int form, const typename SirenArgsOf<CODED>::type& a, int64_t n_upper, hipStream_t s) {
+  switch (form) {
+    case 208: return launch_x3<128, 4, 3, kMinB128, true, CODED>(a, n_upper, s);
+    case 216: return launch_x3<256, kNW256, kNB256, kMinB256, true, CODED>(a, n_upper, s);
+    case 308: return launch_x3<128, 4, 3, kMinB128, false, CODED>(a, n_upper, s);
+    case 416: return launch_x3_both<256, kNW256, kNB256, kMinB256, CODED>(a, n_upper, s);
+    case 516:
+      if constexpr (!CODED) {
+        if (a.L == 2) return launch_x3_both<256, kOcNW, kNB256, kMinB256, false, 2>(a, n_upper, s);
+        if (a.L == 3) return launch_x3_both<256, kOcNW, kNB256, kMinB256, false, 3>(a, n_upper, s);
       }
-      return a.L == 3 ? launch_x3<256, kOcNW, kNB256, kMinB256, false, false, 3>(a, n_upper, s)
-                      : launch_x3<256, kOcNW, kNB256, kMinB256, false, false, 2>(a, n_upper, s);
-    }
+      return -1;
+    default: return -1;
   }
-  if (a.split == 3 && H == 256 && !a.fwd_only) return launch_x3_both<256, kNW256, kNB256, kMinB256, CODED>(a, n_upper, s);
-  if (a.fwd_only) {
-    if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, true, CODED>(a, n_upper, s);
-    if (H == 128) return launch_x3<128, 4, 3, kMinB128, true, CODED>(a, n_upper, s);
-  }
-  // (the H = 256 gradient kernel of one tile shape: only run_step_split's callers reach it, and they take the split
-  // launch above; the coded form is not built)
-  if constexpr (!CODED) {
-    if (H == 256) return launch_x3<256, kNW256, kNB256, kMinB256, false, false>(a, n_upper, s);
-  }
-  if (H == 128) return launch_x3<128, 4, 3, kMinB128, false, CODED>(a, n_upper, s);
-  return -1;
 }
 
-int siren_x3_launch(const SirenCodedArgs& a, int H, int64_t n_upper, hipStream_t s) {
-  return a.code_bias ? launch_any<true>(a, H, n_upper, s) : launch_any<false>(a, H, n_upper, s);
+int siren_x3_launch(int form, const SirenCodedArgs& a, int64_t n_upper, hipStream_t s) {
+  return a.code_bias ? launch_form<true>(form, a, n_upper, s) : launch_form<false>(form, a, n_upper, s);   // (false: the SirenArgs part)
 }

@@ -100,7 +100,6 @@ def test_selection_list_files_are_built_without_the_slp_vectoriser():
 # ceiling a rebuild may not exceed without a look.  Everything else in the library must not spill.
 SPILL_ALLOWED = {
     "20k_siren_step_x3_bothILi256ELi8ELi3ELi1E": (99, "test_siren_step_repeat_stress_1m"),
-    "15k_siren_step_x3ILi256ELi8ELi3ELi1ELb0E": (91, "test_siren_step_repeat_stress_1m"),
     "14k_idr_step_x16ILi512ELi2ELb0E": (100, "test_idr_step_repeat_stress_1m"),
     "14k_idr_step_x16ILi512ELi2ELb1E": (32, "test_idr_step_repeat_stress_1m"),
     "14k_idr_step_x16ILi256ELi3ELb0E": (83, "test_idr_step_repeat_stress_1m"),

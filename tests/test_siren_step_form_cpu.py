@@ -1,5 +1,5 @@
-"""Build guard of the on-chip SIREN step kernels (siren_x3.hip, k_siren_step_x3_oc / k_siren_step_x3_both_oc): they are
-in the library, hold their whole state in registers and LDS, and fit the LDS of a gfx950 CU."""
+"""Build guard of the on-chip SIREN step kernels (siren_x3.hip, k_siren_step_x3_both_oc): they are in the library, hold
+their whole state in registers and LDS, and fit the LDS of a gfx950 CU."""
 import importlib.util
 import os
 import shutil
@@ -25,7 +25,7 @@ def test_on_chip_step_kernels_use_no_scratch_and_fit_lds():
     assert DYN_LDS == 160256
     for L in (2, 3):
         # <H = 256, NB = 3, MINB = 1, CODED = false, LT = L>
-        for pat in ("23k_siren_step_x3_both_ocILi256ELi3ELi1ELb0ELi%dE" % L, "18k_siren_step_x3_ocILi256ELi3ELi1ELb0ELi%dE" % L):
+        for pat in ("23k_siren_step_x3_both_ocILi256ELi3ELi1ELb0ELi%dE" % L,):
             hit = [k for k in ks if pat in k[0]]
             assert len(hit) == 1, (pat, hit)
             name, vgpr_spills, _, private, static_lds = hit[0]

@@ -21,9 +21,8 @@ def spy(name, *a):
         # (pts, out, normals, mask, n, packed, H, L, w0, wh, T, tol, ws, ws_bytes, stream)
         torch.cuda.synchronize()
         n, H, L, T, ws = a[4], a[6], a[7], a[10], a[12].value
-        stash = lib.iso_project_siren_workspace_bytes(n, H, L) - (2 * n * 4 + 64 * 4 + 64)
         buf = (ctypes.c_int32 * 16)()
-        hip.hipMemcpy(buf, ctypes.c_void_p(ws + stash + 8 * n), 64, 2)
+        hip.hipMemcpy(buf, ctypes.c_void_p(ws + lib.iso_project_siren_counts_offset(n, H, L)), 64, 2)
         print("project T=%d of %d points: active list lengths %s" % (T, n, [n] + list(buf[1:T + 2])))
     return rc
 
