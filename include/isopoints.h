@@ -974,7 +974,14 @@ int iso_splat_repack(const float* gathered, int64_t capacity, int world, int ran
  *    records came in (iso_splat_band_return: world segments of cap_pair x 2 int64), the reverse all-to-all returns
  *    them, iso_splat_band_merge adds them to the owner's rows (integer adds: order-independent).
  *    flags (int32[1], caller-cleared): bit 0 a send segment overflowed cap_pair, bit 1 the local arrays did.
- *    counts: (world, 8) int32 rows per view of every rank (all-gathered view totals of iso_splat_front).        */
+ *    counts: (world, 8) int32 rows per view of every rank (all-gathered view totals of iso_splat_front).
+ *    Limits: world <= 64, 1..8 views.  iso_splat_band_export expects num_points[v] <= max_rows_per_view; rows of a view
+ *    beyond (ceil(max_rows_per_view / 512) + 1) * 512 are not looked at (not sent, NOT flagged).  After a clip the
+ *    delivered records are a prefix: a segment keeps its first cap_pair records (the header counts of the views past the
+ *    cut are 0), the local arrays their first cap_local rows.  iso_splat_band_return writes the slots of the local rows
+ *    only: the slot of a record that was dropped at cap_local keeps the caller's value, which iso_splat_band_merge then
+ *    adds -- keep `ret` zero there if such a record is to contribute nothing (a record dropped at cap_pair has no slot).
+ *    Outputs need no initial value; nothing outside the extents above is written (tests/test_exchange_gpu.py).    */
 int64_t iso_splat_band_segment_floats(int64_t cap_pair);
 int64_t iso_splat_band_export_workspace_bytes(int64_t max_rows_per_view, int n_views, int world);
 int iso_splat_band_export(const float* ndc, const float* ellipse, const float* radii, const float* scaler,

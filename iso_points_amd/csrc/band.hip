@@ -359,6 +359,10 @@ extern "C" int64_t iso_splat_band_export_workspace_bytes(int64_t max_rows_per_vi
 // (world segments of iso_splat_band_segment_floats(cap_pair) floats), sent_row (world * cap_pair) int32, and -- in the
 // workspace -- what iso_splat_band_merge needs later; first_global / num_global (n_views int64): the layout of the
 // single-GPU packed arrays, gid_first (n_views int64): where this rank's rows of every view start in it.
+// Contract: num_points[v] <= max_rows_per_view for every view (the grid and the workspace are sized from it).  Rows of a
+// view beyond (ceil(max_rows_per_view / 512) + 1) * 512 are not looked at: not sent, not flagged, acc_own / vis_own not
+// cleared.  acc_own / vis_own are cleared over the own rows [first_idx[v], first_idx[v] + num_points[v]) and touched
+// nowhere else; records past a segment's count, sent_row past it and the workspace need no initial value.
 extern "C" int iso_splat_band_export(const float* ndc, const float* ellipse, const float* radii, const float* scaler,
                                      const float* features, const int64_t* first_idx, const int64_t* num_points,
                                      int n_views, int64_t max_rows_per_view, const int32_t* counts, int world, int rank,
@@ -433,6 +437,11 @@ extern "C" int iso_splat_band_remap(const int32_t* idx_local, const int32_t* gid
   return ISO_OK;
 }
 
+// Contract: writes the slot of every local row (origin[p], p < first_local[n_views - 1] + num_local[n_views - 1]) and no
+// other.  A record that arrived but was dropped at cap_local (flag bit 1) has no local row, so its slot of `ret` keeps
+// what the caller left there and iso_splat_band_merge adds THAT to the owner's row: a caller that wants such a record to
+// contribute nothing keeps `ret` zero outside the written slots (dist.py allocates it zeroed and treats the flag as an
+// error).  A record dropped at cap_pair was never sent: it has no slot and contributes nothing.
 extern "C" int iso_splat_band_return(const int64_t* acc_local, const uint8_t* vis_local, const int32_t* origin,
                                      const int64_t* first_local, const int64_t* num_local, int n_views, int64_t cap_local,
                                      int64_t* ret, void* stream) {
