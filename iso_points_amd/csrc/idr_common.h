@@ -1,18 +1,39 @@
-// Shared between idr.hip (f32-MFMA kernels, packing, C ABI) and idr_x16.hip (split-fp16 kernel):
-// network shape, packed-buffer layout, argument block, encoding and activation.
+// Shared between idr.hip (C ABI, idr_form, the iteration driver), idr_f32.hip (f32-MFMA step kernels, their packing) and
+// idr_x16.hip (split-fp16 step kernel): network shape, argument block, packed-buffer layout, encoding and activation.
 #pragma once
 #include "iso_common.h"
 #include "mlp_common.h"
 
-namespace {
-
-
-constexpr int kD0Pad = 64;          // padded encoding width (D0 = 3 + 6F <= 63)
-constexpr int kW0Row = 64;          // floats per feature row of the VALU backward image
-
 struct IdrShape {
   int H, n_layers, skip, F, D0;     // skip < 0: no skip connection
 };
+
+struct IdrArgs {
+  float* pts; float* normals; uint8_t* mask; float* sdf_out; float* grad_out;
+  const int32_t* idx_in; const int32_t* count_in; int32_t* idx_out; int32_t* count_out;
+  const float* packed; float* stash;
+  int64_t n;
+  IdrShape s;
+  float beta, tol;
+  int do_move, eval_only;
+  // sphere tracing (iso_trace_idr): unit ray directions (n,3); null = Newton / evaluation
+  const float* dirs = nullptr;
+  float alpha = 1.f, bound = 0.f, tol_valid = 0.f;
+  int fwd_only = 0;          // 1: the gradient is not needed
+  // k_idr_step_x16: a counter, ZERO when the launch starts, the workgroups draw their next tile from (null: every
+  // gridDim-th tile -- the launch then ends with the slowest XCD, see x3_step_body in siren_x3.hip)
+  int32_t* tile_ctr = nullptr;
+};
+
+// Most workgroups a step launch runs (persistent: one 160 KiB workgroup per CU at H = 512) -- and so the number of stash
+// slices: every launch (iso_capped_grid over its kernel's tile) and every *_stash_floats sizes itself by this one number.
+constexpr int kIdrBlocks = 256;
+
+namespace {
+
+constexpr int kD0Pad = 64;          // padded encoding width (D0 = 3 + 6F <= 63)
+constexpr int kW0Row = 64;          // floats per feature row of the VALU backward image
+constexpr int kIdrFsEncRows = 48;   // encoding rows of the feature-split f32 kernel: D0 <= 48 (F <= 7), wider ones are staged
 
 // packed buffer (floats):
 //   [b0 H][FW0 (kD0Pad/16)*NT*256][W0v 4*(H/4)*kW0Row]
@@ -97,28 +118,17 @@ __device__ __forceinline__ void softplus_b(float z, float beta, float& y, float&
   dy = lin ? 1.0f : sg;
 }
 
-struct IdrArgs {
-  float* pts; float* normals; uint8_t* mask; float* sdf_out; float* grad_out;
-  const int32_t* idx_in; const int32_t* count_in; int32_t* idx_out; int32_t* count_out;
-  const float* packed; float* stash;
-  int64_t n;
-  IdrShape s;
-  float beta, tol;
-  int do_move, eval_only;
-  // sphere tracing (iso_trace_idr): unit ray directions (n,3); null = Newton / evaluation
-  const float* dirs = nullptr;
-  float alpha = 1.f, bound = 0.f, tol_valid = 0.f;
-  int fwd_only = 0;          // 1: the gradient is not needed
-  // k_idr_step_x16: a counter, ZERO when the launch starts, the workgroups draw their next tile from (null: every
-  // gridDim-th tile -- the launch then ends with the slowest XCD, see x3_step_body in siren_x3.hip)
-  int32_t* tile_ctr = nullptr;
-};
-
 }  // namespace
 
-// ---- idr_x16.hip entry points -------------------------------------------------------------
+// Every launch entry sizes its own grid from n, an upper bound of the list's length, and its kernel's tile; -1: no kernel
+// of that code.
+// ---- idr_f32.hip entry points (idr_form's codes 1xx .. 3xx) -------------------------------
+int64_t idr_f32_stash_floats(int H, int n_layers);
+void idr_f32_pack(const float* raw, float* packed, const IdrShape& shape, hipStream_t s);
+int idr_f32_launch(int form, const IdrArgs& a, int64_t n, hipStream_t s);
+// ---- idr_x16.hip entry points (idr_form's codes 4xx / 5xx) --------------------------------
 bool idr_x16_supported(int H, int n_layers, int skip, int F);
 int64_t idr_x16_floats(int H, int n_layers);            // size of its section of the packed buffer
 int64_t idr_x16_stash_floats(int H, int n_layers);
-void idr_x16_pack(const float* raw, float* packed, int H, int n_layers, int skip, int F, hipStream_t s);
-int idr_x16_launch(const void* idr_args, int64_t n_upper, hipStream_t s);   // const IdrArgs*
+void idr_x16_pack(const float* raw, float* packed, const IdrShape& shape, hipStream_t s);
+int idr_x16_launch(int form, const IdrArgs& a, int64_t n, hipStream_t s);

@@ -11,12 +11,12 @@
 //    max|b_l| + ln2/beta, with the exact per-point maximum of the previous layer exchanged between
 //    the waves through LDS (as for the adjoint in siren_x3.hip);
 //  * skip connection: the narrow layer's padded output slots take the encoding, everything / sqrt(2)
-//    (the image layout of idr.hip: zero rows in the narrow layer, concat folded into the slots);
+//    (the image layout of idr_f32.hip: zero rows in the narrow layer, concat folded into the slots);
 //  * layer 0 reverse on the VALU straight from the registers: p_k = sum_f W0[f][k] a0[f] is
 //    multiplied by d e_k / d x_c as it is formed, only three sums per point leave the wave;
 //  * tanh on the head.
 // Two fp16 parts are exactly the bytes of one f32: LDS layout (64 points x 512 x 4 B) and weight
-// stream (1 MB per layer and direction) equal those of the f32 feature-split kernel of idr.hip
+// stream (1 MB per layer and direction) equal those of the f32 feature-split kernel of idr_f32.hip
 // while the matrix work drops 5.3x.
 #include <float.h>
 #include "idr_common.h"
@@ -558,17 +558,9 @@ __global__ __launch_bounds__(512, 1) void k_idr_step_x16(IdrArgs a) {
 }
 
 template <int H, int NB, bool FWD>
-int launch_i16(const IdrArgs& a, int64_t n_upper, hipStream_t st) {
+int launch_i16(const IdrArgs& a, int64_t n, hipStream_t st) {
   using S = I16Shape<H, NB>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_idr_step_x16<H, NB, FWD>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::kLds);
-    attr_done = true;
-  }
-  const int64_t tiles = (n_upper + S::P - 1) / S::P;
-  const int blocks = (int)(tiles < 256 ? (tiles < 1 ? 1 : tiles) : 256);
-  hipLaunchKernelGGL((k_idr_step_x16<H, NB, FWD>), dim3(blocks), dim3(512), S::kLds, st, a);
+  iso_launch_lds<k_idr_step_x16<H, NB, FWD>>(iso_capped_grid(n, S::P, kIdrBlocks), 512, S::kLds, st, a);
   return 0;
 }
 
@@ -582,23 +574,20 @@ bool idr_x16_supported(int H, int n_layers, int skip, int F) {
 }
 int64_t idr_x16_floats(int H, int n_layers) { return x16i_end(H, n_layers) - x16i_base(H, n_layers); }
 int64_t idr_x16_stash_floats(int H, int n_layers) {
-  if (H == 512) return 256 * I16Shape<512, 2>::kStashPerWg(n_layers);
-  if (H == 256) return 256 * I16Shape<256, 3>::kStashPerWg(n_layers);
+  if (H == 512) return kIdrBlocks * I16Shape<512, 2>::kStashPerWg(n_layers);
+  if (H == 256) return kIdrBlocks * I16Shape<256, 3>::kStashPerWg(n_layers);
   return 0;
 }
-void idr_x16_pack(const float* raw, float* packed, int H, int n_layers, int skip, int F, hipStream_t st) {
-  IdrShape s{H, n_layers, skip, F, 3 + 6 * F};
-  hipLaunchKernelGGL(k_idr16_stats, dim3(n_layers + 1), dim3(256), 0, st, raw, packed, s);
-  hipLaunchKernelGGL(k_idr16_pack, dim3(iso_stream_grid(idr_x16_floats(H, n_layers), 256)), dim3(256), 0, st, raw, packed, s);
+void idr_x16_pack(const float* raw, float* packed, const IdrShape& s, hipStream_t st) {
+  hipLaunchKernelGGL(k_idr16_stats, dim3(s.n_layers + 1), dim3(256), 0, st, raw, packed, s);
+  hipLaunchKernelGGL(k_idr16_pack, dim3(iso_stream_grid(idr_x16_floats(s.H, s.n_layers), 256)), dim3(256), 0, st, raw, packed, s);
 }
-int idr_x16_launch(const void* idr_args, int64_t n_upper, hipStream_t st) {
-  const IdrArgs& a = *static_cast<const IdrArgs*>(idr_args);
-  const int H = a.s.H;
-  if (a.fwd_only) {
-    if (H == 512) return launch_i16<512, 2, true>(a, n_upper, st);
-    if (H == 256) return launch_i16<256, 3, true>(a, n_upper, st);
+int idr_x16_launch(int form, const IdrArgs& a, int64_t n, hipStream_t st) {
+  switch (form) {
+    case 416: return launch_i16<256, 3, false>(a, n, st);
+    case 432: return launch_i16<512, 2, false>(a, n, st);
+    case 516: return launch_i16<256, 3, true>(a, n, st);
+    case 532: return launch_i16<512, 2, true>(a, n, st);
+    default: return -1;
   }
-  if (H == 512) return launch_i16<512, 2, false>(a, n_upper, st);
-  if (H == 256) return launch_i16<256, 3, false>(a, n_upper, st);
-  return -1;
 }

@@ -39,6 +39,17 @@ static inline int iso_capped_grid(int64_t rows, int block, int cap) {
   return g < 1 ? 1 : g;
 }
 
+// Launch kernel K with `lds` bytes of dynamic LDS: what lies above the default limit is asked for once per kernel.
+template <auto K, class Args>
+static inline void iso_launch_lds(int blocks, int threads, size_t lds, hipStream_t s, const Args& a) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    attr_done = true;
+  }
+  hipLaunchKernelGGL(K, dim3(blocks), dim3(threads), lds, s, a);
+}
+
 // Grid for an HBM-bound element-wise kernel: enough workgroups to fill 256 CUs
 // several times over, grid-stride the rest (guide: cap ~2048 blocks).
 static inline int iso_stream_grid(int64_t n, int block) {

@@ -41,7 +41,8 @@ __device__ __forceinline__ bool iso_trace_move(float f, float dx, float dy, floa
 }
 
 // What every step kernel does with the value f and gradient g of point `idx` (Args = SirenArgs /
-// IdrArgs: same field names).  Returns true when the point stays on the active list.
+// IdrArgs: same field names).  Returns true when the point stays on the active list.  (The ballot-and-one-atomic append that
+// follows it stays copied in the five step kernels: as a shared inlined helper every one of them compiled differently.)
 //   eval_only : store sdf (+ gradient when grad_out is given)
 //   dirs      : sphere tracing (levelset_sampling.py:735-779): store the value, mask = |f| <= tol_valid,
 //               still active = |f| > tol (the caller passes 0.1 * proj_tolerance) and inside the sphere

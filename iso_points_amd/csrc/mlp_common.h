@@ -1,4 +1,4 @@
-// Shared pieces of the fused-MLP kernels (siren_f32.hip, idr.hip): accurate sin/cos and the
+// Shared pieces of the fused-MLP kernels (siren_f32.hip, idr_f32.hip): accurate sin/cos and the
 // LDS-staged f32 MFMA layer pass.  See siren_f32.hip for the data-layout story.
 #pragma once
 #include "iso_common.h"
@@ -218,7 +218,7 @@ __device__ __forceinline__ void gemm_pass(const float* __restrict__ img,
 
 
 
-// Register-pipelined form of gemm_pass (used by idr.hip: one workgroup per CU, so nothing else hides
+// Register-pipelined form of gemm_pass (used by idr_f32.hip: one workgroup per CU, so nothing else hides
 // an LDS round trip).  Same staging protocol -- half q-chunks through two LDS buffers, one barrier
 // per half -- but the A fragments of half-chunk c+1 are read from LDS into a second register set
 // WHILE half-chunk c is multiplied (they were published by the previous barrier), the global loads

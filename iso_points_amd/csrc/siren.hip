@@ -1,6 +1,6 @@
 // Fused SIREN SDF path, gfx950: the C ABI (include/isopoints.h), the ONE decision which step kernel a call takes
-// (siren_form), the workspace carve and the iteration driver shared by the Newton projection, sphere tracing and the
-// plain evaluation (siren_run).  The step kernels are in siren_f32.hip (f32 MFMA) and siren_x3.hip (split fp16).
+// (siren_form), the workspace carve and the iteration set-up of the Newton projection, sphere tracing and the plain
+// evaluation (siren_run on sdf_driver.h).  The step kernels are in siren_f32.hip (f32 MFMA) and siren_x3.hip (split fp16).
 //
 // Reference semantics: Siren.forward (DSS/models/common.py:140-165, SineLayer :86-87) evaluated with autograd.grad inside
 // UniformProjection._compute_sdf_and_grad (levelset_sampling.py:142-170) and iterated by _project_points (:313-342).
@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "siren_common.h"
+#include "sdf_driver.h"
 
 namespace {
 
@@ -109,7 +110,6 @@ __global__ void k_siren_zero(int32_t* c, int n, int32_t* tc, int m) {
   if (i < m) tc[i] = 0;
 }
 
-struct SirenTrace { const float* dirs; float alpha, bound; };
 // code_bias / code_of as SirenCodedArgs documents them; null code_bias: the uncoded network (the image's own b0)
 struct SirenCodes { const float* bias; const int32_t* of; };
 
@@ -119,74 +119,46 @@ int siren_codes_ok(const char* who, const float* code_bias, const int32_t* code_
   return ISO_OK;
 }
 
-// The one body of iso_project_siren, iso_trace_siren (trace != null) and iso_siren_sdf_grad (eval_only), coded or not.
-// ptrs_ok: the entry's own pointers are there.  The iterations: launch `it` evaluates the list launch it-1 left
-// (device-side counts, no host read), the last one does not move.
-int siren_run(const char* who, bool ptrs_ok, const float* pts_in, float* pts_out, float* normals_out, uint8_t* mask_out,
-              float* sdf_out, float* grad_out, int64_t n, const float* packed, int hidden, int n_hidden, float omega_first,
-              float omega_hidden, int max_iters, float tol, void* workspace, int64_t workspace_bytes, void* stream,
-              bool eval_only, const SirenTrace* trace, SirenCodes codes) {
+// The one body of iso_project_siren, iso_trace_siren (c.dirs) and iso_siren_sdf_grad (c.eval_only), coded or not.
+// ptrs_ok: the entry's own pointers are there.  Around a launch of the shared schedule (sdf_driver.h): the pair of tile
+// counters of a split form, and from siren_tail_first on ONE tail launch for all the iterations left.
+int siren_run(const SdfCall& c, bool ptrs_ok, const float* packed, int hidden, int n_hidden, float omega_first,
+              float omega_hidden, void* workspace, int64_t workspace_bytes, void* stream, SirenCodes codes) {
   ISO_REQUIRE(siren_shape_ok(hidden, n_hidden), ISO_ERR_UNSUPPORTED,
-              "%s: hidden must be 64/128/256 and 0<=n_hidden<=8 (got %d, %d)", who, hidden, n_hidden);
-  ISO_REQUIRE(n >= 0 && max_iters >= 0 && max_iters <= 60, ISO_ERR_INVALID, "%s: bad n / max_iters (max 60)", who);
-  if (n == 0) return ISO_OK;
-  ISO_REQUIRE(n < (1ll << 31), ISO_ERR_UNSUPPORTED, "%s: n must fit int32", who);
-  ISO_REQUIRE(ptrs_ok && packed && workspace, ISO_ERR_INVALID, "%s: null pointer", who);
-  const SirenCarve c = siren_carve(n, hidden, n_hidden);
+              "%s: hidden must be 64/128/256 and 0<=n_hidden<=8 (got %d, %d)", c.who, hidden, n_hidden);
+  if (const int rc = sdf_call_check(c, ptrs_ok && packed && workspace)) return rc < 0 ? rc : ISO_OK;
+  const SirenCarve cv = siren_carve(c.n, hidden, n_hidden);
   // (an evaluation needs the stash alone; a workspace of the projection's size -- what the Python side allocates -- has
   // room for its two tile counters too)
-  ISO_REQUIRE(workspace_bytes >= (eval_only ? c.idxA : c.end), ISO_ERR_WORKSPACE, "%s: workspace too small", who);
+  ISO_REQUIRE(workspace_bytes >= (c.eval_only ? cv.idxA : cv.end), ISO_ERR_WORKSPACE, "%s: workspace too small", c.who);
   hipStream_t s = (hipStream_t)stream;
   auto at = [&](int64_t off) { return (int32_t*)((char*)workspace + off); };
-  const bool value_only = trace || (eval_only && !grad_out);     // forward sweep only where the kernel has one
-  const int form = siren_form(hidden, n_hidden, value_only, codes.bias != nullptr);
-  const bool dyn_tiles = form_splits(form) && g_dyn_tiles != 0;
-  SirenCodedArgs a;
-  a.packed = packed; a.stash = (float*)workspace; a.n = n; a.L = n_hidden;
-  a.w0 = omega_first; a.wh = omega_hidden; a.tol = tol;
-  a.fwd_only = value_only ? 1 : 0;
-  a.code_bias = codes.bias; a.code_of = codes.of;
-  if (eval_only) {
-    a.pts = const_cast<float*>(pts_in); a.normals = nullptr; a.mask = nullptr;
-    a.sdf_out = sdf_out; a.grad_out = grad_out;
-    a.idx_in = nullptr; a.count_in = nullptr; a.idx_out = nullptr; a.count_out = nullptr;
-    a.do_move = 0; a.eval_only = 1;
-    if (dyn_tiles && workspace_bytes >= c.end) {
-      hipLaunchKernelGGL(k_siren_zero, dim3(1), dim3(64), 0, s, at(c.tile_ctr), 2, nullptr, 0);
-      a.tile_ctr = at(c.tile_ctr);
-    }
-    ISO_REQUIRE(siren_launch_form(form, a, n, s) == 0, ISO_ERR_UNSUPPORTED, "%s: unsupported hidden size %d", who, hidden);
+  const int form = siren_form(hidden, n_hidden, c.value_only(), codes.bias != nullptr);
+  static_assert(2 * (kSdfMaxIters + 1) <= kTileCtrInts, "two tile counters per launch");
+  const bool dyn_tiles = form_splits(form) && g_dyn_tiles != 0 && workspace_bytes >= cv.end;
+  const int tail_from = siren_tail_first(form, c.max_iters);
+  if (c.eval_only) {
+    if (dyn_tiles) hipLaunchKernelGGL(k_siren_zero, dim3(1), dim3(64), 0, s, at(cv.tile_ctr), 2, nullptr, 0);
   } else {
-    if (pts_out != pts_in) (void)hipMemcpyAsync(pts_out, pts_in, (size_t)n * 12, hipMemcpyDeviceToDevice, s);
     const int blocks = siren_x3_tail_blocks();
-    const int tail_from = siren_tail_first(form, max_iters);
-    hipLaunchKernelGGL(k_siren_zero, dim3((2 * blocks + 255) / 256), dim3(256), 0, s, at(c.counts), 64 + kTileCtrInts,
-                       at(c.tail_counts), tail_from <= max_iters ? 2 * blocks : 0);
-    a.pts = pts_out; a.normals = normals_out; a.mask = mask_out; a.sdf_out = trace ? sdf_out : nullptr; a.grad_out = nullptr;
-    a.eval_only = 0;
-    if (trace) {                         // levelset_sampling.py:764,790: still active above 0.1 tol, valid up to tol
-      a.dirs = trace->dirs; a.alpha = trace->alpha; a.bound = trace->bound;
-      a.tol = 0.1f * tol; a.tol_valid = tol;
-    }
-    int32_t* idxA = at(c.idxA), *idxB = at(c.idxB), *counts = at(c.counts);
-    for (int it = 0; it <= max_iters; ++it) {
-      a.idx_in = (it == 0) ? nullptr : ((it & 1) ? idxA : idxB);
-      a.count_in = (it == 0) ? nullptr : counts + it;
-      a.idx_out = (it & 1) ? idxB : idxA;
-      a.count_out = counts + it + 1;
-      a.do_move = (it < max_iters) ? 1 : 0;
-      a.tile_ctr = (dyn_tiles && 2 * (max_iters + 1) <= kTileCtrInts) ? at(c.tile_ctr) + 2 * it : nullptr;
-      if (it >= tail_from && it > 0) {        // iterations it .. max_iters in one launch
-        a.tail_lists = at(c.tail); a.tail_counts = at(c.tail_counts); a.iter_counts = counts; a.tail_cap = (int)c.tail_cap;
-        a.it_first = it; a.it_last = max_iters;
-        ISO_REQUIRE(siren_x3_launch_tail(a, hidden, s) == 0, ISO_ERR_UNSUPPORTED, "%s: no tail kernel for hidden size %d", who, hidden);
-        break;
-      }
-      ISO_REQUIRE(siren_launch_form(form, a, n, s) == 0, ISO_ERR_UNSUPPORTED, "%s: unsupported hidden size %d", who, hidden);
-    }
+    hipLaunchKernelGGL(k_siren_zero, dim3((2 * blocks + 255) / 256), dim3(256), 0, s, at(cv.counts), 64 + kTileCtrInts,
+                       at(cv.tail_counts), tail_from <= c.max_iters ? 2 * blocks : 0);
   }
-  ISO_CHECK_LAUNCH(who);
-  return ISO_OK;
+  SirenCodedArgs a;
+  a.packed = packed; a.stash = (float*)workspace; a.L = n_hidden;
+  a.w0 = omega_first; a.wh = omega_hidden;
+  a.code_bias = codes.bias; a.code_of = codes.of;
+  return sdf_run(c, a, SdfLists{at(cv.idxA), at(cv.idxB), at(cv.counts)}, s, [&](SirenCodedArgs& x, int it) {
+    x.tile_ctr = dyn_tiles ? at(cv.tile_ctr) + 2 * it : nullptr;
+    if (it >= tail_from && it > 0) {        // iterations it .. max_iters in one launch
+      x.tail_lists = at(cv.tail); x.tail_counts = at(cv.tail_counts); x.iter_counts = at(cv.counts); x.tail_cap = (int)cv.tail_cap;
+      x.it_first = it; x.it_last = c.max_iters;
+      ISO_REQUIRE(siren_x3_launch_tail(x, hidden, s) == 0, ISO_ERR_UNSUPPORTED, "%s: no tail kernel for hidden size %d", c.who, hidden);
+      return kSdfStop;
+    }
+    ISO_REQUIRE(siren_launch_form(form, x, c.n, s) == 0, ISO_ERR_UNSUPPORTED, "%s: unsupported hidden size %d", c.who, hidden);
+    return ISO_OK;
+  });
 }
 
 }  // namespace
@@ -300,9 +272,9 @@ extern "C" int iso_siren_fold_codes(const float* w0c, const float* b0, const flo
 static int project_siren(const char* who, const float* pts_in, float* pts_out, float* normals_out, uint8_t* mask_out,
                          int64_t n, const float* packed, int hidden, int n_hidden, float omega_first, float omega_hidden,
                          int max_iters, float tol, void* workspace, int64_t workspace_bytes, void* stream, SirenCodes codes) {
-  return siren_run(who, pts_in && pts_out && normals_out && mask_out, pts_in, pts_out, normals_out, mask_out, nullptr,
-                   nullptr, n, packed, hidden, n_hidden, omega_first, omega_hidden, max_iters, tol, workspace,
-                   workspace_bytes, stream, false, nullptr, codes);
+  const SdfCall c = {who, pts_in, pts_out, normals_out, mask_out, nullptr, nullptr, n, max_iters, tol, false};
+  return siren_run(c, pts_in && pts_out && normals_out && mask_out, packed, hidden, n_hidden, omega_first, omega_hidden,
+                   workspace, workspace_bytes, stream, codes);
 }
 
 extern "C" int iso_project_siren(const float* pts_in, float* pts_out, float* normals_out,
@@ -330,10 +302,9 @@ static int trace_siren(const char* who, const float* ray0, const float* dirs, fl
                        uint8_t* mask_out, int64_t n, const float* packed, int hidden, int n_hidden, float omega_first,
                        float omega_hidden, float alpha, float bound, int max_iters, float tol, void* workspace,
                        int64_t workspace_bytes, void* stream, SirenCodes codes) {
-  const SirenTrace tr = {dirs, alpha, bound};
-  return siren_run(who, ray0 && dirs && pts_out && sdf_out && mask_out, ray0, pts_out, nullptr, mask_out, sdf_out, nullptr,
-                   n, packed, hidden, n_hidden, omega_first, omega_hidden, max_iters, tol, workspace, workspace_bytes,
-                   stream, false, &tr, codes);
+  const SdfCall c = {who, ray0, pts_out, nullptr, mask_out, sdf_out, nullptr, n, max_iters, tol, false, dirs, alpha, bound};
+  return siren_run(c, ray0 && dirs && pts_out && sdf_out && mask_out, packed, hidden, n_hidden, omega_first, omega_hidden,
+                   workspace, workspace_bytes, stream, codes);
 }
 
 extern "C" int iso_trace_siren(const float* ray0, const float* dirs, float* pts_out, float* sdf_out,
@@ -360,8 +331,9 @@ extern "C" int iso_trace_siren_coded(const float* ray0, const float* dirs, float
 static int sdf_grad_siren(const char* who, const float* pts, float* sdf_out, float* grad_out, int64_t n,
                           const float* packed, int hidden, int n_hidden, float omega_first, float omega_hidden,
                           void* workspace, int64_t workspace_bytes, void* stream, SirenCodes codes) {
-  return siren_run(who, pts && sdf_out, pts, nullptr, nullptr, nullptr, sdf_out, grad_out, n, packed, hidden, n_hidden,
-                   omega_first, omega_hidden, 0, 0.f, workspace, workspace_bytes, stream, true, nullptr, codes);
+  const SdfCall c = {who, pts, nullptr, nullptr, nullptr, sdf_out, grad_out, n, 0, 0.f, true};
+  return siren_run(c, pts && sdf_out, packed, hidden, n_hidden, omega_first, omega_hidden, workspace, workspace_bytes, stream,
+                   codes);
 }
 
 extern "C" int iso_siren_sdf_grad(const float* pts, float* sdf_out, float* grad_out,

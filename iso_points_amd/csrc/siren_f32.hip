@@ -248,14 +248,7 @@ constexpr int kSirenBlocks = 512;  // persistent: two workgroups per CU (80 KiB 
 
 template <int NT, bool CODED>
 int launch_step(const typename SirenArgsOf<CODED>::type& a, int blocks, hipStream_t s) {
-  const size_t lds = (size_t)(5 * NT * 256) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_step<NT, CODED>),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((k_siren_step<NT, CODED>), dim3(blocks), dim3(256), lds, s, a);
+  iso_launch_lds<k_siren_step<NT, CODED>>(blocks, 256, (size_t)(5 * NT * 256) * sizeof(float), s, a);
   return 0;
 }
 

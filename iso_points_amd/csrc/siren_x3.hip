@@ -849,16 +849,7 @@ template <int H, int NW, int NB, int MINB, bool FWD, bool CODED>
 int launch_x3(const typename SirenArgsOf<CODED>::type& a, int64_t n_upper, hipStream_t s) {
   using S = X3Shape<H, NW, NB>;
   static_assert(S::kLds <= 163840, "LDS of a gfx950 CU");
-  void (*kern)(typename SirenArgsOf<CODED>::type) = &k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)S::kLds);
-    attr_done = true;
-  }
-  const int64_t tiles = (n_upper + S::P - 1) / S::P;
-  const int64_t cap = 256 * MINB;
-  const int blocks = (int)(tiles < cap ? (tiles < 1 ? 1 : tiles) : cap);
-  hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NW), S::kLds, s, a);
+  iso_launch_lds<k_siren_step_x3<H, NW, NB, MINB, FWD, CODED>>(iso_capped_grid(n_upper, S::P, 256 * MINB), 64 * NW, S::kLds, s, a);
   return 0;
 }
 
@@ -879,11 +870,9 @@ int launch_x3_both(typename SirenArgsOf<CODED>::type a, int64_t n_upper, hipStre
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_done = true;
   }
-  const int64_t cap = 256 * MINB;
-  const int64_t tb = (n_upper + SB::P - 1) / SB::P, ts = (n_upper + SS::P - 1) / SS::P;
-  a.big_blocks = (int)(tb < cap ? (tb < 1 ? 1 : tb) : cap);
+  a.big_blocks = iso_capped_grid(n_upper, SB::P, 256 * MINB);
   a.split = 3;                 // (as SirenArgs documents it; the kernel gives each of its two shapes its own 1 / 2)
-  const int small_blocks = (int)(ts < cap ? (ts < 1 ? 1 : ts) : cap);
+  const int small_blocks = iso_capped_grid(n_upper, SS::P, 256 * MINB);
   hipLaunchKernelGGL(kern, dim3(a.big_blocks + small_blocks), dim3(64 * NW), lds, s, a);
   return 0;
 }
@@ -920,13 +909,7 @@ int siren_x3_tail_blocks() { return 256 * kMinB256; }
 template <bool CODED>
 static int launch_tail(const typename SirenArgsOf<CODED>::type& a, hipStream_t s) {
   using SS = X3Shape<256, kNW256, 1>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_siren_tail_x3<256, kNW256, kMinB256, CODED>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)SS::kLds);
-    attr_done = true;
-  }
-  hipLaunchKernelGGL((k_siren_tail_x3<256, kNW256, kMinB256, CODED>), dim3(siren_x3_tail_blocks()), dim3(64 * kNW256), SS::kLds, s, a);
+  iso_launch_lds<k_siren_tail_x3<256, kNW256, kMinB256, CODED>>(siren_x3_tail_blocks(), 64 * kNW256, SS::kLds, s, a);
   return 0;
 }
 

@@ -1,7 +1,8 @@
-"""Every kernel form of the fused IDR SDF path (csrc/idr.hip, csrc/idr_x16.hip: three kernels in twelve template instances,
-picked from hidden width, encoding width, value-only and the GEMM mode) against the float64 oracle: each form once, the
-limits of the accepted shapes, clouds that end inside a tile and take more than one round of workgroups, the Newton loop
-and the tracer on the forms no other test enters, and a mode switch between two calls on one packed model.
+"""Every kernel form of the fused IDR SDF path (csrc/idr_f32.hip, csrc/idr_x16.hip: three kernels in twelve template
+instances, picked by idr_form in csrc/idr.hip from hidden width, encoding width, value-only and the GEMM mode) against the
+float64 oracle: each form once, the limits of the accepted shapes, clouds that end inside a tile and take more than one
+round of workgroups, the Newton loop and the tracer on the forms no other test enters, a mode switch between two calls
+on one packed model, and 130 points through each family's launch entry at H = 256 and 512.
 
 Every case first asserts iso_idr_step_form: a re-dispatch fails here and not by silently testing another kernel.  CASES
 is also read by tests/test_idr_forms_cpu.py, which checks without a GPU that it reaches every k_idr_step* kernel of the
@@ -67,9 +68,16 @@ TRACE = [
     (512, 3, 2, 6, "f32", 232, 332),
     (512, 3, 2, 8, "split16", 132, 132),
 ]
+# (f) the two launch entries (idr_f32_launch, idr_x16_launch) at both widths either serves: 130 points
+BOUNDARY = [
+    (256, 3, 1, 6, "split16", 416, 516),
+    (512, 3, 2, 6, "split16", 432, 532),
+    (256, 3, 1, 6, "f32", 216, 316),
+    (512, 3, 2, 6, "f32", 232, 332),
+]
 # every (case, value_only) pair a test of this file launches: all of them evaluate with and without the gradient, except
 # the Newton cases (gradient only) and the tracer's (value only)
-CASES = [(c, v) for c in FORMS + LIMITS + [r[0] for r in RAGGED] for v in (0, 1)] + [(c, 0) for c in NEWTON] + \
+CASES = [(c, v) for c in FORMS + LIMITS + [r[0] for r in RAGGED] + BOUNDARY for v in (0, 1)] + [(c, 0) for c in NEWTON] + \
         [(c, 1) for c in TRACE]
 
 
@@ -292,3 +300,67 @@ def test_mode_switch_on_one_packed_model(dev, idr_mode, case):
         outs.append((sdf, grad))
     assert torch.equal(outs[0][0], outs[2][0]) and torch.equal(outs[0][1], outs[2][1])
     assert not torch.equal(outs[0][1], outs[1][1])            # (the f32 kernels did run: another rounding)
+
+
+# ---- (f) 130 points through each family's launch entry -------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _boundary_cloud(case):
+    """(network at its geometric initialisation ~ a sphere of radius 0.6, 130 points around it, the float32 oracle's
+    projection of them with three Newton iterations): made once per case."""
+    m = _network(case, perturb=False)
+    pts = sphere_cloud(130, seed=3) * 0.6
+    return m, pts, _O().project_points(m, pts, torch.tensor([130]), proj_max_iters=3)
+
+
+def _reference_at(m, pts):
+    """_reference's tuple for given points (n,3)."""
+    O = _O()
+    sdf32, grad32 = O.compute_sdf_and_grad(pts, m)
+    sdf64, grad64 = O.compute_sdf_and_grad(pts.double(), copy.deepcopy(m).double())
+    return m, pts, sdf32, grad32, sdf64, grad64
+
+
+@pytest.mark.parametrize("case", BOUNDARY, ids=_id)
+def test_projection_of_130_points_per_family_and_width(dev, idr_mode, case):
+    """130 points are two full 64-point tiles and a part tile (96 + 34 on k_idr_step_x16<256, 3>): three workgroups at
+    most, four launches on the two index lists (max_iters = 3, default tolerance: some points stop early, so the lists
+    shrink).  Positions against the float32 oracle's projection under assert_projection_close, as (d) does.  Against
+    float64: a point is last evaluated where it ends (a launch that moves a point keeps it on the list, the last launch
+    moves nothing), so the normals ARE the kernel's gradient at its own final positions and are held to the standing
+    margin on the gradient there, e_ref being torch's float32 gradient at those positions; and the mask is |f| <= tol, so
+    it must equal the float64 value's wherever that is further from the tolerance than the standing margin on the value."""
+    from iso_points_amd.levelset_sampling import UniformProjection, full_lengths
+    idr_mode(case[4])
+    _assert_forms(case)
+    m, pts, ref = _boundary_cloud(case)
+    x = pts.to(dev)
+    proj = UniformProjection()
+    res = proj._project_points(m, x, full_lengths(x), proj_max_iters=3)
+    assert_projection_close(res.points, ref.points)
+    _, _, sdf32, grad32, sdf64, grad64 = _reference_at(m, res.points.cpu()[0])
+    normals, mask = res.normals.cpu()[0], res.mask.cpu()[0]
+    assert bool(torch.isfinite(normals).all())
+    e_ref = (grad32.double() - grad64).abs().max().item()
+    e_hip = (normals.double() - grad64).abs().max().item()
+    r_grad = (normals.double() - grad32.double()).abs().max().item() / grad32.abs().max().item()
+    s_ref = (sdf32.double() - sdf64).abs().max().item()
+    decided = (sdf64.abs() - proj.proj_tolerance).abs() > 1.5 * s_ref + 2e-7
+    print("%s projection: e_ref %.3g e_hip %.3g rel vs f32 %.3g | s_ref %.3g, %d of 130 converged, %d within the margin of "
+          "the tolerance" % (_id(case), e_ref, e_hip, r_grad, s_ref, int(mask.sum()), int((~decided).sum())))
+    assert e_hip <= 1.5 * e_ref + 2e-6 and r_grad < 2e-5, (e_ref, e_hip, r_grad)
+    assert torch.equal(mask[decided], (sdf64.abs() <= proj.proj_tolerance)[decided])
+    assert 0 < int(mask.sum())                                  # (the lists did shrink: some points stopped)
+
+
+@pytest.mark.parametrize("case", BOUNDARY, ids=_id)
+def test_evaluation_of_130_points_per_family_and_width(dev, idr_mode, case):
+    """The same 130 points through iso_idr_sdf_grad with grad_out and without it (the gradient form and the value form of
+    either entry), under the standing margin."""
+    from iso_points_amd.sdf_models import PackedIdr
+    idr_mode(case[4])
+    _assert_forms(case)
+    m, pts, _ = _boundary_cloud(case)
+    ref = _reference_at(m, pts[0])
+    sdf, grad = _evaluate(case, PackedIdr(m, dev), m, pts[0].to(dev))
+    assert sdf.shape == (130,) and grad.shape == (130, 3)
+    _assert_margin("%s n=130 forms %d/%d" % (_id(case), case[5], case[6]), sdf, grad, ref)

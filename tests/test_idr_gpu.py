@@ -1,4 +1,4 @@
-"""Fused IDR-style SDF kernel (iso_points_amd/csrc/idr.hip) vs the oracle's restatement of the
+"""Fused IDR-style SDF kernel (iso_points_amd/csrc/idr.hip, idr_f32.hip, idr_x16.hip) vs the oracle's restatement of the
 reference SDF class (pinned through tests/golden/idr_small.npz) and vs float64."""
 import copy
 

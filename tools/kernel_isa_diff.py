@@ -1,17 +1,20 @@
 #!/usr/bin/env python3
 """Compare the gfx950 machine code of two build trees kernel by kernel.
 
-    python tools/kernel_isa_diff.py TREE_A TREE_B [file stems ...] > report.txt
+    python tools/kernel_isa_diff.py TREE_A TREE_B [file stems ...] [OLD=NEW] > report.txt
 
 Every `hipcc ... -c csrc/X.hip` line that `make -n -B` prints in a tree is re-run there as a device-only `-S` compile, so each
 file gets exactly the flags of that tree's Makefile.  The assembly is cut at the function symbols (kernels and
 non-inlined device functions; a kernel's descriptor block belongs to it), comments are dropped and the numbers of local
 labels -- which count the functions of a translation unit -- are normalised.  Moving a kernel to another file must leave
 it `identical`.  Exit status 1 when any symbol is not.  File stems restrict the compile to those files of either tree.
+OLD=NEW: a regular expression and its replacement, applied to both trees' assembly before it is cut -- for a change that
+renames a type and so the parameter suffix of every mangled kernel name, and nothing else.
 """
 import concurrent.futures, os, re, subprocess, sys, tempfile
 
 LOCAL = re.compile(r"\.L(BB|JTI|func_begin|func_end|tmp)\d+")
+RENAME = []                          # [(OLD, NEW)] or empty
 
 
 def compile_lines(tree, stems):
@@ -29,6 +32,8 @@ def functions(tree, src, cmd):
         asm = os.path.join(tmp, "out.s")
         subprocess.run(cmd + ["--cuda-device-only", "-S", src, "-o", asm], cwd=tree, check=True)
         text = open(asm).read()
+    for old, new in RENAME:
+        text = re.sub(old, new, text)
     found = {}
     for sym in re.findall(r"^\t\.type\t(\S+),@function$", text, re.M):
         body = re.search(rf"^{re.escape(sym)}:.*?^\.Lfunc_end\d+:", text, re.M | re.S).group(0)
@@ -63,4 +68,5 @@ def main(a, b, *stems):
 if __name__ == "__main__":
     if len(sys.argv) < 3:
         sys.exit(__doc__)
-    sys.exit(main(*sys.argv[1:]))
+    RENAME += [tuple(w.split("=", 1)) for w in sys.argv[3:] if "=" in w]
+    sys.exit(main(*(w for w in sys.argv[1:] if "=" not in w)))
