@@ -1369,6 +1369,52 @@ int iso_meshraster_pixels(const float* face_verts, int n_meshes, int64_t n_faces
                            int perspective_correct, const int32_t* tile_off, const int32_t* pairs, int64_t pair_capacity,
                            int64_t* pix_to_face, float* zbuf, float* bary, float* dists, void* stream);
 
+/* ----------------------------------------------------------------------
+ * N. Mesh extraction: the level set of a sampled SDF as an indexed triangle mesh (csrc/mesh_extract.hip)
+ *    stands where the reference copies the volume to the host for skimage.measure.marching_cubes_lewiner:
+ *      DSS/utils/__init__.py:569-655                  get_surface_high_res_mesh (both of its extractions, :582 and :635),
+ *                                                     called by Generator.generate_mesh (DSS/models/implicit_modeling.py:
+ *                                                     680-700), DSS/training/trainer.py:201, :254, :723, :887,
+ *                                                     generate_mvr.py:75 and test_dtu_points.py:289, :322
+ *    Not Lewiner's marching cubes and not bit for bit skimage's: marching tetrahedra on the Kuhn split, exact and
+ *    deterministic by construction, about twice as many faces (tests/mesh_extract_oracle.py restates the
+ *    rule in numpy, float32 and float64).
+ *
+ *    The rule.  values (nx,ny,nz) f32, C-contiguous; grid point (i,j,k) has linear index p = (i ny + j) nz + k and lies at
+ *    origin + (i,j,k) * spacing, each coordinate one f32 multiplication and one addition.  A point is INSIDE iff its value is
+ *    finite and < iso; a value equal to iso, NaN and +-inf are outside.
+ *    Every point owns 7 slots, the mesh edges that START at it, in the order +x, +y, +z, +xy, +xz, +yz, +xyz.  A slot exists
+ *    if its far end is in the grid and is ACTIVE if exactly one of its ends is inside.  An active slot carries one vertex,
+ *    pa + t (pb - pa) per coordinate with t = (iso - va) / (vb - va), a the owning (lower) end: float32, IEEE division, no
+ *    FMA contraction; t = 0.5 if va or vb is not finite (never interpolated).  Vertex index = the exclusive scan of the
+ *    active flags in (p, slot) order.
+ *    A cell is cut into six tetrahedra around its diagonal 000-111: 000 -> +e_a -> +e_a+e_b -> 111 for the permutations
+ *    (a,b,c) of the axes in lexicographic order; neighbouring cells share every face diagonal, so there are no cracks.  A
+ *    tetrahedron with corners P0..P3 and 1 or 3 of them inside gives the triangle (AB, AC, AD), A the lone corner, B < C < D
+ *    the others, XY the vertex on edge XY; with A < B inside and C < D outside the triangles (AC, AD, BD), (AC, BD, BC).
+ *    The last two corners are swapped where needed for the right-hand normal to point to the outside corners (towards
+ *    larger values); csrc/mesh_extract.hip derives the 16 cases at compile time.  Faces are ordered by cell (linear index of
+ *    its lowest point), tetrahedron, triangle; face index = the exclusive scan of the cells' counts.  Zero-area faces
+ *    (t = 0: a value on the level) are kept.  No atomics: the same input gives the same bits on every run and stream.
+ *
+ * iso_meshextract_workspace_bytes: 17 bytes per grid point (the slots' mask, two counts, two offsets) plus the tiles'
+ *   partial sums and iso_prefix_sum's workspace; 0 for sizes outside the limits.  16-byte aligned.
+ * iso_meshextract_count: pass 1 (4 x 4 x 64 tiles with a one-point halo through LDS), the 64-bit totals and the scan
+ *   (iso_prefix_sum over both count rows).  totals (device, 2 x i64) = the number of vertices and of faces.  Enqueues on
+ *   `stream`, does not synchronise.
+ * iso_meshextract_emit: pass 2 on the workspace iso_meshextract_count left, same values and iso: verts (V,3) f32, faces
+ *   (F,3) i32.  Reads `totals` back (16 bytes, synchronises the stream) and refuses capacities below them with
+ *   ISO_ERR_INVALID; verts / faces may be NULL where the total is 0.  spacing > 0.
+ * Limits: 2 <= nx, ny, nz (ISO_ERR_INVALID below) <= 1024 (ISO_ERR_UNSUPPORTED above); fewer than 2^31 vertices and fewer
+ *   than 2^31 faces (ISO_ERR_UNSUPPORTED from iso_meshextract_emit; the totals themselves are exact).
+ *   (The entries are iso_meshextract_*, in one word, as section M's are: the prefix iso_mesh_ is section I's.)         */
+int64_t iso_meshextract_workspace_bytes(int nx, int ny, int nz);
+int iso_meshextract_count(const float* values, int nx, int ny, int nz, float iso, int64_t* totals, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+int iso_meshextract_emit(const float* values, int nx, int ny, int nz, float ox, float oy, float oz, float sx, float sy,
+                          float sz, float iso, const int64_t* totals, float* verts, int64_t vert_capacity, int32_t* faces,
+                          int64_t face_capacity, const void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -187,6 +187,9 @@ SIGNATURES = {
     "iso_meshraster_count": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P]),
     "iso_meshraster_fill": (_I, [_P, _P, _P, _I, _L, _I, _I, _P, _P, _P, _L, _P]),
     "iso_meshraster_pixels": (_I, [_P, _I, _L, _I, _I, _I, _P, _P, _L, _P, _P, _P, _P, _P]),
+    "iso_meshextract_workspace_bytes": (_L, [_I, _I, _I]),
+    "iso_meshextract_count": (_I, [_P, _I, _I, _I, _F, _P, _P, _L, _P]),
+    "iso_meshextract_emit": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _L, _P, _L, _P, _L, _P]),
 }
 
 class Follow(ctypes.Structure):

@@ -10,9 +10,14 @@ counting-sorted lists of the loss module: no float atomics, values and gradients
 sample_points_from_meshes_even is the even sampling the reference takes from trimesh.sample.sample_surface_even
 (config.py:227, DSS/training/trainer.py:255) and pcu.sample_mesh_poisson_disk (DSS/utils/dataset.py:123): the same draw, three
 times as long, followed by the Poisson-disk elimination of include/isopoints.h section L.
+
+marching_tetrahedra, sdf_grid, mesh_components / largest_component and get_surface_high_res_mesh are the way back: the
+model's level set as a mesh, where the reference runs skimage's marching cubes and trimesh on the host
+(DSS/utils/__init__.py:569-700; include/isopoints.h section N).
 """
 import math
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -222,3 +227,241 @@ def mesh_face_areas_normals(verts, faces):
     normals = torch.empty((F, 3), dtype=torch.float32, device=tris.device)
     _lib.call("iso_mesh_face_areas", _lib.ptr(tris), F, _lib.ptr(areas), _lib.ptr(normals), _lib.stream())
     return areas, normals
+
+
+# ----------------------------------------------------------------------------- the level set as a mesh
+_GRID_MAX = 1024
+
+
+def marching_tetrahedra(values, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0), level=0.0):
+    """The level set {values = level} of a volume sampled on a regular grid as an indexed triangle mesh: (verts (V,3)
+    float32, faces (F,3) int64), where the reference calls skimage.measure.marching_cubes_lewiner
+    (DSS/utils/__init__.py:582, :635).  Marching tetrahedra on the Kuhn split, not Lewiner's cubes: every vertex lies on
+    a grid edge or a cell's face / body diagonal at the zero of the linear interpolant, about twice as many faces, closed
+    and consistently oriented wherever the surface does not leave the grid (include/isopoints.h section N has the rule).
+
+    values (nx,ny,nz), each n in [2, 1024]; grid point (i,j,k) lies at origin + (i,j,k) * spacing (three floats each,
+    spacing > 0).  A point is inside iff its value is finite and < level; normals point to larger values.  Vertices and
+    faces come in a fixed order (by owning grid point and slot; by cell, tetrahedron, triangle) and the same input gives
+    the same bits on every run.  A volume without a sign change gives (0,3) tensors.  Faces without area (a value exactly
+    on the level) are kept.  Host reads: the two totals, to size the outputs (the library reads the same 16 bytes once
+    more to check the outputs' sizes).  No gradient."""
+    fn = "marching_tetrahedra"
+    if not torch.is_tensor(values) or values.dim() != 3:
+        raise ValueError("%s: values must be a (nx, ny, nz) tensor" % fn)
+    nx, ny, nz = values.shape
+    if min(nx, ny, nz) < 2 or max(nx, ny, nz) > _GRID_MAX:
+        raise ValueError("%s: every side must be in [2, %d], got %d x %d x %d" % (fn, _GRID_MAX, nx, ny, nz))
+    org, spc, level = [float(o) for o in origin], [float(s) for s in spacing], float(level)
+    if len(org) != 3 or len(spc) != 3 or not all(math.isfinite(o) for o in org) or \
+            not all(s > 0.0 and math.isfinite(s) for s in spc) or not math.isfinite(level):
+        raise ValueError("%s: origin and spacing are three finite floats each, spacing > 0, and level is finite" % fn)
+    _on_gpu(values)
+    vol = values.detach().float().contiguous()
+    dev = vol.device
+    ws_bytes = _lib.load().iso_meshextract_workspace_bytes(nx, ny, nz)
+    ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
+    totals = torch.empty((2,), dtype=torch.int64, device=dev)
+    p = _lib.ptr
+    _lib.call("iso_meshextract_count", p(vol), nx, ny, nz, level, p(totals), p(ws), ws_bytes, _lib.stream())
+    V, F = totals.tolist()
+    if V >= _ROW_LIMIT or F >= _ROW_LIMIT:
+        raise ValueError("%s: %d vertices and %d faces; the limit is 2^31 - 1 of each" % (fn, V, F))
+    verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+    _lib.call("iso_meshextract_emit", p(vol), nx, ny, nz, org[0], org[1], org[2], spc[0], spc[1], spc[2], level, p(totals),
+              p(verts) if V else None, V, p(faces) if F else None, F, p(ws), ws_bytes, _lib.stream())
+    return verts, faces.long()
+
+
+def _sdf_device(sdf):
+    from .sdf_models import FusedSdf
+    model = sdf.model if isinstance(sdf, FusedSdf) else sdf
+    if isinstance(model, torch.nn.Module):
+        for t in list(model.parameters()) + list(model.buffers()):
+            return t.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _fused(sdf, device):
+    """The fused evaluator of `sdf` (a FusedSdf on the SIREN or IDR kernels), or None."""
+    from .sdf_models import FusedSdf, idr_spec, siren_spec
+    if isinstance(sdf, FusedSdf):
+        return sdf if sdf.kind in ("siren", "idr") else None
+    if siren_spec(sdf) is not None or idr_spec(sdf) is not None:
+        return FusedSdf(sdf, device)
+    return None
+
+
+def _sdf_values(sdf, pts, chunk=100000):
+    """sdf at pts (n,3) -> (n,) float32: the fused value-only kernels in one launch where the model has them, any other
+    callable in chunks of 100 000 points as the reference does (DSS/utils/__init__.py:575)."""
+    from .sdf_models import FusedSdf
+    fused = _fused(sdf, pts.device)
+    if fused is not None:
+        return fused(pts).reshape(-1).float()
+    fn = sdf.model if isinstance(sdf, FusedSdf) else sdf
+    out = []
+    with torch.no_grad():
+        for part in torch.split(pts, chunk, dim=0):
+            val = fn(part)
+            out.append(getattr(val, "sdf", val).reshape(-1).float())
+    return torch.cat(out) if out else pts.new_zeros((0,))
+
+
+def sdf_grid(sdf, resolution, box_side_length=2.0, points=None):
+    """The SDF sampled on a grid: (values (nx,ny,nz) float32, origin, spacing), ready for marching_tetrahedra.
+
+    Without `points` the grid is get_grid_uniform's (DSS/utils/__init__.py:554-566): resolution^3 points,
+    linspace(-0.5, 0.5, resolution) * box_side_length along every axis, values[i,j,k] = sdf(x_i, y_j, z_k); origin and
+    spacing are three floats each.  With `points` (nx,ny,nz,3) the SDF is evaluated there -- a rotated grid, say -- and
+    origin and spacing are None: the caller made the grid and knows its frame.
+
+    sdf: a FusedSdf, or a model that siren_spec / idr_spec accept, runs on the fused value-only kernels in one launch; any
+    other callable (points (n,3) -> values, or an object with .sdf) is called on chunks of 100 000 points."""
+    fn = "sdf_grid"
+    if points is not None:
+        if not torch.is_tensor(points) or points.dim() != 4 or points.shape[-1] != 3:
+            raise ValueError("%s: points must be (nx, ny, nz, 3)" % fn)
+        _on_gpu(points)
+        pts = points.detach().float().reshape(-1, 3).contiguous()
+        return _sdf_values(sdf, pts).reshape(points.shape[:3]), None, None
+    n = int(resolution)
+    if n < 2:
+        raise ValueError("%s: resolution must be at least 2" % fn)
+    dev = _sdf_device(sdf)
+    if dev.type != "cuda":
+        raise RuntimeError("iso_points_amd: the model must be on the GPU; there is no CPU path")
+    axis64 = np.linspace(-0.5, 0.5, n) * float(box_side_length)
+    axis = torch.from_numpy(axis64.astype(np.float32)).to(dev)
+    pts = torch.stack(torch.meshgrid(axis, axis, axis, indexing="ij"), dim=-1).reshape(-1, 3).contiguous()
+    origin, spacing = (float(axis64[0]),) * 3, (float(axis64[1] - axis64[0]),) * 3
+    return _sdf_values(sdf, pts).reshape(n, n, n), origin, spacing
+
+
+def mesh_components(verts, faces):
+    """Connected components of a mesh over shared vertex indices, what trimesh's split(only_watertight=False) groups by
+    (DSS/utils/__init__.py:595, :651): (labels (F,) int64, areas (C,) float64).  Components are numbered by their lowest
+    vertex index; areas[c] is the float64 sum of the face areas of component c, in face order.  Plain torch on the tensors'
+    device: minimum-label hooking with pointer jumping, one host read per round (a few rounds), and one for C."""
+    fn = "mesh_components"
+    if not torch.is_tensor(verts) or verts.dim() != 2 or verts.shape[-1] != 3:
+        raise ValueError("%s: verts must be (V, 3)" % fn)
+    if not torch.is_tensor(faces) or faces.dim() != 2 or faces.shape[-1] != 3 or faces.is_floating_point():
+        raise ValueError("%s: faces must be an integer tensor (F, 3)" % fn)
+    faces = faces.long()
+    dev = faces.device
+    if faces.shape[0] == 0:
+        return torch.zeros((0,), dtype=torch.int64, device=dev), torch.zeros((0,), dtype=torch.float64, device=dev)
+    u = torch.cat([faces[:, 0], faces[:, 1], faces[:, 2], faces[:, 1], faces[:, 2], faces[:, 0]])
+    v = torch.cat([faces[:, 1], faces[:, 2], faces[:, 0], faces[:, 0], faces[:, 1], faces[:, 2]])
+    parent = torch.arange(verts.shape[0], dtype=torch.int64, device=dev)
+    while True:
+        # parent[x] <= x always.  At a fixed point every parent is a root and equal across every edge: the component's
+        # lowest vertex
+        grand = parent[parent]
+        nxt = parent.scatter_reduce(0, parent[u], grand[v], "amin")      # hook the parent ...
+        nxt = nxt.scatter_reduce(0, u, grand[v], "amin")                 # ... and the vertex to the neighbour's grandparent
+        nxt = torch.minimum(nxt, grand)                                   # pointer jumping
+        if torch.equal(nxt, parent):
+            break
+        parent = nxt
+    _roots, labels = torch.unique(parent[faces[:, 0]], return_inverse=True)
+    tri = verts.detach().double()[faces]
+    area = 0.5 * torch.linalg.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]).norm(dim=1)
+    order = torch.argsort(labels, stable=True)
+    run = torch.cat([area.new_zeros(1), torch.cumsum(area[order], 0)])    # a scan, not atomics: the same bits every run
+    size = torch.bincount(labels)
+    ends = torch.cumsum(size, 0)
+    return labels, run[ends] - run[ends - size]
+
+
+def _largest(verts, faces):
+    labels, areas = mesh_components(verts, faces)
+    if areas.numel() == 0:
+        return verts[:0], faces.long()[:0]
+    kept = faces.long()[labels == areas.argmax()]
+    used = torch.zeros((verts.shape[0],), dtype=torch.bool, device=verts.device)
+    used[kept.reshape(-1)] = True
+    return verts[used], (torch.cumsum(used, 0) - 1)[kept]
+
+
+def largest_component(verts, faces):
+    """(verts, faces) of the component of largest area (the first of equals), as the reference keeps
+    components[areas.argmax()] (DSS/utils/__init__.py:595-597, :650-653): vertices that no kept face uses are dropped and
+    the faces re-indexed; the order of what stays is unchanged."""
+    return _largest(verts, faces)
+
+
+def _sdf_normals(sdf, verts):
+    """Unit SDF gradients at verts: the fused gradient kernel where the model has one, autograd otherwise."""
+    from .sdf_models import FusedSdf, idr_sdf_and_grad, siren_sdf_and_grad
+    fused = _fused(sdf, verts.device)
+    if fused is not None:
+        grad_fn = siren_sdf_and_grad if fused.kind == "siren" else idr_sdf_and_grad
+        grad = grad_fn(fused.model, verts, need_grad=True, packed=fused.packed)[1]
+    else:
+        fn = sdf.model if isinstance(sdf, FusedSdf) else sdf
+        grads = []
+        for part in torch.split(verts.detach(), 100000, dim=0):
+            with torch.enable_grad():
+                x = part.clone().requires_grad_(True)
+                val = fn(x)
+                grads.append(torch.autograd.grad(getattr(val, "sdf", val).sum(), x)[0])
+        grad = torch.cat(grads) if grads else verts.new_zeros((0, 3))
+    return grad / grad.norm(dim=-1, keepdim=True).clamp_min(1e-30)
+
+
+def _aligned_grid(lo, hi, resolution):
+    """get_grid (DSS/utils/__init__.py:658-696) from the bounding box of the aligned samples: `resolution` points along the
+    shortest axis over [min - 0.2, max + 0.2], the same step along the other two.  (origin (3,), step, sizes (3,))"""
+    eps = 0.2
+    short = int(np.argmin(hi - lo))
+    axis = np.linspace(lo[short] - eps, hi[short] + eps, resolution)
+    step = (axis.max() - axis.min()) / (resolution - 1)
+    sizes = [resolution if d == short else len(np.arange(lo[d] - eps, hi[d] + step + eps, step)) for d in range(3)]
+    return lo - eps, float(step), sizes
+
+
+def get_surface_high_res_mesh(sdf, resolution=100, box_side_length=2.0, largest_component=True, return_normals=False,
+                              generator=None):
+    """The SDF's zero level set as a mesh, by the steps of the reference's get_surface_high_res_mesh
+    (DSS/utils/__init__.py:569-655): a 64^3 mesh over the box -> its largest component -> 10 000 surface samples
+    (sample_points_from_meshes, seeded through `generator`) -> their PCA frame -> the aligned grid of get_grid with
+    `resolution` points along its shortest side -> the extraction on that grid -> rotated back -> the largest component.
+
+    Returns (verts (V,3) float32, faces (F,3) int64) on the model's device, with return_normals also the unit SDF gradient
+    at every vertex (V,3); tensors, not a trimesh object, and empty ones where the SDF has no sign change on a grid (the
+    reference returns an empty Trimesh).  Not the reference's triangles: marching_tetrahedra is not Lewiner's marching
+    cubes; the PCA axes come in ascending order of variance; normals are SDF gradients, not skimage's volume gradients.
+    Host reads: the totals of both extractions, the component rounds, the 3 x 3 covariance and the samples' bounding box."""
+    keep_largest, res = bool(largest_component), int(resolution)
+    if res < 2:
+        raise ValueError("get_surface_high_res_mesh: resolution must be at least 2")
+
+    def result(verts, faces):
+        return (verts, faces, _sdf_normals(sdf, verts)) if return_normals else (verts, faces)
+    values, origin, spacing = sdf_grid(sdf, 64, box_side_length)
+    verts, faces = marching_tetrahedra(values, origin, spacing)
+    if faces.shape[0] == 0:
+        return result(verts, faces)
+    verts, faces = _largest(verts, faces)
+    cloud = sample_points_from_meshes((verts[None], faces[None]), 10000, generator=generator)[0]
+    mean = cloud.mean(dim=0)
+    centred = cloud - mean
+    cov = (centred.t() @ centred).double().cpu()
+    vecs = torch.linalg.eigh(cov)[1].t().contiguous()                     # rows: the axes, ascending variance
+    if torch.det(vecs) < 0:
+        vecs = vecs[[0, 2, 1]]
+    vecs = vecs.to(device=cloud.device, dtype=torch.float32)
+    aligned = centred @ vecs.t()
+    box = torch.stack([aligned.amin(dim=0), aligned.amax(dim=0)]).double().cpu().numpy()
+    lo, step, sizes = _aligned_grid(box[0], box[1], res)
+    axes = [torch.from_numpy((lo[d] + step * np.arange(sizes[d])).astype(np.float32)).to(cloud.device) for d in range(3)]
+    grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1)
+    values = sdf_grid(sdf, None, points=grid @ vecs + mean)[0]
+    verts, faces = marching_tetrahedra(values, [float(x) for x in lo], (step,) * 3)
+    verts = verts @ vecs + mean
+    if keep_largest:
+        verts, faces = _largest(verts, faces)
+    return result(verts, faces)
