@@ -1415,6 +1415,61 @@ int iso_meshextract_emit(const float* values, int nx, int ny, int nz, float ox, 
                           float sz, float iso, const int64_t* totals, float* verts, int64_t vert_capacity, int32_t* faces,
                           int64_t face_capacity, const void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ----------------------------------------------------------------------
+ * O. Block-sparse mesh extraction: section N's rule over a list of bricks of grid points (csrc/mesh_extract_sparse.hip)
+ *    Work and memory follow the surface's area, not the box; sides go up to 4096 (DESIGN.md 3.4k;
+ *    tests/mesh_sparse_oracle.py restates this section in numpy).
+ *
+ *    The grid.  (nx,ny,nz) points, each n in [2, 4096].  The inside test, the 7 slots of a point, the Kuhn split, the 16
+ *    triangle cases, the vertex's arithmetic and the winding are section N's, from the same text (csrc/mesh_tables.h).
+ *    Bricks.  Brick b = (bx,by,bz) holds the grid points with index 8 b_d .. 8 b_d + 7 per axis, clipped by the grid; there
+ *    are ceil(n_d / 8) bricks per axis.  CELL-BLOCK b holds the cells whose base (lowest) point lies in brick b.  A sparse
+ *    volume is
+ *      coords (S,3) i32       the listed bricks, sorted by linear brick index (bx nby + by) nbz + bz and unique,
+ *      values (S,8,8,8) f32   values[s][i][j][k] at grid point 8 coords[s] + (i,j,k); entries outside the grid are ignored,
+ *      cell_active (S) u8     non-zero: the cells of cell-block coords[s] are marched.
+ *    Every grid point is stored once: no halo, no duplicated sample.  The caller GUARANTEES that for a cell-active b every
+ *    brick b + {0,1}^3 that exists in the grid is in the list (the sampled set); the library does not check it (a triangle
+ *    corner whose owner is missing gets index -1; nothing is read or written out of bounds).
+ *    Live slots.  Slot s of point p (offset code(s) in {1..7}, x = 1, y = 2, z = 4) is contained in the cells with base
+ *    p - d for the offsets d in {0,1}^3 with d & code(s) == 0; they lie in cell-block b or a lower neighbour b - {0,1}^3.
+ *    The slot is LIVE iff at least one of those cells exists and lies in a cell-active block; by the guarantee both its ends
+ *    are then sampled.  A live slot whose ends differ in the inside test carries a vertex.  A cell is marched iff it
+ *    exists and its block is cell-active.
+ *    Order.  Vertices by brick in list order, then local point index (i 8 + j) 8 + k, then slot; faces by cell-block in list
+ *    order, then local cell, tetrahedron, triangle.  Indices are one exclusive scan over S * 512 counts; no atomics on
+ *    global memory, no hashing, no welding: the same input gives the same bits on every run and stream.
+ *    Keys.  vert_key (V) i64 = 7 p + slot and face_cell (F) i64 = p of the cell's base, p = (i ny + j) nz + k the dense
+ *    linear index.  Sorted by these keys the sparse mesh is section N's mesh of the same volume restricted to the cells of
+ *    the cell-active blocks; if every cell with a sign change lies in one, it is section N's mesh, vertex bits and faces.
+ *    Need.  need (S) u8, bit o (o in {0,1}^3 as a code) of brick b: some slot owned by a point of b carries a vertex (live,
+ *    ends differ) and is also contained in an existing cell of block b - o that is not cell-active.  The surface leaves the
+ *    cell-active set exactly there; if no bit is set the mesh is closed wherever the surface does not leave the grid.
+ *
+ * iso_meshextract_sparse_workspace_bytes: 4 bytes per brick OF THE GRID (the table brick -> list slot, -1 = not listed:
+ *   8 MB at 1024^3, 512 MB at 4096^3) plus 17 bytes per listed grid point, the bricks' sums and iso_prefix_sum's
+ *   workspace; 0 outside the limits.  16-byte aligned.
+ * iso_meshextract_sparse_count: fills the table, pass 1 (one workgroup per listed brick; the 9 x 9 x 9 values its cells
+ *   touch are gathered through the table into LDS), need, the totals and the scan.  totals (device, 4 x i64) = vertices,
+ *   faces, set need bits over all bricks, bricks whose coords lie outside the grid (such a brick counts nothing).
+ *   Enqueues on `stream`, does not synchronise.
+ * iso_meshextract_sparse_emit: pass 2 on the workspace the count left, same arguments: verts (V,3) f32, faces (F,3) i32,
+ *   and vert_key (V) / face_cell (F) i64 where not NULL.  Reads `totals` back (32 bytes, synchronises the stream): coords
+ *   outside the grid and capacities below the totals are ISO_ERR_INVALID; verts / faces may be NULL where the total is 0.
+ * Limits: 2 <= nx, ny, nz (ISO_ERR_INVALID below) <= 4096 (ISO_ERR_UNSUPPORTED above); 1 <= S (ISO_ERR_INVALID) and
+ *   S * 512 < 2^31 (ISO_ERR_UNSUPPORTED); fewer than 2^31 vertices and fewer than 2^31 faces (ISO_ERR_UNSUPPORTED from
+ *   iso_meshextract_sparse_emit).  Unsorted or repeated coords are the caller's to refuse (ops.marching_tetrahedra_bricks
+ *   does): the kernels stay in bounds on them, the order of the output is then not the one stated above.           */
+int64_t iso_meshextract_sparse_workspace_bytes(int nx, int ny, int nz, int64_t n_bricks);
+int iso_meshextract_sparse_count(const float* values, const int32_t* coords, const uint8_t* cell_active, int64_t n_bricks,
+                                  int nx, int ny, int nz, float iso, uint8_t* need, int64_t* totals, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
+int iso_meshextract_sparse_emit(const float* values, const int32_t* coords, const uint8_t* cell_active, int64_t n_bricks,
+                                 int nx, int ny, int nz, float ox, float oy, float oz, float sx, float sy, float sz, float iso,
+                                 const int64_t* totals, float* verts, int64_t vert_capacity, int32_t* faces,
+                                 int64_t face_capacity, int64_t* vert_key, int64_t* face_cell, const void* workspace,
+                                 int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

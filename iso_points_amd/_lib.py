@@ -190,6 +190,10 @@ SIGNATURES = {
     "iso_meshextract_workspace_bytes": (_L, [_I, _I, _I]),
     "iso_meshextract_count": (_I, [_P, _I, _I, _I, _F, _P, _P, _L, _P]),
     "iso_meshextract_emit": (_I, [_P, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _L, _P, _L, _P, _L, _P]),
+    "iso_meshextract_sparse_workspace_bytes": (_L, [_I, _I, _I, _L]),
+    "iso_meshextract_sparse_count": (_I, [_P, _P, _P, _L, _I, _I, _I, _F, _P, _P, _P, _L, _P]),
+    "iso_meshextract_sparse_emit": (_I, [_P, _P, _P, _L, _I, _I, _I, _F, _F, _F, _F, _F, _F, _F, _P, _P, _L, _P, _L, _P, _P, _P,
+                                         _L, _P]),
 }
 
 class Follow(ctypes.Structure):

@@ -15,6 +15,7 @@ marching_tetrahedra, sdf_grid, mesh_components / largest_component and get_surfa
 model's level set as a mesh, where the reference runs skimage's marching cubes and trimesh on the host
 (DSS/utils/__init__.py:569-700; include/isopoints.h section N).
 """
+import contextlib
 import math
 
 import numpy as np
@@ -274,6 +275,307 @@ def marching_tetrahedra(values, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0),
     return verts, faces.long()
 
 
+# ----------------------------------------------------------------------------- ... block-sparse (section O)
+_SPARSE_MAX = 4096
+_BRICK = 8
+_OFFSETS = ((0, 0, 0), (1, 0, 0), (0, 1, 0), (1, 1, 0), (0, 0, 1), (1, 0, 1), (0, 1, 1), (1, 1, 1))    # index = x + 2 y + 4 z
+
+
+def _grid_args(fn, grid_size, origin, spacing, level):
+    size = [int(n) for n in grid_size]
+    if len(size) != 3 or min(size) < 2 or max(size) > _SPARSE_MAX:
+        raise ValueError("%s: grid_size is three sides in [2, %d], got %r" % (fn, _SPARSE_MAX, tuple(grid_size)))
+    org, spc, level = [float(o) for o in origin], [float(s) for s in spacing], float(level)
+    if len(org) != 3 or len(spc) != 3 or not all(math.isfinite(o) for o in org) or \
+            not all(s > 0.0 and math.isfinite(s) for s in spc) or not math.isfinite(level):
+        raise ValueError("%s: origin and spacing are three finite floats each, spacing > 0, and level is finite" % fn)
+    return size, org, spc, level
+
+
+def _brick_dims(size):
+    return [(n + _BRICK - 1) // _BRICK for n in size]
+
+
+def _brick_lin(coords, nb):
+    c = coords.long()
+    return (c[:, 0] * nb[1] + c[:, 1]) * nb[2] + c[:, 2]
+
+
+def _brick_unlin(lin, nb):
+    return torch.stack([lin // (nb[1] * nb[2]), (lin // nb[2]) % nb[1], lin % nb[2]], dim=1)
+
+
+def _upper_neighbours(lin, nb):
+    """The bricks b + {0,1}^3 of the blocks `lin` that exist in the grid: sorted unique linear indices."""
+    b = _brick_unlin(lin, nb)
+    off = torch.tensor(_OFFSETS, dtype=torch.int64, device=lin.device)
+    q = (b[:, None, :] + off[None]).reshape(-1, 3)
+    lim = torch.tensor(nb, dtype=torch.int64, device=lin.device)
+    q = q[(q < lim).all(dim=1)]
+    return torch.unique((q[:, 0] * nb[1] + q[:, 1]) * nb[2] + q[:, 2])
+
+
+class _SparseCount:
+    """One count pass on a sorted brick list: the workspace, need (S,) uint8 and totals (4,) int64 = vertices, faces, set
+    need bits, bricks outside the grid, all on the device; emit() then writes the mesh."""
+
+    def __init__(self, values, coords, cell_active, size, level):
+        S, dev = coords.shape[0], values.device
+        self.args = (values, coords, cell_active, S, size, level)
+        self.ws_bytes = _lib.load().iso_meshextract_sparse_workspace_bytes(size[0], size[1], size[2], S)
+        if self.ws_bytes <= 0:
+            raise ValueError("marching_tetrahedra_bricks: %d bricks on a %d x %d x %d grid are outside the limits "
+                             "(sides in [2, %d], fewer than 2^31 / 512 bricks)" % (S, size[0], size[1], size[2], _SPARSE_MAX))
+        self.ws = torch.empty((self.ws_bytes,), dtype=torch.uint8, device=dev)
+        self.need = torch.empty((S,), dtype=torch.uint8, device=dev)
+        self.totals = torch.empty((4,), dtype=torch.int64, device=dev)
+        p = _lib.ptr
+        _lib.call("iso_meshextract_sparse_count", p(values), p(coords), p(cell_active), S, size[0], size[1], size[2], level,
+                  p(self.need), p(self.totals), p(self.ws), self.ws_bytes, _lib.stream())
+
+    def emit(self, org, spc, return_keys):
+        values, coords, cell_active, S, size, level = self.args
+        dev = values.device
+        V, F = self.totals[:2].tolist()
+        if V >= _ROW_LIMIT or F >= _ROW_LIMIT:
+            raise ValueError("marching_tetrahedra_bricks: %d vertices and %d faces; the limit is 2^31 - 1 of each" % (V, F))
+        verts = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        faces = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        vkey = torch.empty((V,), dtype=torch.int64, device=dev) if return_keys else None
+        fcell = torch.empty((F,), dtype=torch.int64, device=dev) if return_keys else None
+        p = _lib.ptr
+        _lib.call("iso_meshextract_sparse_emit", p(values), p(coords), p(cell_active), S, size[0], size[1], size[2], org[0],
+                  org[1], org[2], spc[0], spc[1], spc[2], level, p(self.totals), p(verts) if V else None, V,
+                  p(faces) if F else None, F, p(vkey) if V and return_keys else None, p(fcell) if F and return_keys else None,
+                  p(self.ws), self.ws_bytes, _lib.stream())
+        return (verts, faces.long(), vkey, fcell) if return_keys else (verts, faces.long())
+
+
+def marching_tetrahedra_bricks(values, coords, cell_active, grid_size, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0),
+                               level=0.0, return_keys=False, return_need=False):
+    """marching_tetrahedra over a list of 8 x 8 x 8 bricks of grid points instead of the whole volume (include/isopoints.h
+    section O): (verts (V,3) float32, faces (F,3) int64[, vert_key (V,) int64, face_cell (F,) int64][, need (S,) uint8]).
+
+    grid_size = (nx, ny, nz), each in [2, 4096].  coords (S,3) integer: brick b holds the grid points 8 b .. 8 b + 7 per
+    axis; values (S,8,8,8) float32, values[s,i,j,k] at grid point 8 coords[s] + (i,j,k) (entries outside the grid are
+    ignored); cell_active (S,) bool or uint8: the cells whose lowest point lies in brick s are marched.  For every
+    cell-active b all bricks b + {0,1}^3 that exist in the grid must be in the list (checked).  coords must be unique; they
+    need not be sorted: the list is sorted by linear brick index (bx nby + by) nbz + bz here, and `need` comes back in the
+    caller's order.
+
+    The rule is marching_tetrahedra's.  Vertices are ordered by brick (sorted), local point, slot; faces by brick, local
+    cell, tetrahedron, triangle.  vert_key = 7 p + slot and face_cell = p, p = (i ny + j) nz + k the dense linear index of
+    the owning point / the cell's lowest point: sorted by them the mesh is the dense mesh of the same volume restricted to
+    the cells of the cell-active bricks, bit for bit.  need[s] bit o (o = x + 2 y + 4 z in {0,1}^3): a vertex of brick s
+    lies on a mesh edge that also belongs to a cell of block coords[s] - o which is not cell-active; no bit set anywhere =
+    the surface does not leave the cell-active set.  Host reads: the totals, and the checks of the list.  No gradient."""
+    fn = "marching_tetrahedra_bricks"
+    size, org, spc, level = _grid_args(fn, grid_size, origin, spacing, level)
+    if not torch.is_tensor(coords) or coords.dim() != 2 or coords.shape[1] != 3 or coords.is_floating_point():
+        raise ValueError("%s: coords must be an integer tensor (S, 3)" % fn)
+    S = coords.shape[0]
+    if not torch.is_tensor(values) or tuple(values.shape) != (S, _BRICK, _BRICK, _BRICK):
+        raise ValueError("%s: values must be (S, 8, 8, 8) for coords (S, 3)" % fn)
+    if not torch.is_tensor(cell_active) or tuple(cell_active.shape) != (S,) or cell_active.is_floating_point():
+        raise ValueError("%s: cell_active must be a bool or uint8 tensor (S,)" % fn)
+    if S * _BRICK ** 3 >= _ROW_LIMIT:
+        raise ValueError("%s: %d bricks; the limit is 2^31 - 1 grid points in all" % (fn, S))
+    _on_gpu(values, coords, cell_active)
+    dev = values.device
+    nb = _brick_dims(size)
+
+    def empty():
+        out = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev))
+        if return_keys:
+            out = out + (torch.empty((0,), dtype=torch.int64, device=dev),) * 2
+        return out + (torch.zeros((S,), dtype=torch.uint8, device=dev),) if return_need else out
+    if S == 0:
+        return empty()
+    c64 = coords.long()
+    lim = torch.tensor(nb, dtype=torch.int64, device=dev)
+    if bool(((c64 < 0) | (c64 >= lim)).any()):
+        raise ValueError("%s: coords outside the grid of %d x %d x %d bricks" % ((fn,) + tuple(nb)))
+    lin, order = torch.sort(_brick_lin(c64, nb))
+    if S > 1 and bool((lin[1:] == lin[:-1]).any()):
+        raise ValueError("%s: coords holds a brick twice" % fn)
+    active = (cell_active != 0)[order]
+    want = _upper_neighbours(lin[active], nb)
+    at = torch.searchsorted(lin, want).clamp(max=S - 1)
+    if bool((lin[at] != want).any()):
+        raise ValueError("%s: a cell-active brick lacks one of its neighbours b + {0,1}^3 in the list" % fn)
+    run = _SparseCount(values.detach().float()[order].contiguous(), c64[order].int().contiguous(),
+                       active.to(torch.uint8).contiguous(), size, level)
+    out = run.emit(org, spc, return_keys)
+    if return_need:
+        need = torch.empty_like(run.need)
+        need[order] = run.need
+        out = out + (need,)
+    return out
+
+
+def _brick_points(lin, nb, size, axes, rotation, translation):
+    """The sample points of the bricks `lin`: (len(lin) * 512, 3) float32, brick by brick in local order (i 8 + j) 8 + k.
+    An index past the grid's end is clamped into it: its value is never looked at."""
+    dev = lin.device
+    b = _brick_unlin(lin, nb)
+    r = torch.arange(_BRICK, device=dev)
+    cols = []
+    for d in range(3):
+        idx = (b[:, d, None] * _BRICK + r[None]).clamp(max=size[d] - 1)             # (S, 8)
+        shape = [lin.shape[0], 1, 1, 1]
+        shape[d + 1] = _BRICK
+        cols.append(axes[d][idx].reshape(shape).expand(-1, _BRICK, _BRICK, _BRICK))
+    pts = torch.stack(cols, dim=-1).reshape(-1, 3)
+    if rotation is not None:
+        pts = pts @ rotation
+    if translation is not None:
+        pts = pts + translation
+    return pts.contiguous()
+
+
+def sparse_level_set(sdf, grid_size, origin=None, spacing=None, *, axes=None, band=1.5, seeds=None, rotation=None,
+                     translation=None, level=0.0, max_rounds=64, return_info=False, return_keys=False,
+                     _timer=None):
+    """The level set {sdf = level} on a regular grid of up to 4096 points per side as (verts (V,3) float32, faces (F,3) int64
+    [, vert_key (V,) int64, face_cell (F,) int64][, info]), evaluating the SDF only in 8 x 8 x 8 bricks of grid points near the surface: marching_tetrahedra_bricks on
+    the bricks that a seeding finds and a closure loop completes.  Where the bricks cover the surface the mesh is
+    marching_tetrahedra's on the full volume, up to the order of its vertices and faces (by brick here; return_keys gives
+    marching_tetrahedra_bricks' keys to sort them back).
+
+    Grid point (i,j,k) lies at origin + (i,j,k) * spacing in float32, or at (axes[0][i], axes[1][j], axes[2][k]) for three
+    1-D float32 tensors `axes` (sdf_grid's linspace, say; they must be evenly spaced: origin and spacing, which place the
+    vertices, default to axes[d][0] and the mean step).  The SDF is evaluated at point @ rotation + translation where given
+    (the vertices stay in the grid's frame, as get_surface_high_res_mesh's aligned grid has it).  sdf: as sdf_grid takes it.
+
+    Seeds.  By band: cell-block b (the cells whose lowest point has index 8 b .. 8 b + 7 per axis) is a seed iff
+    |sdf(c) - level| <= band * R_b at the grid point c = min(8 b + 4, n - 1) per axis, R_b the largest distance from c to a
+    corner of the block's cells; band = 1 is conservative for an exact distance, the default leaves room for a trained
+    network's gradient norm, band = 0 (or None) switches it off and saves the evaluation of one point per block.  By points:
+    the blocks that contain the cells of `seeds` (N,3), given in the grid's frame -- iso-points, samples of a coarse mesh.
+    Closure.  The newly added bricks are evaluated, the count pass reports where the surface leaves the cell-active blocks
+    (need), those blocks are added, until none is reported; so a surface component that touches one seed is extracted whole,
+    whatever the SDF's Lipschitz constant.  RuntimeError after max_rounds count passes that still report a need.
+
+    info: rounds, cell_active_bricks, sampled_bricks, seed_blocks, points_evaluated (bricks * 512 plus the band's test
+    points), workspace_bytes.  Host reads: 8 bytes per round (the number of set need bits), the totals, and the sizes of the
+    torch set operations on the block lists.  No gradient.  (_timer: tools/mesh_sparse_timing.py's stage clock, a callable
+    name -> context manager.)"""
+    fn = "sparse_level_set"
+    stage = _timer if _timer is not None else (lambda name: contextlib.nullcontext())
+    if axes is not None:
+        if len(axes) != 3 or not all(torch.is_tensor(a) and a.dim() == 1 and a.shape[0] == int(n) for a, n in zip(axes, grid_size)):
+            raise ValueError("%s: axes are three 1-D tensors of grid_size points" % fn)
+        _on_gpu(*axes)
+        axes = [a.detach().float().contiguous() for a in axes]
+        if origin is None:
+            origin = [float(a[0]) for a in axes]
+        if spacing is None:
+            spacing = [(float(a[-1]) - float(a[0])) / (a.shape[0] - 1) for a in axes]
+    elif origin is None or spacing is None:
+        raise ValueError("%s: give origin and spacing, or axes" % fn)
+    size, org, spc, level = _grid_args(fn, grid_size, origin, spacing, level)
+    max_rounds = int(max_rounds)
+    if max_rounds < 1:
+        raise ValueError("%s: max_rounds must be at least 1" % fn)
+    dev = _sdf_device(sdf) if axes is None else axes[0].device
+    if dev.type != "cuda":
+        raise RuntimeError("iso_points_amd: the model must be on the GPU; there is no CPU path")
+    if axes is None:
+        o32 = torch.tensor(org, dtype=torch.float32, device=dev)
+        s32 = torch.tensor(spc, dtype=torch.float32, device=dev)
+        axes = [o32[d] + torch.arange(size[d], dtype=torch.float32, device=dev) * s32[d] for d in range(3)]
+    if rotation is not None:
+        rotation = rotation.detach().to(device=dev, dtype=torch.float32)
+    if translation is not None:
+        translation = translation.detach().to(device=dev, dtype=torch.float32)
+    nb = _brick_dims(size)
+    n_cells = [(n - 1 + _BRICK - 1) // _BRICK for n in size]          # blocks per axis that hold a cell
+    evaluated = 0
+
+    # ---- seeds: sorted linear indices of cell-blocks
+    active = torch.empty((0,), dtype=torch.int64, device=dev)
+    if band is not None and float(band) > 0.0:
+        band = float(band)
+        test, reach = [], []
+        for d in range(3):
+            b = torch.arange(n_cells[d], device=dev)
+            c = (b * _BRICK + 4).clamp(max=size[d] - 1)
+            hi = (b * _BRICK + _BRICK).clamp(max=size[d] - 1)
+            test.append(axes[d][c])
+            reach.append(torch.maximum(c - b * _BRICK, hi - c).double() * spc[d])
+        pts = torch.stack(torch.meshgrid(*test, indexing="ij"), dim=-1).reshape(-1, 3)
+        if rotation is not None:
+            pts = pts @ rotation
+        if translation is not None:
+            pts = pts + translation
+        with stage("seed"):
+            f = _sdf_values(sdf, pts.contiguous()).double()
+        evaluated += pts.shape[0]
+        R = torch.sqrt(reach[0][:, None, None] ** 2 + reach[1][None, :, None] ** 2 + reach[2][None, None, :] ** 2).reshape(-1)
+        hit = torch.nonzero((f - level).abs() <= band * R).reshape(-1)
+        active = (hit // (n_cells[1] * n_cells[2]) * nb[1] + (hit // n_cells[2]) % n_cells[1]) * nb[2] + hit % n_cells[2]
+    if seeds is not None:
+        if not torch.is_tensor(seeds) or seeds.dim() != 2 or seeds.shape[1] != 3:
+            raise ValueError("%s: seeds must be (N, 3)" % fn)
+        _on_gpu(seeds)
+        o64 = torch.tensor(org, dtype=torch.float64, device=dev)
+        s64 = torch.tensor(spc, dtype=torch.float64, device=dev)
+        cell = torch.floor((seeds.detach().double() - o64) / s64)
+        top = torch.tensor([n - 2 for n in size], dtype=torch.float64, device=dev)
+        cell = cell[torch.isfinite(cell).all(dim=1) & (cell >= -1).all(dim=1) & (cell <= top + 1).all(dim=1)]
+        blk = torch.minimum(cell.clamp(min=0), top).long() // _BRICK
+        active = torch.cat([active, (blk[:, 0] * nb[1] + blk[:, 1]) * nb[2] + blk[:, 2]])
+    active = torch.unique(active)
+    n_seeds = active.shape[0]
+    empty = (torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int64, device=dev))
+    if return_keys:
+        empty = empty + (torch.empty((0,), dtype=torch.int64, device=dev),) * 2
+    info = {"rounds": 0, "cell_active_bricks": 0, "sampled_bricks": 0, "seed_blocks": n_seeds, "points_evaluated": evaluated,
+            "workspace_bytes": 0}
+    if n_seeds == 0:
+        return empty + (info,) if return_info else empty
+
+    # ---- closure
+    lin = torch.empty((0,), dtype=torch.int64, device=dev)                                # the sampled bricks, sorted
+    values = torch.empty((0, _BRICK, _BRICK, _BRICK), dtype=torch.float32, device=dev)
+    off = torch.tensor(_OFFSETS, dtype=torch.int64, device=dev)
+    rounds = 0
+    while True:
+        want = _upper_neighbours(active, nb)
+        fresh = want[~torch.isin(want, lin)] if lin.shape[0] else want
+        if fresh.shape[0]:
+            if (lin.shape[0] + fresh.shape[0]) * _BRICK ** 3 >= _ROW_LIMIT:
+                raise ValueError("%s: more than 2^31 - 1 grid points in the sampled bricks" % fn)
+            parts = []
+            with stage("evaluate"):
+                for chunk in torch.split(fresh, 32768):                                    # 16.8 M points at a time
+                    parts.append(_sdf_values(sdf, _brick_points(chunk, nb, size, axes, rotation, translation)))
+            evaluated += fresh.shape[0] * _BRICK ** 3
+            lin, order = torch.sort(torch.cat([lin, fresh]))
+            values = torch.cat([values, torch.cat(parts).reshape(-1, _BRICK, _BRICK, _BRICK)])[order].contiguous()
+        S = lin.shape[0]
+        flags = torch.isin(lin, active).to(torch.uint8)
+        coords = _brick_unlin(lin, nb).int().contiguous()
+        with stage("count"):
+            run = _SparseCount(values, coords, flags, size, level)
+        rounds += 1
+        if int(run.totals[2]) == 0:                                                        # the round's one host read
+            break
+        if rounds >= max_rounds:
+            raise RuntimeError("%s: the surface still leaves the cell-active blocks after %d rounds (max_rounds); %d blocks "
+                               "are active" % (fn, rounds, active.shape[0]))
+        more = []
+        for o in range(8):
+            b = coords[((run.need >> o) & 1).bool()].long() - off[o]
+            more.append((b[:, 0] * nb[1] + b[:, 1]) * nb[2] + b[:, 2])
+        active = torch.unique(torch.cat([active] + more))
+    with stage("emit"):
+        out = run.emit(org, spc, bool(return_keys))
+    info.update(rounds=rounds, cell_active_bricks=int(active.shape[0]), sampled_bricks=S, points_evaluated=evaluated,
+                workspace_bytes=int(run.ws_bytes))
+    return out + (info,) if return_info else out
+
+
 def _sdf_device(sdf):
     from .sdf_models import FusedSdf
     model = sdf.model if isinstance(sdf, FusedSdf) else sdf
@@ -424,7 +726,7 @@ def _aligned_grid(lo, hi, resolution):
 
 
 def get_surface_high_res_mesh(sdf, resolution=100, box_side_length=2.0, largest_component=True, return_normals=False,
-                              generator=None):
+                              generator=None, sparse=False):
     """The SDF's zero level set as a mesh, by the steps of the reference's get_surface_high_res_mesh
     (DSS/utils/__init__.py:569-655): a 64^3 mesh over the box -> its largest component -> 10 000 surface samples
     (sample_points_from_meshes, seeded through `generator`) -> their PCA frame -> the aligned grid of get_grid with
@@ -434,7 +736,11 @@ def get_surface_high_res_mesh(sdf, resolution=100, box_side_length=2.0, largest_
     at every vertex (V,3); tensors, not a trimesh object, and empty ones where the SDF has no sign change on a grid (the
     reference returns an empty Trimesh).  Not the reference's triangles: marching_tetrahedra is not Lewiner's marching
     cubes; the PCA axes come in ascending order of variance; normals are SDF gradients, not skimage's volume gradients.
-    Host reads: the totals of both extractions, the component rounds, the 3 x 3 covariance and the samples' bounding box."""
+    Host reads: the totals of both extractions, the component rounds, the 3 x 3 covariance and the samples' bounding box.
+
+    sparse=True takes the second extraction through sparse_level_set on the same aligned grid, seeded by band and by the
+    10 000 samples: the SDF is evaluated near the surface only and `resolution` may go past marching_tetrahedra's 1024
+    points per side, up to 4096 on the longest side.  The default is the dense path, unchanged."""
     keep_largest, res = bool(largest_component), int(resolution)
     if res < 2:
         raise ValueError("get_surface_high_res_mesh: resolution must be at least 2")
@@ -458,9 +764,13 @@ def get_surface_high_res_mesh(sdf, resolution=100, box_side_length=2.0, largest_
     box = torch.stack([aligned.amin(dim=0), aligned.amax(dim=0)]).double().cpu().numpy()
     lo, step, sizes = _aligned_grid(box[0], box[1], res)
     axes = [torch.from_numpy((lo[d] + step * np.arange(sizes[d])).astype(np.float32)).to(cloud.device) for d in range(3)]
-    grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1)
-    values = sdf_grid(sdf, None, points=grid @ vecs + mean)[0]
-    verts, faces = marching_tetrahedra(values, [float(x) for x in lo], (step,) * 3)
+    if sparse:
+        verts, faces = sparse_level_set(sdf, sizes, [float(x) for x in lo], (step,) * 3, axes=axes, seeds=aligned,
+                                        rotation=vecs, translation=mean)
+    else:
+        grid = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1)
+        values = sdf_grid(sdf, None, points=grid @ vecs + mean)[0]
+        verts, faces = marching_tetrahedra(values, [float(x) for x in lo], (step,) * 3)
     verts = verts @ vecs + mean
     if keep_largest:
         verts, faces = _largest(verts, faces)
