@@ -97,7 +97,8 @@ int iso_siren_pack_weights(const float* raw, float* packed, int hidden,
  *                sweep -- and three partial products are accumulated in f32: same error level as an
  *                f32 GEMM (the accumulation dominates), 5.3x the MFMA rate.  H in {128,256},
  *                n_hidden >= 1.
- *   0            f32 matrix cores (v_mfma_f32_16x16x4_f32; bitwise an fmaf chain).
+ *   0            f32 matrix cores (v_mfma_f32_16x16x4_f32: a sum over the H inputs is two fmaf chains, over the even and
+ *                the odd chunks of 16 inputs, added at the end).
  * Shapes mode 1 does not cover run in mode 0.  ISO_SIREN_GEMM=f32 in the environment selects 0. */
 int iso_siren_set_gemm_mode(int mode);
 int iso_siren_get_gemm_mode(void);

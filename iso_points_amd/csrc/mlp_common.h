@@ -130,38 +130,45 @@ __device__ __forceinline__ void iso_wcos8(float w_in, float w, const float (&z)[
   }
 }
 
+template <int V> struct IsoInt { static constexpr int value = V; };
+
 template <int NT, bool HAS_BIAS>
 __device__ __forceinline__ void gemm_pass(const float* __restrict__ img,
                                           const float* __restrict__ bias,
                                           const float* __restrict__ hL,
                                           float* __restrict__ wbuf, f32x4 (&acc)[NT],
-                                          int lane, int g, int nq = NT) {
-  // One pass = nq q-chunks (nq = NT for a square layer); each q-chunk is staged in two halves of TC = NT/2 tiles so
+                                          int lane, int g) {
+  // One pass = NT q-chunks of 16 input features (a square H x H layer: the chunk count used to be a parameter that no
+  // caller passed); each q-chunk is staged in two halves of TC = NT/2 tiles so
   // that the LDS stage is 2 x (NT/2) KiB and two workgroups fit on a CU.  All A
   // fragments of a half are requested up front (TC ds_read_b128 in flight) and the MFMAs
   // consume them as they land.  (Without the LDS stage -- every wave streaming its own fragments from L2, no barrier --
   // the pass measured 84 instead of 98 TFLOP/s on the bench workload.)
+  //
+  // Order of the sums.  An output is NOT one fmaf chain over all H inputs: the even q-chunks go to one accumulator
+  // (which starts at the bias), the odd ones to a second, and the two are added at the end.  One chain of H roundings
+  // put the mean gradient error of an 8-layer network at 1.6 .. 1.7 x that of torch's float32 path against float64
+  // (tests/test_siren_forms_gpu.py; restated in numpy the chain alone reproduces the figure, the sine does not matter);
+  // two chains of H / 2 measure 1.3 x (the split-fp16 kernels, whose MFMA sums 16 exact products per rounding: 1.25 x).
+  // To keep the registers of one accumulator per tile, the pass takes the two halves of the output tiles one after the
+  // other -- all q-chunks of tiles 0 .. TC-1, then all of tiles TC .. NT-1: the same half-chunks through the same two LDS
+  // buffers with the same barriers, in another order (NT = 16: 228 VGPRs instead of 204, still two workgroups per CU).
   constexpr int TC = NT / 2;              // tiles per staged half
   constexpr int CH = TC * 256;            // floats per half-chunk
   constexpr int NV = CH / 4;              // float4 per half-chunk
   constexpr int PER = (NV + 255) / 256;   // float4 per thread per half-chunk
+  constexpr int NC = 2 * NT;              // half-chunks of the pass
   static_assert(NT % 2 == 0, "NT must be even");
   const int tid = threadIdx.x;
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    if constexpr (HAS_BIAS) {
-      acc[t] = *reinterpret_cast<const f32x4*>(bias + 16 * t + 4 * g);
-    } else {
-      acc[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    }
-  }
   constexpr bool FULL = (NV % 256) == 0;  // every thread moves PER float4 (no tail guard)
-  // Two register sets: the global loads of half-chunk c+2 are issued while chunk c is
-  // multiplied and chunk c+1 (loaded one stage earlier) is written to the other LDS buffer,
+  // position i of the schedule -> half-chunk of the image (laid out [q][half]): i < NT is (q = i, half 0), then half 1
+  auto chunk_of = [](int i) { return i < NT ? 2 * i : 2 * (i - NT) + 1; };
+  // Two register sets: the global loads of half-chunk i+2 are issued while half-chunk i is
+  // multiplied and half-chunk i+1 (loaded one stage earlier) is written to the other LDS buffer,
   // so a load has two MFMA stages (~2k cycles) to land before it is needed.
   f32x4 sx[PER], sy[PER];
-  auto gload = [&](f32x4 (&r)[PER], int c) {
-    const f32x4* src = reinterpret_cast<const f32x4*>(img + (int64_t)c * CH);
+  auto gload = [&](f32x4 (&r)[PER], int i) {
+    const f32x4* src = reinterpret_cast<const f32x4*>(img + (int64_t)chunk_of(i) * CH);
 #pragma unroll
     for (int k = 0; k < PER; ++k)
       if (FULL || tid + 256 * k < NV) r[k] = src[tid + 256 * k];
@@ -172,8 +179,8 @@ __device__ __forceinline__ void gemm_pass(const float* __restrict__ img,
     for (int k = 0; k < PER; ++k)
       if (FULL || tid + 256 * k < NV) dst[tid + 256 * k] = r[k];
   };
-  auto stage = [&](int half, const f32x4& b4) {
-    const f32x4* wa = reinterpret_cast<const f32x4*>(wbuf + half * CH);
+  auto stage = [&](int buf, const f32x4& b4, f32x4 (&part)[TC]) {
+    const f32x4* wa = reinterpret_cast<const f32x4*>(wbuf + buf * CH);
     f32x4 a4[TC];
 #pragma unroll
     for (int t = 0; t < TC; ++t) a4[t] = wa[t * 64 + lane];
@@ -182,16 +189,47 @@ __device__ __forceinline__ void gemm_pass(const float* __restrict__ img,
     __builtin_amdgcn_sched_barrier(0);
     // k-major: consecutive MFMAs hit different accumulators (32 cycles issue, 40 dependent latency)
 #pragma unroll
-    for (int t = 0; t < TC; ++t) acc[half * TC + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t].x, b4.x, acc[half * TC + t], 0, 0, 0);
+    for (int t = 0; t < TC; ++t) part[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t].x, b4.x, part[t], 0, 0, 0);
 #pragma unroll
-    for (int t = 0; t < TC; ++t) acc[half * TC + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t].y, b4.y, acc[half * TC + t], 0, 0, 0);
+    for (int t = 0; t < TC; ++t) part[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t].y, b4.y, part[t], 0, 0, 0);
 #pragma unroll
-    for (int t = 0; t < TC; ++t) acc[half * TC + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t].z, b4.z, acc[half * TC + t], 0, 0, 0);
+    for (int t = 0; t < TC; ++t) part[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t].z, b4.z, part[t], 0, 0, 0);
 #pragma unroll
-    for (int t = 0; t < TC; ++t) acc[half * TC + t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t].w, b4.w, acc[half * TC + t], 0, 0, 0);
+    for (int t = 0; t < TC; ++t) part[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a4[t].w, b4.w, part[t], 0, 0, 0);
     // ... and the LDS write + barrier of the next chunk BEHIND it (hoisted, they make the wave
     // drain all of its reads with only a few MFMAs in flight)
     __builtin_amdgcn_sched_barrier(0);
+  };
+  // the output tiles half * TC .. + TC - 1: the schedule's positions half * NT .. + NT - 1, two per trip
+  auto run_half = [&](auto half_c) {
+    constexpr int half = decltype(half_c)::value;
+    f32x4 even[TC], odd[TC];
+#pragma unroll
+    for (int t = 0; t < TC; ++t) {
+      if constexpr (HAS_BIAS) {
+        even[t] = *reinterpret_cast<const f32x4*>(bias + 16 * (half * TC + t) + 4 * g);
+      } else {
+        even[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+      }
+      odd[t] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    }
+    for (int q = 0; q < NT; q += 2) {
+      const int i = half * NT + q;
+      // ---- q even: half-chunk i in buffer 0; sx holds half-chunk i+1
+      const f32x4 b4e = reinterpret_cast<const f32x4*>(hL)[q * 64 + lane];
+      if (i + 2 < NC) gload(sy, i + 2);
+      stage(0, b4e, even);
+      lwrite(sx, 1);
+      __syncthreads();
+      // ---- q odd: half-chunk i+1 in buffer 1; sy holds half-chunk i+2
+      const f32x4 b4o = reinterpret_cast<const f32x4*>(hL)[(q + 1) * 64 + lane];
+      if (i + 3 < NC) gload(sx, i + 3);
+      stage(1, b4o, odd);
+      if (i + 2 < NC) lwrite(sy, 0);
+      __syncthreads();
+    }
+#pragma unroll
+    for (int t = 0; t < TC; ++t) acc[half * TC + t] = even[t] + odd[t];
   };
   gload(sx, 0);
   lwrite(sx, 0);
@@ -200,19 +238,8 @@ __device__ __forceinline__ void gemm_pass(const float* __restrict__ img,
   // the wave in its MFMA phase outranks a co-resident wave that is in a VALU (sin/cos) phase:
   // +2 % measured (98.2 -> 100.2 TFLOP/s); the two workgroups of a CU stay better interleaved
   __builtin_amdgcn_s_setprio(1);
-  for (int q = 0; q < nq; ++q) {
-    const f32x4 b4 = reinterpret_cast<const f32x4*>(hL)[q * 64 + lane];
-    // ---- half 0: chunk 2q in buffer 0; sx holds chunk 2q+1
-    if (2 * q + 2 < 2 * nq) gload(sy, 2 * q + 2);
-    stage(0, b4);
-    lwrite(sx, 1);
-    __syncthreads();
-    // ---- half 1: chunk 2q+1 in buffer 1; sy holds chunk 2q+2
-    if (2 * q + 3 < 2 * nq) gload(sx, 2 * q + 3);
-    stage(1, b4);
-    if (2 * q + 2 < 2 * nq) lwrite(sy, 0);
-    __syncthreads();
-  }
+  run_half(IsoInt<0>());
+  run_half(IsoInt<1>());
   __builtin_amdgcn_s_setprio(0);
 }
 

@@ -1,11 +1,14 @@
 """The fused SIREN SDF path without a GPU: the dispatch of iso_project_siren / iso_siren_sdf_grad / iso_trace_siren (and
 their coded forms) on both sides of every boundary, in both GEMM modes and both step forms (iso_siren_step_kernel), its
 refusals, the older queries that must follow the same table (iso_siren_step_form_used, iso_siren_step_launches), and the
-guard that the table reaches exactly the k_siren_step* / k_siren_tail* kernels of the built library.  Nothing is launched."""
+guard that the table reaches exactly the k_siren_step* / k_siren_tail* kernels of the built library -- and that the cases of
+tests/test_siren_forms_gpu.py do.  Nothing is launched."""
 import itertools
 import re
 
 import pytest
+
+from test_siren_forms_gpu import CASES, MODES, PROJECTED
 
 F32, X3_VALUE, X3_128, BOTH, BOTH_OC = 100, 200, 300, 400, 500
 
@@ -188,4 +191,39 @@ def test_dispatch_reaches_every_siren_step_kernel_of_the_library(knobs):
     assert len(in_library) == 18, sorted(in_library)
     assert not [k for k in in_library if k.startswith("k_siren_step_x3_oc<")]
     assert "k_siren_step_x3<256,8,3,1,0,0>" not in in_library and "k_siren_step_x3<256,8,3,1,0,1>" not in in_library
+    assert reached == in_library, (sorted(reached - in_library), sorted(in_library - reached))
+
+
+def _library_kernels():
+    """The k_siren_step* / k_siren_tail* instances of the code object, as _kernel_of names them."""
+    from test_abi import _code_object_kernels
+    in_library = set()
+    for name in (k[0] for k in _code_object_kernels()):
+        m = re.search(r"_GLOBAL__N_1(\d+)(k_siren_(?:step|tail)[a-z0-9_]*)I((?:L[ib]\d+E)+)E", name)
+        if m and len(m.group(2)) == int(m.group(1)):
+            in_library.add("%s<%s>" % (m.group(2), ",".join(re.findall(r"L[ib](\d+)E", m.group(3)))))
+    return in_library
+
+
+def test_gpu_cases_reach_every_siren_kernel_of_the_library(knobs):
+    """The orphan guard on the GPU file: CASES (every shape, value_only, codedness, mode and step form that
+    tests/test_siren_forms_gpu.py launches) taken through iso_siren_step_kernel give each case's expected code and reach
+    exactly the 18 kernels the code object holds.  The two Newton-tail kernels count as reached only through a 4xx / 5xx
+    gradient case of their codedness that the GPU file takes through a projection (PROJECTED).  A re-dispatch that orphans
+    an instance, or a new instance without a case, fails here, on the CPU."""
+    lib = _lib()
+    in_library = _library_kernels()
+    reached = set()
+    for H, L, value_only, coded, mode, form, code in CASES:
+        knobs(MODES[mode], form)
+        assert lib.iso_siren_step_kernel(H, L, value_only, coded) == code, (H, L, value_only, coded, mode, form)
+        reached.add(_kernel_of(code, H, L, coded))
+    for H, L, coded, mode, form, code in PROJECTED:
+        assert (H, L, 0, coded, mode, form, code) in CASES, (H, L, coded, mode, form, code)
+        if code // 100 in (4, 5):
+            assert H == 256
+            reached.add("k_siren_tail_x3<256,8,1,%d>" % coded)
+    print("reached: %s" % sorted(reached))
+    assert TAIL_KERNELS <= reached, sorted(TAIL_KERNELS - reached)
+    assert len(in_library) == 18, sorted(in_library)
     assert reached == in_library, (sorted(reached - in_library), sorted(in_library - reached))
