@@ -249,6 +249,40 @@ int iso_trace_idr(const float* ray0, const float* dirs, float* pts_out, float* s
                   int skip_layer, int n_freq, float beta, float alpha, float bound, int max_iters,
                   float tol, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Texture network, forward only: RenderingNetwork.forward, DSS/models/common.py:351-366, on the rows NeuralTexture.forward
+ * builds (DSS/core/texture.py:136-159); reached by ImplicitModel.decode_color (implicit_modeling.py:96-113),
+ * Generator.estimate_colors (:790-820) and Generator.raytrace_images (:951-1001).
+ *   x_i  = [ codes_i (c_dim) | normal_i, point_i (geom = 6) or point_i (geom = 3) | e(d_i) (n_freq >= 0) ]
+ *   d_i  = v / max(|v|, 1e-12),  v = point_i - view_origins[origin_of[i]]             (F.normalize, texture.py:152-153)
+ *   e(d) = [d, sin(2^0 d), cos(2^0 d), ..., sin(2^(F-1) d), cos(2^(F-1) d)], 3 + 6 F slots (get_embedder :205-217); F = 0:
+ *          the raw direction; n_freq = -1: no view direction, no slots
+ *   h_0  = relu(W_0 x + b_0),  h_l = relu(W_l h_(l-1) + b_l), l < n_layers;  rgb = (tanh(W_n h + b_n) + 1) / 2    (:356-365)
+ * Shape (hidden, n_layers, c_dim, geom, n_freq): hidden 256 / 512, 1 <= n_layers <= 8, 0 <= c_dim <= 256, geom 3 / 6,
+ * -1 <= n_freq <= 6, three outputs; the row is D0 = c_dim + geom + (3 + 6 n_freq) <= 301 long.  Weight-norm must already be
+ * folded into the weights.  raw = for l = 0..n_layers: W_l (row-major [out][in]) then b_l.
+ * One persistent kernel per hidden size on the fp16 matrix cores at f32 accuracy (two fp16 parts per operand under exact
+ * power-of-two scales, per layer for the weights and per point for the activations and the input row); the row is
+ * assembled in the kernel, no (n, D0) matrix is written.
+ *
+ * iso_texture_form (host only, no GPU): 600 + hidden / 16 = k_texture_x16<hidden>, by the predicate the packing and the
+ *   launch use; -1: a shape they refuse (ISO_ERR_UNSUPPORTED).
+ * iso_texture_raw_floats / iso_texture_packed_floats: lengths of raw and packed (0 for a refused shape).
+ * iso_texture_rgb: points (n,3); normals (n,3), NULL iff geom == 3; codes (n, c_dim), NULL iff c_dim == 0; view_origins
+ *   (n_origins, 3), NULL iff n_freq < 0; origin_of (n) int32 in [0, n_origins), NULL = origin 0 for every point; rgb_out
+ *   (n,3) in [0, 1].  A point's result does not depend on the other points of the call.  Refusals launch nothing: an
+ *   unsupported shape is ISO_ERR_UNSUPPORTED; a NULL pointer where one is required, one given where none is allowed, and a
+ *   workspace below iso_texture_workspace_bytes are ISO_ERR_INVALID; n == 0 is ISO_OK without a launch.              */
+int iso_texture_form(int hidden, int n_layers, int c_dim, int geom, int n_freq);
+int64_t iso_texture_raw_floats(int hidden, int n_layers, int c_dim, int geom, int n_freq);
+int64_t iso_texture_packed_floats(int hidden, int n_layers, int c_dim, int geom, int n_freq);
+int iso_texture_pack_weights(const float* raw, float* packed, int hidden, int n_layers, int c_dim, int geom,
+                             int n_freq, void* stream);
+int64_t iso_texture_workspace_bytes(int64_t n, int hidden, int n_layers, int c_dim, int geom, int n_freq);
+int iso_texture_rgb(const float* points, const float* normals, const float* codes, const float* view_origins,
+                    const int32_t* origin_of, int64_t n_origins, float* rgb_out, int64_t n, const float* packed,
+                    int hidden, int n_layers, int c_dim, int geom, int n_freq, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+
 /* Nearest point to each ray (brute force, fused): the (R,M) point-to-ray search of
  * CombinedModel.sample_offsurface_using_isopoints, DSS/models/combined_modeling.py:336-352.
  *   pC = p - origin;  ray_sq = (pC . ray)^2;  dist = |pC|^2 - ray_sq;  nn = argmin_m dist

@@ -9,4 +9,4 @@ a hyphen is not importable in Python.)
 """
 from . import _lib  # noqa: F401
 
-__all__ = ["_lib", "frnn", "prefix_sum", "levelset_sampling", "sdf_models"]
+__all__ = ["_lib", "frnn", "prefix_sum", "levelset_sampling", "sdf_models", "texture"]

@@ -726,7 +726,7 @@ def _aligned_grid(lo, hi, resolution):
 
 
 def get_surface_high_res_mesh(sdf, resolution=100, box_side_length=2.0, largest_component=True, return_normals=False,
-                              generator=None, sparse=False):
+                              generator=None, sparse=False, texture=None, texture_kwargs=None):
     """The SDF's zero level set as a mesh, by the steps of the reference's get_surface_high_res_mesh
     (DSS/utils/__init__.py:569-655): a 64^3 mesh over the box -> its largest component -> 10 000 surface samples
     (sample_points_from_meshes, seeded through `generator`) -> their PCA frame -> the aligned grid of get_grid with
@@ -740,13 +740,21 @@ def get_surface_high_res_mesh(sdf, resolution=100, box_side_length=2.0, largest_
 
     sparse=True takes the second extraction through sparse_level_set on the same aligned grid, seeded by band and by the
     10 000 samples: the SDF is evaluated near the surface only and `resolution` may go past marching_tetrahedra's 1024
-    points per side, up to 4096 on the longest side.  The default is the dense path, unchanged."""
+    points per side, up to 4096 on the longest side.  The default is the dense path, unchanged.
+
+    texture: a texture.NeuralTexture; the result then ends with the vertex colours (V,3) in [0, 1] of texture.vertex_colors
+    (Generator.estimate_colors, implicit_modeling.py:790-820, which gives generate_mesh its colours); texture_kwargs go to
+    that call (c, with_normals, camera_centers).  The default, None, returns what it always did."""
     keep_largest, res = bool(largest_component), int(resolution)
     if res < 2:
         raise ValueError("get_surface_high_res_mesh: resolution must be at least 2")
 
     def result(verts, faces):
-        return (verts, faces, _sdf_normals(sdf, verts)) if return_normals else (verts, faces)
+        out = (verts, faces, _sdf_normals(sdf, verts)) if return_normals else (verts, faces)
+        if texture is not None:
+            from .texture import vertex_colors
+            out = out + (vertex_colors(sdf, texture, verts, **(texture_kwargs or {})),)
+        return out
     values, origin, spacing = sdf_grid(sdf, 64, box_side_length)
     verts, faces = marching_tetrahedra(values, origin, spacing)
     if faces.shape[0] == 0:
