@@ -283,6 +283,53 @@ int iso_texture_rgb(const float* points, const float* normals, const float* code
                     int hidden, int n_layers, int c_dim, int geom, int n_freq, void* workspace,
                     int64_t workspace_bytes, void* stream);
 
+/* Backward of the texture network (csrc/texgrad.hip): given g = dL/d rgb (n,3), the gradient of every weight and bias
+ * and of the codes, normals and points of the rows.  With z_l = W_l h_(l-1) + b_l, h_l = relu(z_l), y = W_n h + b_n:
+ *   dy  = g (1 - tanh^2 y) / 2,  dW_n = dy^T h,  db_n = sum_p dy,  a_top = (W_n^T dy) [z_top > 0]
+ *   dW_l = a_l^T h_(l-1),  db_l = sum_p a_l,  a_(l-1) = (W_l^T a_l) [z_(l-1) > 0],  dW_0 = a_0^T x
+ *   dx = W_0^T a_0, cut into d codes | d normals | d points; the view slots are dropped (the reference detaches the
+ *   direction, texture.py:152) and the view origins get no gradient.  The ReLU mask is zero at z == 0, as torch's.
+ * Same shapes as iso_texture_*.  Two kernels per 64-point tile on the fp16 matrix cores at f32 accuracy: the forward's own
+ * form recomputes and stashes every h_l (k_texgrad_fwd_x16<hidden>), and the reverse sweep runs the same three-pass GEMM on
+ * transposed split-fp16 images, the adjoint cut under a per-point power-of-two scale from the column-sum bound
+ * (k_texgrad_rev_x16<hidden>).  The head adjoint, dx and the dW products run in f32 (dx and dW on the exact f32 matrix
+ * instruction).  The
+ * reduction over the points is cut into chunks of iso_texgrad_chunk_points() points BY INDEX, one partial per chunk, the
+ * partials added in chunk order: no float atomic, the same bits on every call.  A point's d codes / d normals / d points
+ * do not depend on the other points of the call.
+ *
+ * iso_texgrad_form (host only): 700 + hidden / 16 for an accepted shape (one code per width, as iso_texture_form's
+ *   600 + hidden / 16), -1 for a refused one.
+ * iso_texgrad_packed_floats / iso_texgrad_pack_weights: the backward's own image of raw (iso_texture_raw_floats), separate
+ *   from the forward's packed image, which the recompute reads unchanged: per-layer weight scales and column sums, the
+ *   head rows and bias, W_0^T in f32 and the split-fp16 images of W_l^T, l >= 1.  Its layout is private to the library and
+ *   its length is whatever iso_texgrad_packed_floats returns: size the buffer by that call, not by a formula.
+ * iso_texgrad_workspace_points (host only) / iso_texgrad_workspace_bytes: the points are processed
+ *   iso_texgrad_workspace_points() = 16384 at a time, so the workspace stops growing there:
+ *   4 * (mw * (K0 + 2 * n_layers * hidden + 4) + ceil(mw / chunk_points) * raw_floats) + 64, mw = min(max(n, 1), 16384),
+ *   K0 = D0 rounded up to a multiple of 64.
+ * Summation: dW_l partials are f32 matrix-instruction chains over the 512 points of a chunk; db_l, dW_n and db_n add
+ *   their terms in float64 and round to f32 once per chunk; the partials of one workspace chunk (up to 32) are added in
+ *   chunk order in ONE float64 chain and rounded to f32 once, on top of the f32 sum of the earlier workspace chunks.
+ * iso_texgrad_backward: inputs as iso_texture_rgb, grad_rgb (n,3); packed_fw the forward's image of the same weights
+ *   (iso_texture_pack_weights), packed_bw the backward's; grad_raw_out in the layout of raw, NULL = the weight gradients
+ *   are not wanted (no dW / db work is done); grad_points (n,3), grad_normals (n,3), grad_codes (n, c_dim): each may be
+ *   NULL (not wanted; all three NULL skips dx); grad_normals / grad_codes must be NULL where the shape has no normals /
+ *   codes.  Outputs are written, not accumulated.  Refusals as iso_texture_rgb, launching nothing; workspace, packed_fw
+ *   and packed_bw must be 16-byte aligned; n == 0 writes zeros to grad_raw_out and is ISO_OK.                          */
+int iso_texgrad_form(int hidden, int n_layers, int c_dim, int geom, int n_freq);
+int64_t iso_texgrad_packed_floats(int hidden, int n_layers, int c_dim, int geom, int n_freq);
+int iso_texgrad_pack_weights(const float* raw, float* packed_bw, int hidden, int n_layers, int c_dim, int geom,
+                             int n_freq, void* stream);
+int64_t iso_texgrad_chunk_points(void);
+int64_t iso_texgrad_workspace_points(void);
+int64_t iso_texgrad_workspace_bytes(int64_t n, int hidden, int n_layers, int c_dim, int geom, int n_freq);
+int iso_texgrad_backward(const float* points, const float* normals, const float* codes, const float* view_origins,
+                         const int32_t* origin_of, int64_t n_origins, const float* grad_rgb, int64_t n,
+                         const float* packed_fw, const float* packed_bw, int hidden, int n_layers, int c_dim, int geom, int n_freq,
+                         float* grad_raw_out, float* grad_points, float* grad_normals, float* grad_codes,
+                         void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Nearest point to each ray (brute force, fused): the (R,M) point-to-ray search of
  * CombinedModel.sample_offsurface_using_isopoints, DSS/models/combined_modeling.py:336-352.
  *   pC = p - origin;  ray_sq = (pC . ray)^2;  dist = |pC|^2 - ray_sq;  nn = argmin_m dist

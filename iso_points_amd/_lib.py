@@ -65,6 +65,13 @@ SIGNATURES = {
     "iso_texture_pack_weights": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     "iso_texture_workspace_bytes": (_L, [_L, _I, _I, _I, _I, _I]),
     "iso_texture_rgb": (_I, [_P, _P, _P, _P, _P, _L, _P, _L, _P, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "iso_texgrad_form": (_I, [_I, _I, _I, _I, _I]),
+    "iso_texgrad_packed_floats": (_L, [_I, _I, _I, _I, _I]),
+    "iso_texgrad_pack_weights": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "iso_texgrad_chunk_points": (_L, []),
+    "iso_texgrad_workspace_points": (_L, []),
+    "iso_texgrad_workspace_bytes": (_L, [_L, _I, _I, _I, _I, _I]),
+    "iso_texgrad_backward": (_I, [_P, _P, _P, _P, _P, _L, _P, _L, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _L, _P]),
     "iso_ray_nearest_point_workspace_bytes": (_L, [_L]),
     "iso_ray_nearest_point": (_I, [_P, _L, _F, _F, _F, _P, _L, _P, _P, _P, _P, _L, _P]),
     "iso_raymarch_settle": (_I, [_P, _P, _L, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P]),

@@ -6,7 +6,8 @@ constructor arguments, attribute names `lin0..`, `embed_fn`, `c_dim`, `dim`, `nu
 forward kernel (csrc/texture.hip, iso_texture_rgb): the row [c | normal, point | e(view direction)] is assembled per tile
 inside the kernel and the activations never leave the chip.  What the kernel does not cover (texture_spec is None:
 other widths, other outputs, wider codes) and any forward kwarg it does not know take decoder.forward on the GPU, with one
-warning per decoder class.  There is no CPU path.
+warning per decoder class.  There is no CPU path.  Under grad mode the rows train: `_TextureFunction` pairs the forward kernel
+with the backward of csrc/texgrad.hip (iso_texgrad_backward) into the weights, biases, codes, normals and points.
 
 `vertex_colors` is Generator.estimate_colors (implicit_modeling.py:790-820) and `raytrace_image` the body of
 Generator.raytrace_images (:951-1001) for one view, both on the package's own SDF, tracing and texture kernels.
@@ -17,6 +18,7 @@ from collections import OrderedDict
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 from .sdf_models import NetOutput, _effective_weight
@@ -183,6 +185,76 @@ def _warn_torch_route(decoder, why):
                   % (type(decoder).__name__, why), RuntimeWarning, stacklevel=3)
 
 
+def _launch_rgb(shape, packed, ws, pts, nrm, codes, cams, origin_of):
+    n = pts.shape[0]
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=pts.device)
+    _lib.call("iso_texture_rgb", _lib.ptr(pts), _lib.ptr(nrm), _lib.ptr(codes), _lib.ptr(cams), _lib.ptr(origin_of),
+              0 if cams is None else cams.shape[0], _lib.ptr(rgb), n, _lib.ptr(packed), *shape, _lib.ptr(ws), ws.numel(),
+              _lib.stream())
+    return rgb
+
+
+def _raw_of(wb, device):
+    """The effective weights and biases W_0, b_0, ..., W_n, b_n as the kernels' raw vector."""
+    return torch.cat([t.detach().reshape(-1) for t in wb]).to(device=device, dtype=torch.float32).contiguous()
+
+
+class _TextureFunction(torch.autograd.Function):
+    """rgb of the fused forward kernel, with the fused backward (csrc/texgrad.hip, iso_texgrad_backward) into the points,
+    normals, codes and the EFFECTIVE weights and biases: those are made under grad by the caller, so weight_g / weight_v
+    of either weight-norm style get their gradients from torch's own chain.  Only the inputs are kept for the backward,
+    which recomputes the forward from them: the forward packs its split-fp16 image, the backward that image again and its own transposed
+    one (iso_texgrad_pack_weights) from the same tensors, and neither image outlives its call."""
+
+    @staticmethod
+    def forward(ctx, shape, pts, nrm, codes, cams, origin_of, *wb):
+        lib = _lib.load()
+        dev = pts.device
+        raw = _raw_of(wb, dev)
+        packed = torch.empty((lib.iso_texture_packed_floats(*shape),), dtype=torch.float32, device=dev)
+        _lib.call("iso_texture_pack_weights", _lib.ptr(raw), _lib.ptr(packed), *shape, _lib.stream())
+        ws = torch.empty((lib.iso_texture_workspace_bytes(pts.shape[0], *shape),), dtype=torch.uint8, device=dev)
+        ctx.shape = shape
+        ctx.save_for_backward(pts, nrm, codes, cams, origin_of, *wb)
+        return _launch_rgb(shape, packed, ws, pts, nrm, codes, cams, origin_of)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_rgb):
+        lib = _lib.load()
+        shape = ctx.shape
+        pts, nrm, codes, cams, origin_of = ctx.saved_tensors[:5]
+        wb = ctx.saved_tensors[5:]
+        dev, n = pts.device, pts.shape[0]
+        raw = _raw_of(wb, dev)
+        packed_fw = torch.empty((lib.iso_texture_packed_floats(*shape),), dtype=torch.float32, device=dev)
+        _lib.call("iso_texture_pack_weights", _lib.ptr(raw), _lib.ptr(packed_fw), *shape, _lib.stream())
+        packed_bw = torch.empty((lib.iso_texgrad_packed_floats(*shape),), dtype=torch.float32, device=dev)
+        _lib.call("iso_texgrad_pack_weights", _lib.ptr(raw), _lib.ptr(packed_bw), *shape, _lib.stream())
+        need = ctx.needs_input_grad
+        g_pts = torch.empty_like(pts) if need[1] else None
+        g_nrm = torch.empty_like(nrm) if (need[2] and nrm is not None) else None
+        g_codes = torch.empty_like(codes) if (need[3] and codes is not None) else None
+        g_raw = torch.empty_like(raw) if any(need[6:]) else None      # NULL: no dW / db work is done
+        ws = torch.empty((lib.iso_texgrad_workspace_bytes(n, *shape),), dtype=torch.uint8, device=dev)
+        g = grad_rgb.reshape(n, 3).to(torch.float32).contiguous()
+        _lib.call("iso_texgrad_backward", _lib.ptr(pts), _lib.ptr(nrm), _lib.ptr(codes), _lib.ptr(cams), _lib.ptr(origin_of),
+                  0 if cams is None else cams.shape[0], _lib.ptr(g), n, _lib.ptr(packed_fw), _lib.ptr(packed_bw), *shape,
+                  _lib.ptr(g_raw),
+                  _lib.ptr(g_pts), _lib.ptr(g_nrm), _lib.ptr(g_codes), _lib.ptr(ws), ws.numel(), _lib.stream())
+        grads, at = [], 0
+        for k, t in enumerate(wb):
+            grads.append(g_raw[at:at + t.numel()].reshape(t.shape).to(t.dtype) if need[6 + k] else None)
+            at += t.numel()
+        return (None, g_pts, g_nrm, g_codes, None, None) + tuple(grads)
+
+
+def _wants_grad(decoder, *tensors):
+    if not torch.is_grad_enabled():
+        return False
+    return any(p.requires_grad for p in decoder.parameters()) or any(t is not None and t.requires_grad for t in tensors)
+
+
 def texture_rgb(decoder, points, normals=None, c=None, camera_centers=None, cloud_idx=None, packed=None, **forward_kwargs):
     """rgb (..., 3) in [0, 1] of decoder([c, normals, points, e(view direction)]) at points (..., 3).
 
@@ -190,30 +262,45 @@ def texture_rgb(decoder, points, normals=None, c=None, camera_centers=None, clou
     direction); cloud_idx (...) integer, the row of camera_centers a point looks from (None: row 0).  What is passed must
     add up to decoder.dim.  packed: a PackedTexture of this decoder to re-use -- on the caller's word that the weights have
     not changed since; by default the image is packed from the live weights on every call.  A decoder texture_spec refuses,
-    and any further forward kwarg, takes decoder.forward on the rows of texture_rows (one warning per decoder class)."""
+    and any further forward kwarg, takes decoder.forward on the rows of texture_rows (one warning per decoder class).
+
+    Under grad mode, with a parameter of the decoder or one of points / normals / c requiring grad and packed None, the
+    result carries a grad_fn: the fused backward kernels give the gradients of every weight and bias (through the
+    weight-norm parameters, where there are any), of the codes, the normals and the points; as in the reference the view
+    direction is detached and camera_centers get none.  A caller's `packed` image is a snapshot of the weights and stays
+    inference-only: the result then has no grad_fn.  The torch route keeps its graph when a gradient is wanted."""
     if not points.is_cuda:
         raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
     shp = points.shape
     n = points.numel() // 3
     has_c = c is not None and c.numel() > 0
     spec = texture_spec(decoder) if packed is None else True
+    train = packed is None and _wants_grad(decoder, points, normals, c if has_c else None)
     if spec is None or forward_kwargs:
         _warn_torch_route(decoder, "forward kwargs" if spec is not None else "shape outside the kernel's")
-        with torch.no_grad():
+        with torch.enable_grad() if train else torch.no_grad():
             x = texture_rows(decoder, points, normals, camera_centers, cloud_idx)
             cc = c.reshape(n, -1).to(x.dtype) if has_c else None
             return decoder.forward(x, c=cc, **forward_kwargs).rgb.reshape(shp[:-1] + (3,))
-    pk = packed if packed is not None else PackedTexture(decoder, points.device)
+    if train:
+        Ws, bs = spec[0], spec[1]
+        pk = None
+        pk_c, pk_g, pk_f = spec[4:7]
+        kshape = tuple(spec[2:7])
+    else:
+        pk = packed if packed is not None else PackedTexture(decoder, points.device)
+        pk_c, pk_g, pk_f = pk.c_dim, pk.geom, pk.n_freq
+        kshape = pk.shape
     G = 3 if normals is None else 6
-    Fq = -1 if camera_centers is None else max(pk.n_freq, 0)
+    Fq = -1 if camera_centers is None else max(pk_f, 0)
     C = c.shape[-1] if has_c else 0
-    if (C, G, Fq) != (pk.c_dim, pk.geom, pk.n_freq):
+    if (C, G, Fq) != (pk_c, pk_g, pk_f):
         raise ValueError("texture_rgb: the decoder takes rows of (c_dim, geometry, n_freq) = %s, the arguments make %s"
-                         % ((pk.c_dim, pk.geom, pk.n_freq), (C, G, Fq)))
+                         % ((pk_c, pk_g, pk_f), (C, G, Fq)))
     dev = points.device
 
     def dense(t, width):
-        t = t.detach().reshape(-1, width).to(device=dev, dtype=torch.float32).contiguous()
+        t = (t if train else t.detach()).reshape(-1, width).to(device=dev, dtype=torch.float32).contiguous()
         if t.shape[0] != n:
             raise ValueError("texture_rgb: %d rows for %d points" % (t.shape[0], n))
         return t
@@ -229,10 +316,11 @@ def texture_rgb(decoder, points, normals=None, c=None, camera_centers=None, clou
             origin_of = cloud_idx.detach().reshape(-1).to(device=dev, dtype=torch.int32).contiguous()
             if origin_of.shape[0] != n:
                 raise ValueError("texture_rgb: %d cloud indices for %d points" % (origin_of.shape[0], n))
-    rgb = torch.empty((n, 3), dtype=torch.float32, device=dev)
-    ws = pk.workspace(n)
-    _lib.call("iso_texture_rgb", _lib.ptr(pts), _lib.ptr(nrm), _lib.ptr(codes), _lib.ptr(cams), _lib.ptr(origin_of),
-              n_origins, _lib.ptr(rgb), n, _lib.ptr(pk.packed), *pk.shape, _lib.ptr(ws), ws.numel(), _lib.stream())
+    if train:
+        wb = [t for pair in zip(Ws, bs) for t in pair]
+        rgb = _TextureFunction.apply(kshape, pts, nrm, codes, cams, origin_of, *wb)
+    else:
+        rgb = _launch_rgb(kshape, pk.packed, pk.workspace(n), pts, nrm, codes, cams, origin_of)
     return rgb.reshape(shp[:-1] + (3,))
 
 
