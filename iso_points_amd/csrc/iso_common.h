@@ -109,6 +109,20 @@ __device__ __forceinline__ float iso_wave_sum(float v) {
   return v;
 }
 
+// maximum of one float per thread over a workgroup of 256 threads (all threads call); s_m: 256 floats of LDS, free again
+// on return
+__device__ __forceinline__ float iso_block_max256(float v, float* s_m) {
+  s_m[threadIdx.x] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) s_m[threadIdx.x] = fmaxf(s_m[threadIdx.x], s_m[threadIdx.x + o]);
+    __syncthreads();
+  }
+  const float r = s_m[0];
+  __syncthreads();
+  return r;
+}
+
 // order-preserving float <-> uint key (integer atomicMin / atomicMax on floats)
 __device__ __forceinline__ unsigned iso_f2key(float f) {
   const unsigned u = __float_as_uint(f);

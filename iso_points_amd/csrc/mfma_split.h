@@ -44,6 +44,15 @@ __device__ __forceinline__ float x3_scale_for(float bound) {
   k = k > 120 ? 120 : (k < -120 ? -120 : k);
   return ldexpf(1.0f, k);
 }
+// the weight scale of a layer: 2^k with 2^k * mx in [512, 1024), mx = max |W| (1 for a zero / non-finite mx)
+__device__ __forceinline__ float x3_weight_scale(float mx) {
+  if (!(mx > 0.f && mx < 3.0e38f)) return 1.0f;
+  int e;
+  (void)frexpf(mx, &e);                      // mx = f * 2^e, f in [0.5, 1)
+  int k = 10 - e;
+  k = k > 100 ? 100 : (k < -100 ? -100 : k);
+  return ldexpf(1.0f, k);
+}
 constexpr float kActScale = 4096.0f;             // 2^12
 
 // two-way fp16 cut of scale * v, step-major over the four pairs (a packed op whose result feeds the next

@@ -108,16 +108,7 @@ __global__ void k_siren_wscale(const float* __restrict__ raw, float* __restrict_
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    float mx = s_m[0];
-    int e = 0;
-    float sc = 1.0f;
-    if (mx > 0.f && mx < 3.0e38f) {
-      (void)frexpf(mx, &e);                    // mx = f * 2^e, f in [0.5, 1)
-      int k = 10 - e;                          // 2^k * mx in [512, 1024)
-      k = k > 100 ? 100 : (k < -100 ? -100 : k);
-      sc = ldexpf(1.0f, k);
-    }
-    packed[x16_base(H, L) + l] = sc;
+    packed[x16_base(H, L) + l] = x3_weight_scale(s_m[0]);
   }
   __syncthreads();
   // c_l = max_f sum_k |W_l[k][f]|: |(W_l^T a)[f]| <= c_l max|a|

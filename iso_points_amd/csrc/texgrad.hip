@@ -1,6 +1,6 @@
 // Backward of the texture network (texture.hip) into every weight and bias and into codes, normals and points:
-//   recompute the forward kernel's own form (row assembly, three-pass split-fp16 tex_gemm on the forward's image,
-//             per-point scales, tiles drawn from the counter) without its head; x_0 (m, K0) and every h_l (m, H) stashed
+//   recompute the forward kernel's own body (tex_forward_tiles of texture_tile.h: row assembly, three-pass split-fp16
+//             tex_gemm on the forward's image, per-point scales) without its head; x_0 (m, K0) and every h_l (m, H) stashed
 //                                                                                          k_texgrad_fwd_x16<256|512>
 //   head      y = W_head h_top + b_head, dy = g (1 - tanh^2 y) / 2, a_top = (W_head^T dy) [h_top > 0]   k_texgrad_head
 //   reverse   a_{l-1} = (W_l^T a_l) [h_{l-1} > 0], l = n_layers-1 .. 1, per 64-point tile: tex_gemm on the TRANSPOSED
@@ -17,7 +17,7 @@
 #include "idr_common.h"
 #include "mfma_split.h"
 #include "texture_common.h"
-#include "texture_gemm.h"
+#include "texture_tile.h"
 
 namespace {
 
@@ -44,17 +44,6 @@ __host__ __device__ inline int64_t tgp_end(const TexShape& s) { return tgp_bw(s,
 __global__ void k_texgrad_stats(const float* __restrict__ raw, float* __restrict__ packed, TexShape s) {
   __shared__ float s_m[256];
   const int H = s.H, l = blockIdx.x;
-  auto block_max = [&](float v) {
-    s_m[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-      if ((int)threadIdx.x < o) s_m[threadIdx.x] = fmaxf(s_m[threadIdx.x], s_m[threadIdx.x + o]);
-      __syncthreads();
-    }
-    const float r = s_m[0];
-    __syncthreads();
-    return r;
-  };
   float mx = 0.f, cs = 0.f;
   if (l >= 1) {
     const float* __restrict__ Wl = raw + tex_raw_off(s, l);
@@ -64,18 +53,8 @@ __global__ void k_texgrad_stats(const float* __restrict__ raw, float* __restrict
       cs = fmaxf(cs, t);
     }
   }
-  mx = block_max(mx); cs = block_max(cs);
-  if (threadIdx.x == 0) {
-    float sc = 1.0f;
-    if (mx > 0.f && mx < 3.0e38f) {
-      int e;
-      (void)frexpf(mx, &e);
-      int k = 10 - e;                          // 2^k * mx in [512, 1024)
-      k = k > 100 ? 100 : (k < -100 ? -100 : k);
-      sc = ldexpf(1.0f, k);
-    }
-    packed[l] = sc; packed[16 + l] = cs;
-  }
+  mx = iso_block_max256(mx, s_m); cs = iso_block_max256(cs, s_m);
+  if (threadIdx.x == 0) { packed[l] = x3_weight_scale(mx); packed[16 + l] = cs; }
 }
 
 __global__ void k_texgrad_pack(const float* __restrict__ raw, float* __restrict__ packed, TexShape s) {
@@ -108,9 +87,7 @@ __global__ void k_texgrad_pack(const float* __restrict__ raw, float* __restrict_
         const int fi = x3_feat(ks, 8 * (lane >> 5) + 2 * d + u);   // K of the reverse: output index of W_l
         v[u] = raw[tex_raw_off(s, l) + (int64_t)fi * H + fo] * sc;
       }
-      const f16x2 hh = __builtin_convertvector(v, f16x2);
-      const f16x2 lo = __builtin_convertvector(v - __builtin_convertvector(hh, f32x2), f16x2);
-      reinterpret_cast<unsigned*>(packed)[o] = part == 0 ? __builtin_bit_cast(unsigned, hh) : __builtin_bit_cast(unsigned, lo);
+      reinterpret_cast<unsigned*>(packed)[o] = tex_f16_word(v, part);
     }
   }
 }
@@ -410,8 +387,7 @@ __global__ void k_texgrad_reduce(const float* __restrict__ part, int64_t part_st
   }
 }
 
-// ---- recompute: the forward kernel of texture.hip (same row assembly, same three-pass split-fp16 tex_gemm, same per-point
-// scales, tiles drawn from the counter) without its head, writing every h_l of its 64-point tile to the stash ----------
+// ---- recompute: the forward of texture.hip without its head, x_0 and every h_l of a 64-point tile written to the stashes
 struct TgFwdArgs {
   TexArgs t;                         // rgb unused
   float* hst;                        // layer l at hst + l * lstride, row-major (n, H)
@@ -421,202 +397,8 @@ struct TgFwdArgs {
 
 template <int H>
 __global__ __launch_bounds__(512, 1) void k_texgrad_fwd_x16(TgFwdArgs fa) {
-  const TexArgs a = fa.t;
-  using S = TexTile<H>;
-  constexpr int NW = S::NW, NB = S::NB, NS = S::NS, NTO = S::NTO, TW = S::TW, SL = S::SL, P = S::P;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  u32x4* act = reinterpret_cast<u32x4*>(smem_raw);
-  float* geo = reinterpret_cast<float*>(smem_raw + S::kActBytes);                    // [k][P]: normal, point, view
-  f32x4* red = reinterpret_cast<f32x4*>(smem_raw + S::kActBytes + S::kGeoBytes);     // [NW][P]
-  float* redm = reinterpret_cast<float*>(red);                                      // [2][P][NW] maxima exchange
-  const int tid = threadIdx.x;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lane = tid & 63, h = lane >> 5, j = lane & 31, h8 = h * 8;
-  const TexShape s = a.s;
-  const int nL = s.n_layers, C = s.C, GV = s.G + s.V, KS0 = s.K0 / 16;
-  const float* hdr = a.packed;
-  u32x4* own = act + (size_t)(SL * w) * NB * kAP * 64 + lane;
-
-  auto fwd_img = [&](int l) {
-    const float* base = a.packed + (l == 0 ? texp_fw0(s) : texp_fw(s, l));
-    return reinterpret_cast<const u32x4*>(base) + (TW * w * 2) * 64;
-  };
-  u32x4 A[4][TW];
-#pragma unroll
-  for (int d = 0; d < kTexAD; ++d) tex_load_a<TW, NTO>(A[d], fwd_img(0), d, kTexQA[0], lane);
-
-  float bscale[NB], amax[NB];
-  auto put_amax = [&](int buf) {
-#pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      const float m = __builtin_fmaxf(amax[n], __shfl_xor(amax[n], 32));
-      if (h == 0) redm[(buf * P + 32 * n + j) * NW + w] = m;
-    }
-  };
-  auto get_max = [&](int buf, float (&Mp)[NB]) {
-#pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      float m = 0.f;
-#pragma unroll
-      for (int ww = 0; ww < NW; ++ww) m = __builtin_fmaxf(m, redm[(buf * P + 32 * n + j) * NW + ww]);
-      Mp[n] = m;
-    }
-  };
-
-  const int64_t count = a.n;
-  const int64_t n_tiles = (count + P - 1) / P;
-  __shared__ int s_next_tile;
-  int64_t next_tile = 0;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile = next_tile) {
-    int drawn = 0;
-    if (tid == 0) drawn = (int)gridDim.x + atomicAdd(a.tile_ctr, 1);
-    // ---- the row's geometry part and its largest entry: wave w, lane = point, takes every NW-th row / code column --
-    {
-      const int64_t slot = tile * P + lane;
-      const bool live = slot < count;
-      float px = 0.f, py = 0.f, pz = 0.f, nx = 0.f, ny = 0.f, nz = 0.f, vx = 0.f, vy = 0.f, vz = 0.f, m = 0.f;
-      if (live) {
-        px = a.points[slot * 3]; py = a.points[slot * 3 + 1]; pz = a.points[slot * 3 + 2];
-        if (s.G == 6) { nx = a.normals[slot * 3]; ny = a.normals[slot * 3 + 1]; nz = a.normals[slot * 3 + 2]; }
-        if (s.V > 0) {
-          int64_t o = a.origin_of ? (int64_t)a.origin_of[slot] : 0;
-          o = o < 0 ? 0 : (o >= a.n_origins ? a.n_origins - 1 : o);
-          vx = px - a.origins[o * 3]; vy = py - a.origins[o * 3 + 1]; vz = pz - a.origins[o * 3 + 2];
-          // F.normalize: v / max(|v|, 1e-12)
-          const float den = __builtin_fmaxf(__builtin_sqrtf((vx * vx + vy * vy) + vz * vz), 1e-12f);
-          vx = vx / den; vy = vy / den; vz = vz / den;
-        }
-        const float* crow = a.codes + slot * C;
-#pragma unroll 1
-        for (int c = w; c < C; c += NW) m = __builtin_fmaxf(m, __builtin_fabsf(crow[c]));
-      }
-#pragma unroll 1
-      for (int k = w; k < GV; k += NW) {
-        float v = 0.f;
-        if (live) {
-          if (k < s.G - 3) v = k == 0 ? nx : (k == 1 ? ny : nz);
-          else if (k < s.G) { const int c = k - (s.G - 3); v = c == 0 ? px : (c == 1 ? py : pz); }
-          else { float dv; int c; posenc(k - s.G, vx, vy, vz, v, c, dv); }
-        }
-        geo[k * P + lane] = v;
-        m = __builtin_fmaxf(m, __builtin_fabsf(v));
-      }
-      redm[(0 * P + lane) * NW + w] = m;
-    }
-    __syncthreads();
-    float Mp[NB];
-    get_max(0, Mp);
-#pragma unroll
-    for (int n = 0; n < NB; ++n) bscale[n] = x3_scale_for(Mp[n] * 1.01f);
-    // B operand of layer 0: the KS0*NB entries are spread over the waves; slots above D0 are zero
-#pragma unroll 1
-    for (int ent = w; ent < KS0 * NB; ent += NW) {
-      const int ks = ent / NB, n = ent % NB;
-      const int64_t slot = tile * P + 32 * n + j;
-      const bool live = slot < count;
-      float v[8];
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const int f = x3_feat(ks, h8 + e);
-        float x = 0.f;
-        if (live && f < C) x = a.codes[slot * C + f];
-        else if (f >= C && f < s.D0) x = geo[(f - C) * P + 32 * n + j];
-        v[e] = x;
-      }
-      if (live) {                                 // x_0 (n, K0), zero above D0: the B operand of dW_0
-        float* dst = fa.x0 + slot * s.K0 + (32 * (ks >> 1) + 16 * (ks & 1) + 4 * h);
-        *reinterpret_cast<f32x4*>(dst) = (f32x4){v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(dst + 8) = (f32x4){v[4], v[5], v[6], v[7]};
-      }
-      const float sc = n == 0 ? bscale[0] : bscale[1];
-      u32x4 p0, p1;
-      split8_f16(v, p0, p1, sc);
-      act[((ks * NB + n) * kAP + 0) * 64 + lane] = p0;
-      act[((ks * NB + n) * kAP + 1) * 64 + lane] = p1;
-    }
-    __syncthreads();
-
-    f32x16 acc[TW][NB];
-    int mbuf = 0;                              // exchange buffer written last
-    for (int l = 0; l < nL; ++l) {
-      const u32x4* img = fwd_img(l);
-      const float* bias = a.packed + texp_bias(s, l);
-      const float wsc = hdr[l];
-      float zs[NB];
-#pragma unroll
-      for (int n = 0; n < NB; ++n) zs[n] = wsc * bscale[n];
-      const bool top = (l == nL - 1);
-      const u32x4* nxt = top ? fwd_img(0) : fwd_img(l + 1);
-      if (l == 0) {
-        // K0 / 16 K-steps in groups of four, once per product: every group requests the fragments of the one after it
-        const int NG0 = KS0 / 4;
-        for (int g = 0; g < 3 * NG0; ++g) {
-          const int q = g / NG0, k0 = 4 * (g % NG0);
-          const bool more = g + 1 < 3 * NG0;
-          const u32x4* after = more ? img : nxt;
-          const int kn = more ? 4 * ((g + 1) % NG0) : 0, pn = more ? kTexQA[(g + 1) / NG0] : kTexQA[0];
-          if (g == 0) tex_gemm<TW, NB, NTO, 4, true>(img, kTexQA[q], act + lane, kTexQB[q], acc, k0, A, after, kn, pn, lane, bias, w, zs);
-          else tex_gemm<TW, NB, NTO, 4, false>(img, kTexQA[q], act + lane, kTexQB[q], acc, k0, A, after, kn, pn, lane);
-        }
-      } else {
-        tex_gemm<TW, NB, NTO, NS, true>(img, kTexQA[0], act + lane, kTexQB[0], acc, 0, A, img, 0, kTexQA[1], lane, bias, w, zs);
-        tex_gemm<TW, NB, NTO, NS, false>(img, kTexQA[1], act + lane, kTexQB[1], acc, 0, A, img, 0, kTexQA[2], lane);
-        tex_gemm<TW, NB, NTO, NS, false>(img, kTexQA[2], act + lane, kTexQB[2], acc, 0, A, nxt, 0, kTexQA[0], lane);
-      }
-      __syncthreads();                                   // every wave has read the activations
-      // bound of this layer's output per point -> scale of the next operand
-      float nscale[NB], iz[NB];
-      float* __restrict__ hl = fa.hst + (int64_t)l * fa.lstride;        // this layer's stash, row-major (n, H)
-#pragma unroll
-      for (int n = 0; n < NB; ++n) {
-        nscale[n] = top ? 1.0f : x3_scale_for((hdr[16 + l] * Mp[n] + hdr[32 + l]) * 1.01f);
-        iz[n] = 1.0f / zs[n];
-        amax[n] = 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < TW; ++t)
-#pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-          for (int n = 0; n < NB; ++n) {
-            const int k = (2 * t + p) * NB + n;
-            float hv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) hv[e] = __builtin_fmaxf(acc[t][n][8 * p + e] * iz[n], 0.f);
-            {
-              // registers 8p..8p+7 of output tile T = TW w + t are features 32 T + 16 p + 4 h + {0..3, 8..11} (x3_feat)
-              const int64_t slot = tile * P + 32 * n + j;
-              if (slot < count) {
-                float* dst = hl + slot * H + (32 * (TW * w + t) + 16 * p + 4 * h);
-                *reinterpret_cast<f32x4*>(dst) = (f32x4){hv[0], hv[1], hv[2], hv[3]};
-                *reinterpret_cast<f32x4*>(dst + 8) = (f32x4){hv[4], hv[5], hv[6], hv[7]};
-              }
-            }
-            if (top) continue;
-            float m = amax[n];
-#pragma unroll
-            for (int e = 0; e < 8; e += 2) m = __builtin_fmaxf(m, __builtin_fmaxf(hv[e], hv[e + 1]));
-            amax[n] = m;
-            u32x4 p0, p1;
-            split8_f16(hv, p0, p1, nscale[n]);
-            own[(k * kAP + 0) * 64] = p0; own[(k * kAP + 1) * 64] = p1;
-            __builtin_amdgcn_sched_barrier(0);     // one group at a time: bounds register pressure
-          }
-      if (top) break;
-#pragma unroll
-      for (int n = 0; n < NB; ++n) bscale[n] = nscale[n];
-      mbuf ^= 1;
-      put_amax(mbuf);
-      __syncthreads();                                   // the next layer's inputs (and maxima) are complete
-      get_max(mbuf, Mp);
-    }
-    if (tid == 0) s_next_tile = drawn;
-    __syncthreads();
-    next_tile = (int64_t)__builtin_amdgcn_readfirstlane(s_next_tile);        // uniform: the tile's addresses stay scalar
-    __syncthreads();
-  }
+  tex_forward_tiles<H, true>(fa.t, fa.hst, fa.lstride, fa.x0);
 }
-
 
 template <int H>
 void launch_texgrad_fwd(const TgFwdArgs& a, hipStream_t st) {
@@ -624,12 +406,12 @@ void launch_texgrad_fwd(const TgFwdArgs& a, hipStream_t st) {
   iso_launch_lds<k_texgrad_fwd_x16<H>>(iso_capped_grid(a.t.n, S::P, kIdrBlocks), 512, S::kLds, st, a);
 }
 
-// ---- reverse sweep: a_{l-1} = (W_l^T a_l) [h_{l-1} > 0] for l = n_layers-1 .. 1 of one 64-point tile, the forward's three-pass
-// split-fp16 tex_gemm on the TRANSPOSED images.  The adjoint has no a-priori range: every point carries its own
-// power-of-two scale, taken from the column-sum bound colsum_l * max_o |a_l[o][p]| (the maxima ride on the barrier that
-// ends the stage, as the forward's).  a_top comes from k_texgrad_head's stash, the mask from the h stash the recompute has
-// just written; every a_l goes to the a stash (the dW GEMMs and dx_0 read it).  Registers 8p..8p+7 of output tile T are
-// features 32 T + 16 p + 4 h + {0..3, 8..11}: the stash addresses of k_texgrad_fwd_x16.
+// ---- reverse sweep: a_{l-1} = (W_l^T a_l) [h_{l-1} > 0] for l = n_layers-1 .. 1 of one 64-point tile, on the tile skeleton of
+// the forward (texture_tile.h): its three-pass split-fp16 GEMM on the TRANSPOSED images, acc zeroed instead of the bias.
+// The adjoint has no a-priori range: every point carries its own power-of-two scale, taken from the column-sum bound
+// colsum_l * max_o |a_l[o][p]| (the maxima ride on the barrier that ends the stage, as the forward's).  a_top comes from
+// k_texgrad_head's stash, the mask from the h stash the recompute has just written; every a_l goes to the a stash (the dW
+// GEMMs and dx_0 read it).
 struct TgRevArgs {
   const float* packed_bw;
   TexShape s;
@@ -642,52 +424,24 @@ struct TgRevArgs {
 template <int H>
 __global__ __launch_bounds__(512, 1) void k_texgrad_rev_x16(TgRevArgs a) {
   using S = TexTile<H>;
-  constexpr int NW = S::NW, NB = S::NB, NS = S::NS, NTO = S::NTO, TW = S::TW, SL = S::SL, P = S::P;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  u32x4* act = reinterpret_cast<u32x4*>(smem_raw);
-  float* redm = reinterpret_cast<float*>(smem_raw + S::kActBytes + S::kGeoBytes);    // [2][P][NW] maxima exchange
-  const int tid = threadIdx.x;
-  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int lane = tid & 63, h = lane >> 5, j = lane & 31;
+  constexpr int NB = S::NB, TW = S::TW, P = S::P;
+  const TexLds<H> c = tex_lds<H>();
   const TexShape s = a.s;
   const int nL = s.n_layers;
   const float* hdr = a.packed_bw;
-  u32x4* own = act + (size_t)(SL * w) * NB * kAP * 64 + lane;
-
-  auto bw_img = [&](int l) {
-    return reinterpret_cast<const u32x4*>(a.packed_bw + tgp_bw(s, l)) + (TW * w * 2) * 64;
-  };
+  auto bw_img = [&](int l) { return tex_wave_img<H>(a.packed_bw + tgp_bw(s, l), c.w); };
   u32x4 A[4][TW];
-#pragma unroll
-  for (int d = 0; d < kTexAD; ++d) tex_load_a<TW, NTO>(A[d], bw_img(nL - 1), d, kTexQA[0], lane);
+  tex_prefetch_a<H>(A, bw_img(nL - 1), c.lane);
 
   float bscale[NB], amax[NB];
-  auto put_amax = [&](int buf) {
-#pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      const float m = __builtin_fmaxf(amax[n], __shfl_xor(amax[n], 32));
-      if (h == 0) redm[(buf * P + 32 * n + j) * NW + w] = m;
-    }
-  };
-  auto get_max = [&](int buf, float (&Mp)[NB]) {
-#pragma unroll
-    for (int n = 0; n < NB; ++n) {
-      float m = 0.f;
-#pragma unroll
-      for (int ww = 0; ww < NW; ++ww) m = __builtin_fmaxf(m, redm[(buf * P + 32 * n + j) * NW + ww]);
-      Mp[n] = m;
-    }
-  };
-
   const int64_t count = a.n;
   const int64_t n_tiles = (count + P - 1) / P;
-  __shared__ int s_next_tile;
   int64_t next_tile = 0;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile = next_tile) {
-    int drawn = 0;
-    if (tid == 0) drawn = (int)gridDim.x + atomicAdd(a.tile_ctr, 1);
+    const int drawn = tex_draw_tile(a.tile_ctr);
     f32x16 acc[TW][NB];
-    // ---- a_top of the tile into the accumulator registers, its largest entry per point
+    // ---- a_top of the tile into the accumulator registers, its largest entry per point; cut into act once the maxima of
+    // all waves give the scale
     {
       const float* __restrict__ at = a.ast + (int64_t)(nL - 1) * a.lstride;
 #pragma unroll
@@ -698,10 +452,10 @@ __global__ __launch_bounds__(512, 1) void k_texgrad_rev_x16(TgRevArgs a) {
         for (int p = 0; p < 2; ++p)
 #pragma unroll
           for (int n = 0; n < NB; ++n) {
-            const int64_t slot = tile * P + 32 * n + j;
+            const int64_t slot = tile * P + 32 * n + c.j;
             f32x4 lo = {0.f, 0.f, 0.f, 0.f}, hi = {0.f, 0.f, 0.f, 0.f};
             if (slot < count) {
-              const float* src = at + slot * H + (32 * (TW * w + t) + 16 * p + 4 * h);
+              const float* src = at + slot * H + c.stash_off(t, p);
               lo = *reinterpret_cast<const f32x4*>(src);
               hi = *reinterpret_cast<const f32x4*>(src + 8);
             }
@@ -714,27 +468,16 @@ __global__ __launch_bounds__(512, 1) void k_texgrad_rev_x16(TgRevArgs a) {
             amax[n] = m;
           }
     }
-    put_amax(0);
+    tex_put_amax(c, 0, amax);
     __syncthreads();
     float Mp[NB];
-    get_max(0, Mp);
+    tex_get_max(c, 0, Mp);
 #pragma unroll
     for (int n = 0; n < NB; ++n) bscale[n] = x3_scale_for(Mp[n] * 1.01f);
+    tex_requantize<H, true>(c, bscale, amax, true, [&](int t, int p, int n, float (&hv)[8]) __attribute__((always_inline)) {
 #pragma unroll
-    for (int t = 0; t < TW; ++t)
-#pragma unroll
-      for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int n = 0; n < NB; ++n) {
-          const int k = (2 * t + p) * NB + n;
-          float hv[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) hv[e] = acc[t][n][8 * p + e];
-          u32x4 p0, p1;
-          split8_f16(hv, p0, p1, bscale[n]);
-          own[(k * kAP + 0) * 64] = p0; own[(k * kAP + 1) * 64] = p1;
-          __builtin_amdgcn_sched_barrier(0);
-        }
+      for (int e = 0; e < 8; ++e) hv[e] = acc[t][n][8 * p + e];
+    });
     __syncthreads();
 
     int mbuf = 0;
@@ -752,9 +495,7 @@ __global__ __launch_bounds__(512, 1) void k_texgrad_rev_x16(TgRevArgs a) {
         for (int n = 0; n < NB; ++n)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[t][n][r] = 0.f;
-      tex_gemm<TW, NB, NTO, NS, false>(img, kTexQA[0], act + lane, kTexQB[0], acc, 0, A, img, 0, kTexQA[1], lane);
-      tex_gemm<TW, NB, NTO, NS, false>(img, kTexQA[1], act + lane, kTexQB[1], acc, 0, A, img, 0, kTexQA[2], lane);
-      tex_gemm<TW, NB, NTO, NS, false>(img, kTexQA[2], act + lane, kTexQB[2], acc, 0, A, nxt, 0, kTexQA[0], lane);
+      tex_gemm3<H, false>(c, img, nxt, acc, A);
       __syncthreads();                                   // every wave has read the adjoints
       // column-sum bound of this stage's output per point -> scale of the next operand
       float nscale[NB], iz[NB];
@@ -764,52 +505,28 @@ __global__ __launch_bounds__(512, 1) void k_texgrad_rev_x16(TgRevArgs a) {
       for (int n = 0; n < NB; ++n) {
         nscale[n] = last ? 1.0f : x3_scale_for(hdr[16 + l] * Mp[n] * 1.01f);
         iz[n] = 1.0f / zs[n];
-        amax[n] = 0.f;
       }
+      // a_{l-1} = (acc / zs) [h_{l-1} > 0], stashed
+      tex_requantize<H, true>(c, nscale, amax, !last, [&](int t, int p, int n, float (&hv)[8]) __attribute__((always_inline)) {
+        const int64_t slot = tile * P + 32 * n + c.j;
 #pragma unroll
-      for (int t = 0; t < TW; ++t)
+        for (int e = 0; e < 8; ++e) hv[e] = 0.f;
+        if (slot < count) {
+          const int64_t off = slot * H + c.stash_off(t, p);
+          const f32x4 m0 = *reinterpret_cast<const f32x4*>(hm + off);
+          const f32x4 m1 = *reinterpret_cast<const f32x4*>(hm + off + 8);
 #pragma unroll
-        for (int p = 0; p < 2; ++p)
-#pragma unroll
-          for (int n = 0; n < NB; ++n) {
-            const int k = (2 * t + p) * NB + n;
-            const int64_t slot = tile * P + 32 * n + j;
-            float hv[8];
-#pragma unroll
-            for (int e = 0; e < 8; ++e) hv[e] = 0.f;
-            if (slot < count) {
-              const int64_t off = slot * H + (32 * (TW * w + t) + 16 * p + 4 * h);
-              const f32x4 m0 = *reinterpret_cast<const f32x4*>(hm + off);
-              const f32x4 m1 = *reinterpret_cast<const f32x4*>(hm + off + 8);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                hv[e] = m0[e] > 0.f ? acc[t][n][8 * p + e] * iz[n] : 0.f;
-                hv[4 + e] = m1[e] > 0.f ? acc[t][n][8 * p + 4 + e] * iz[n] : 0.f;
-              }
-              *reinterpret_cast<f32x4*>(al + off) = (f32x4){hv[0], hv[1], hv[2], hv[3]};
-              *reinterpret_cast<f32x4*>(al + off + 8) = (f32x4){hv[4], hv[5], hv[6], hv[7]};
-            }
-            if (last) continue;
-            float m = amax[n];
-#pragma unroll
-            for (int e = 0; e < 8; e += 2) m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(hv[e]), __builtin_fabsf(hv[e + 1])));
-            amax[n] = m;
-            u32x4 p0, p1;
-            split8_f16(hv, p0, p1, nscale[n]);
-            own[(k * kAP + 0) * 64] = p0; own[(k * kAP + 1) * 64] = p1;
-            __builtin_amdgcn_sched_barrier(0);     // one group at a time: bounds register pressure
+          for (int e = 0; e < 4; ++e) {
+            hv[e] = m0[e] > 0.f ? acc[t][n][8 * p + e] * iz[n] : 0.f;
+            hv[4 + e] = m1[e] > 0.f ? acc[t][n][8 * p + 4 + e] * iz[n] : 0.f;
           }
+          tex_store8(al + off, hv);
+        }
+      });
       if (last) break;
-#pragma unroll
-      for (int n = 0; n < NB; ++n) bscale[n] = nscale[n];
-      mbuf ^= 1;
-      put_amax(mbuf);
-      __syncthreads();                                   // the next stage's inputs (and maxima) are complete
-      get_max(mbuf, Mp);
+      tex_end_layer(c, mbuf, amax, nscale, bscale, Mp);
     }
-    if (tid == 0) s_next_tile = drawn;
-    __syncthreads();
-    next_tile = (int64_t)__builtin_amdgcn_readfirstlane(s_next_tile);
+    next_tile = tex_next_tile(drawn);
     __syncthreads();
   }
 }
@@ -878,9 +595,8 @@ extern "C" int iso_texgrad_backward(const float* points, const float* normals, c
                                     const float* packed_fw, const float* packed_bw, int hidden, int n_layers, int c_dim, int geom, int n_freq,
                                     float* grad_raw_out, float* grad_points, float* grad_normals, float* grad_codes,
                                     void* workspace, int64_t workspace_bytes, void* stream) {
-  ISO_REQUIRE(tex_shape_ok(hidden, n_layers, c_dim, geom, n_freq), ISO_ERR_UNSUPPORTED,
-              "iso_texgrad_backward: unsupported shape (hidden 256/512, 1..8 layers, c_dim <= 256, geom 3/6, n_freq -1..6)");
-  ISO_REQUIRE(n >= 0, ISO_ERR_INVALID, "iso_texgrad_backward: negative n");
+  const char* fn = "iso_texgrad_backward";
+  if (int rc = tex_check_shape(fn, n, hidden, n_layers, c_dim, geom, n_freq)) return rc;
   const TexShape s = tex_shape(hidden, n_layers, c_dim, geom, n_freq);
   hipStream_t st = (hipStream_t)stream;
   const TgWs ws = tg_workspace(n, s);
@@ -889,13 +605,9 @@ extern "C" int iso_texgrad_backward(const float* points, const float* normals, c
     ISO_CHECK_LAUNCH("iso_texgrad_backward");
     return ISO_OK;
   }
-  ISO_REQUIRE(points && grad_rgb && packed_fw && packed_bw && workspace, ISO_ERR_INVALID, "iso_texgrad_backward: null pointer");
-  ISO_REQUIRE((geom == 6) == (normals != nullptr), ISO_ERR_INVALID, "iso_texgrad_backward: normals are required iff geom == 6");
-  ISO_REQUIRE((c_dim > 0) == (codes != nullptr), ISO_ERR_INVALID, "iso_texgrad_backward: codes are required iff c_dim > 0");
-  ISO_REQUIRE((n_freq >= 0) == (view_origins != nullptr), ISO_ERR_INVALID,
-              "iso_texgrad_backward: view_origins are required iff n_freq >= 0");
-  ISO_REQUIRE(n_freq < 0 || n_origins >= 1, ISO_ERR_INVALID, "iso_texgrad_backward: n_origins must be at least 1");
-  ISO_REQUIRE(n_freq >= 0 || !origin_of, ISO_ERR_INVALID, "iso_texgrad_backward: origin_of without a view direction");
+  if (int rc = tex_check_inputs(fn, points && grad_rgb && packed_fw && packed_bw && workspace, normals, codes, view_origins,
+                                origin_of, n_origins, c_dim, geom, n_freq))
+    return rc;
   ISO_REQUIRE(geom == 6 || !grad_normals, ISO_ERR_INVALID, "iso_texgrad_backward: grad_normals without normals");
   ISO_REQUIRE(c_dim > 0 || !grad_codes, ISO_ERR_INVALID, "iso_texgrad_backward: grad_codes without codes");
   ISO_REQUIRE(workspace_bytes >= 4 * ws.end, ISO_ERR_INVALID, "iso_texgrad_backward: workspace too small");

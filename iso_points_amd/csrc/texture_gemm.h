@@ -1,5 +1,5 @@
-// The split-fp16 layer GEMM of the texture network, its packed weight image and the tile geometry: shared by the forward
-// kernel (texture.hip) and the backward's recompute kernel (texgrad.hip).  Moved out of texture.hip unchanged.
+// The split-fp16 layer GEMM of the texture network and its packed weight image: what the tile skeleton (texture_tile.h) and
+// the pack kernels of texture.hip and texgrad.hip (the reverse sweep runs the same GEMM on transposed images) share.
 #pragma once
 #include "idr_common.h"
 #include "mfma_split.h"
@@ -11,18 +11,6 @@ namespace {
 
 constexpr int kTexAD = 2;            // weight fragments requested two K-steps ahead (idr_x16.hip)
 constexpr int kTexHdr = 64;          // header floats: [0..7] 2^s_l | [16..23] rowsum_l | [32..39] max|b_l|
-constexpr int kTexGeoRows = 48;      // G + V <= 6 + 39
-constexpr int kTexP = 64;            // points per tile
-
-struct TexArgs {
-  const float* points; const float* normals; const float* codes; const float* origins; const int32_t* origin_of;
-  int64_t n_origins;
-  float* rgb;
-  int64_t n;
-  const float* packed;
-  TexShape s;
-  int32_t* tile_ctr;                 // ZERO when the launch starts: the workgroups draw their next tile from it
-};
 
 // packed (floats): header kTexHdr | bias_k n_layers*H (K-order) | head 3*H (K-order rows) | head bias 4 |
 //   FW16_0 K0*H | per l = 1..n_layers-1: FW16_l H*H
@@ -37,6 +25,14 @@ __host__ __device__ inline int64_t texp_fw(const TexShape& s, int l) {     // l 
 __host__ __device__ inline int64_t texp_end(const TexShape& s) { return texp_fw(s, s.n_layers); }
 
 __host__ __device__ inline int tex_feat_of_ko(int64_t ko) { return x3_feat((int)(ko >> 4), 8 * (int)((ko >> 3) & 1) + (int)(ko & 7)); }
+
+// one 32-bit word of a split-fp16 image: two neighbouring values (already under the layer's scale) as two halves, part 0
+// their fp16 roundings, part 1 what the roundings left
+__device__ __forceinline__ unsigned tex_f16_word(f32x2 v, int part) {
+  const f16x2 h = __builtin_convertvector(v, f16x2);
+  const f16x2 lo = __builtin_convertvector(v - __builtin_convertvector(h, f32x2), f16x2);
+  return part == 0 ? __builtin_bit_cast(unsigned, h) : __builtin_bit_cast(unsigned, lo);
+}
 
 // The layer GEMM in THREE passes over K, one partial product each, smallest first: W_l x_h, W_h x_l (each 2^-11 of the
 // result), then W_h x_h.  With all three in one pass (gemm_x3) every 16-term MFMA rounds the accumulator at the magnitude
@@ -123,19 +119,5 @@ __device__ __forceinline__ void tex_gemm(const u32x4* imgw, int a_part, const u3
     }
   }
 }
-
-// ---- the forward kernel ----------------------------------------------------------------------
-template <int H>
-struct TexTile {
-  static constexpr int NW = 8, NB = 2, P = kTexP;
-  static constexpr int NS = H / 16, NTO = H / 32, TW = NTO / NW, SL = 2 * TW;
-  static constexpr int KSA = NS > kTexK0Max / 16 ? NS : kTexK0Max / 16;       // K-steps the activation buffer holds
-  static constexpr size_t kActBytes = (size_t)KSA * NB * kAP * 1024;
-  static constexpr size_t kGeoBytes = (size_t)kTexGeoRows * P * sizeof(float);
-  static constexpr size_t kRedBytes = (size_t)NW * P * 16;
-  static constexpr size_t kLds = kActBytes + kGeoBytes + kRedBytes;
-  static_assert(NTO % NW == 0 && TW >= 1, "features must split evenly over the waves");
-  static_assert(kLds <= 160 * 1024, "LDS budget");
-};
 
 }  // namespace
