@@ -791,13 +791,19 @@ int iso_rasterize_fine(const float* points, const float* ellipse, const float* c
                        int32_t* idx_out, float* zbuf_out, float* qvalue_out, float* occ_out, void* stream);
 
 /* DSS/utils/__init__.py:172-185 (gather_with_neg_idx) for one float per point, as SurfaceSplatting.forward uses it for
- * the fragments' scaler (rasterizer.py:635-637): out[i] = idx[i] >= 0 ? values[idx[i]] : 0, i < n.  idx and out 16-byte
- * aligned.                                                                                                            */
+ * the fragments' scaler (rasterizer.py:635-637): out[i] = idx[i] >= 0 ? values[idx[i]] : 0, i < n.  idx and out must be
+ * 16-byte aligned (they are read and written four entries at a time): ISO_ERR_INVALID otherwise.  The Python
+ * gather_with_neg_idx takes its torch route for an index view that is not.                                            */
 int iso_gather_neg_idx(const float* values, const int32_t* idx, int64_t n, float* out, void* stream);
 
 /* renderer.py:53-78: w = exp(-0.5 q) * scaler[idx] (0 where idx < 0);
  * image[..., c] = sum_k w f / max(sum_k w, eps) (norm_weighted) or sum_k w f;
- * image[..., channels] = occupancy.  frag_scaler_out (n_pixels,K) may be NULL.  */
+ * image[..., channels] = occupancy.  frag_scaler_out (n_pixels,K) may be NULL.
+ * Which kernel runs: points_per_pixel 8 or 4 with channels <= 3 and idx, qvalue and frag_scaler_out (NULL counts) all
+ * 16-byte aligned take a form that holds the pixel's list in registers; every other K, channel count or alignment the
+ * generic loop.  All forms, and the raster's fused epilogue (iso_splat_render), do the same operations in the same
+ * order: bit-identical images (tests/test_composite_gpu.py).  channels <= 8 here and in the backward
+ * (ISO_ERR_UNSUPPORTED above); the Python composite() runs wider features in chunks of 8 channels.  */
 int iso_splat_composite(const int32_t* idx, const float* qvalue, const float* occ,
                         const float* scaler, const float* features, int64_t n_pixels,
                         int points_per_pixel, int channels, int norm_weighted, float eps,

@@ -24,6 +24,7 @@ from . import _lib
 from . import frnn
 from .levelset_sampling import host_lengths, with_host_lengths
 
+_COMPOSITE_CHANNELS = 8      # iso_splat_composite's and its backward's limit (include/isopoints.h); composite() chunks above it
 kMaxPointsPerPixel = 150     # as the reference (rasterization_utils.cuh:18); lists deeper than 32 take the slow kernel
 
 
@@ -1017,7 +1018,8 @@ def gather_with_neg_idx(values, idx):
     """utils/__init__.py:172-185: values[idx], 0 where idx < 0.  One float per point and int32 indices on the GPU (the
     fragments' scaler, rasterizer.py:635-637): one kernel (iso_gather_neg_idx) instead of five elementwise passes."""
     if (values.is_cuda and values.ndim == 1 and values.dtype == torch.float32 and idx.dtype == torch.int32
-            and idx.is_contiguous() and not values.requires_grad):
+            and idx.is_contiguous() and idx.data_ptr() % 16 == 0 and not values.requires_grad):
+        # (the kernel reads idx 16 bytes at a time: a contiguous view at an odd offset takes the torch route below)
         out = torch.empty(idx.shape, dtype=torch.float32, device=idx.device)
         _lib.call("iso_gather_neg_idx", _lib.ptr(values.contiguous()), _lib.ptr(idx), idx.numel(), _lib.ptr(out), _lib.stream())
         return out
@@ -1104,18 +1106,33 @@ class LazyDict(dict):
 
 class _Composite(autograd.Function):
     """iso_splat_composite with its backward: gradients to the per-point features and scaler, the
-    fragments' qvalue and occupancy (idx carries none)."""
+    fragments' qvalue and occupancy (idx carries none).  The kernels take up to _COMPOSITE_CHANNELS channels; wider
+    features (SurfaceSplatting.forward carries 16) run in chunks of that many: the colour channels are independent
+    of each other in the forward, and dL/dw is linear in them, so the chunks' grad_qvalue add up and their
+    grad_scaler accumulates into one buffer."""
 
     @staticmethod
     def forward(ctx, idx, qvalue, occupancy, scaler, features, norm_weighted, eps):
         N, S, S2, K = idx.shape
         C = features.shape[1]
         out = torch.empty((N, S, S2, C + 1), dtype=torch.float32, device=idx.device)
-        idx_c, qv, occ, sc, ft = idx.contiguous(), _f32c(qvalue), _f32c(occupancy), _f32c(scaler), _f32c(features)
-        _lib.call("iso_splat_composite", _lib.ptr(idx_c), _lib.ptr(qv), _lib.ptr(occ), _lib.ptr(sc), _lib.ptr(ft),
-                  N * S * S2, K, C, int(bool(norm_weighted)), float(eps), None, _lib.ptr(out), _lib.stream())
+        idx_c = (idx if idx.dtype == torch.int32 else idx.to(torch.int32)).contiguous()     # the kernels read int32
+        qv, occ, sc, ft = _f32c(qvalue), _f32c(occupancy), _f32c(scaler), _f32c(features)
+        cfg = (int(bool(norm_weighted)), float(eps))
+        if C <= _COMPOSITE_CHANNELS:
+            _lib.call("iso_splat_composite", _lib.ptr(idx_c), _lib.ptr(qv), _lib.ptr(occ), _lib.ptr(sc), _lib.ptr(ft),
+                      N * S * S2, K, C, cfg[0], cfg[1], None, _lib.ptr(out), _lib.stream())
+        else:
+            for c0 in range(0, C, _COMPOSITE_CHANNELS):
+                ftc = ft[:, c0:c0 + _COMPOSITE_CHANNELS].contiguous()
+                Cc = ftc.shape[1]
+                part = torch.empty((N, S, S2, Cc + 1), dtype=torch.float32, device=idx.device)
+                _lib.call("iso_splat_composite", _lib.ptr(idx_c), _lib.ptr(qv), _lib.ptr(occ), _lib.ptr(sc), _lib.ptr(ftc),
+                          N * S * S2, K, Cc, cfg[0], cfg[1], None, _lib.ptr(part), _lib.stream())
+                out[..., c0:c0 + Cc] = part[..., :Cc]
+            out[..., C] = occ
         ctx.save_for_backward(idx_c, qv, sc, ft)
-        ctx.cfg = (int(bool(norm_weighted)), float(eps))
+        ctx.cfg = cfg
         return out
 
     @staticmethod
@@ -1134,8 +1151,23 @@ class _Composite(autograd.Function):
         gsc = torch.zeros_like(sc) if need[3] else None
         gft = torch.zeros_like(ft) if need[4] else None
         p = _lib.ptr
-        _lib.call("iso_splat_composite_backward", p(idx), p(qv), p(sc), p(ft), p(g), N * S * S2, K, C, ctx.cfg[0],
-                  ctx.cfg[1], p(gft), p(gq), p(gsc), p(gocc), _lib.stream())
+        if C <= _COMPOSITE_CHANNELS:
+            _lib.call("iso_splat_composite_backward", p(idx), p(qv), p(sc), p(ft), p(g), N * S * S2, K, C, ctx.cfg[0],
+                      ctx.cfg[1], p(gft), p(gq), p(gsc), p(gocc), _lib.stream())
+            return None, gq, gocc, gsc, gft, None, None
+        gq_c = torch.empty_like(qv) if need[1] else None
+        for c0 in range(0, C, _COMPOSITE_CHANNELS):
+            c1 = min(c0 + _COMPOSITE_CHANNELS, C)
+            ftc = ft[:, c0:c1].contiguous()
+            gc = torch.cat([g[..., c0:c1], g[..., C:]], dim=-1).contiguous()        # the chunk's channels + alpha
+            gftc = torch.zeros_like(ftc) if need[4] else None
+            _lib.call("iso_splat_composite_backward", p(idx), p(qv), p(sc), p(ftc), p(gc), N * S * S2, K, c1 - c0,
+                      ctx.cfg[0], ctx.cfg[1], p(gftc), p(gq if c0 == 0 else gq_c), p(gsc), p(gocc if c1 == C else None),
+                      _lib.stream())
+            if need[1] and c0 > 0:
+                gq += gq_c
+            if need[4]:
+                gft[:, c0:c1] = gftc
         return None, gq, gocc, gsc, gft, None, None
 
 
