@@ -330,6 +330,55 @@ int iso_texgrad_backward(const float* points, const float* normals, const float*
                          float* grad_raw_out, float* grad_points, float* grad_normals, float* grad_codes,
                          void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Backward of the SIREN SDF AND of its gradient (csrc/sirengrad.hip): given u = dL/d sdf (n) and v = dL/d grad (n,3) of
+ * one iso_siren_sdf_grad evaluation, the gradient of every weight and bias and of the points.  With u, v held constant this
+ * is the derivative of u f + v . grad f, and v . grad f is the forward-mode derivative of f along v: one tangent column per
+ * point (s_l = w cos(w z_l)):
+ *   zt_0 = W_0 v, ht_l = s_l zt_l, zt_l = W_l ht_(l-1);  dw_L = sum_p (u h_top + ht_top), db_L = sum_p u
+ *   ztbar_l = htbar_l s_l, zbar_l = hbar_l s_l - w^2 h_l zt_l htbar_l   (seeds hbar_top = u w_L, htbar_top = w_L)
+ *   dW_l = sum_p (zbar_l h_(l-1)^T + ztbar_l ht_(l-1)^T), db_l = sum_p zbar_l, hbar_(l-1) = W_l^T zbar_l, htbar_(l-1) = W_l^T ztbar_l
+ *   dW_0 = sum_p (zbar_0 x^T + ztbar_0 v^T), d pts = W_0^T zbar_0
+ * All matrix products run on the exact f32 matrix instruction, whatever iso_siren_set_gemm_mode says: the sweeps are the f32
+ * tile GEMM of the step kernel (k_siren_step's) on the f32 weight images inside `packed`, a wave's 16 columns being 8 points
+ * x {value, tangent} (k_sirengrad_sweep<hidden / 16, tangent>); dW_l is one product over 2 n rows (k_sirengrad_tn).  The
+ * reduction over the points is cut into chunks of iso_sirengrad_chunk_points() = 256 points BY INDEX: dW_l partials are f32
+ * matrix-instruction chains over a chunk's rows; db_l, dW_0, dw_L and db_L add exact products in float64 and round to f32
+ * once per chunk (k_sirengrad_cols); the partials of one workspace chunk are added in chunk order in ONE float64 chain and
+ * rounded to f32 once, on top of the f32 sum of the earlier workspace chunks (k_sirengrad_reduce).  No float atomic, the same
+ * bits on every call; a point's d pts does not depend on the other points of the call.
+ *
+ * iso_sirengrad_form (host only): 800 + H / 16, H the kernel width that serves a network of `hidden` units (64 / 128 / 256,
+ *   the next one up: the caller zero-pads), for 1 <= hidden <= 256 and 0 <= n_hidden <= 8; 0 for a shape that is refused.
+ * iso_sirengrad_workspace_points / iso_sirengrad_workspace_bytes (host only): the points are processed
+ *   iso_sirengrad_workspace_points() = 16384 at a time, so the workspace stops growing there:
+ *   4 * (256 + 4 * (n_hidden + 1) * mw * hidden + ceil(mw / chunk_points) * raw_floats), mw = min(max(n, 1), 16384);
+ *   0 for a shape iso_sirengrad_backward refuses.
+ * iso_sirengrad_backward: pts (n,3), g_sdf (n), g_grad (n,3) or NULL (only the value was used: the first-order form, 16
+ *   value columns per wave, no tangent work); packed from iso_siren_pack_weights of the same weights, `hidden` its width
+ *   (64 / 128 / 256 exactly: ISO_ERR_UNSUPPORTED otherwise, as n_hidden outside 0..8); raw is the vector packed was made
+ *   from and is not read by this version (it may be NULL).  grad_raw_out in the layout of raw (iso_siren_raw_floats), NULL =
+ *   the weight gradients are not wanted (no dW / db work is done); grad_pts_out (n,3) or NULL.  Outputs are written, not
+ *   accumulated; zero-padded rows and columns of the weights get zero gradients.  n < 0, a NULL pts / g_sdf / packed /
+ *   workspace, and a workspace or packed that is not 16-byte aligned are ISO_ERR_INVALID; a workspace below
+ *   iso_sirengrad_workspace_bytes is ISO_ERR_WORKSPACE; nothing is launched on a refusal.  n == 0 writes zeros to
+ *   grad_raw_out and is ISO_OK.
+ * iso_sirengrad_backward_b0: the same call with layer 0's bias b_0[f] = packed's b_0[f] + b0_tail[f] (hidden floats in natural
+ *   feature order, NULL = none), the sum taken in float64 inside z_0.  For a latent-conditioned SIREN, whose code is folded
+ *   into b_0 (iso_siren_fold_codes: b_0 + W_0[:, :C] c): the f32 rounding of the folded bias is the SAME for every point, so
+ *   unlike a per-point rounding it does not average out of the sums over the points; the caller hands over the bits the
+ *   f32 bias lost (sdf_models.siren_forward).  grad_raw_out's b_0 is the gradient of the whole bias.                       */
+int iso_sirengrad_form(int hidden, int n_hidden);
+int64_t iso_sirengrad_workspace_points(void);
+int64_t iso_sirengrad_chunk_points(void);
+int64_t iso_sirengrad_workspace_bytes(int64_t n, int hidden, int n_hidden);
+int iso_sirengrad_backward(const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* raw,
+                           const float* packed, int hidden, int n_hidden, float omega_first, float omega_hidden,
+                           float* grad_raw_out, float* grad_pts_out, void* workspace, int64_t workspace_bytes, void* stream);
+int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* raw,
+                              const float* packed, int hidden, int n_hidden, float omega_first, float omega_hidden,
+                              float* grad_raw_out, float* grad_pts_out, void* workspace, int64_t workspace_bytes, void* stream,
+                              const float* b0_tail);
+
 /* Nearest point to each ray (brute force, fused): the (R,M) point-to-ray search of
  * CombinedModel.sample_offsurface_using_isopoints, DSS/models/combined_modeling.py:336-352.
  *   pC = p - origin;  ray_sq = (pC . ray)^2;  dist = |pC|^2 - ray_sq;  nn = argmin_m dist

@@ -914,3 +914,27 @@ class NormalLoss(torch.nn.Module):
         if reduction == "mean":
             return loss.mean()
         return loss
+
+
+class NormalLengthLoss(torch.nn.Module):
+    """DSS/training/losses.py:74-83: (|n| - 1)^2 per normal, the Eikonal term on the normals of
+    sdf_models.get_normals_from_grad(requires_grad=True); plain torch on top of the fused SIREN backward."""
+
+    def __init__(self, reduction="mean", **kwargs):
+        super(NormalLengthLoss, self).__init__()
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("Invalid reduction method (%s)" % (reduction,))
+        self.reduction = reduction
+
+    def forward(self, normals, reduction=None):
+        reduction = reduction or self.reduction
+        if reduction not in ("mean", "sum", "none"):
+            raise ValueError("Invalid reduction method (%s)" % (reduction,))
+        if normals.shape[-1] != 3:
+            raise ValueError("NormalLengthLoss: normals must be (..., 3), got %s" % (tuple(normals.shape),))
+        loss = (normals.norm(p=2, dim=-1) - 1) ** 2
+        if reduction == "sum":
+            return loss.sum()
+        if reduction == "mean":
+            return loss.mean()
+        return loss

@@ -8,11 +8,13 @@ by the reference's config factory and one built here are interchangeable for
 `UniformProjection`.  Weights are re-read on every call (they change every optimiser
 step).
 """
+import warnings
 from collections import OrderedDict, namedtuple
 
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib
 
@@ -282,6 +284,219 @@ def siren_sdf_and_grad(model, points, need_grad=True, packed=None, code=None):
         table, code_of = ps.fold(code.codes), code.code_of
         _lib.call("iso_siren_sdf_grad_coded", *args, _lib.ptr(table), _lib.ptr(code_of), table.shape[0])
     return sdf.view(shp[:-1]), (grad.view(shp) if need_grad else None)
+
+
+# ----------------------------------------------------------------------------- training a SIREN on the fused kernels
+def _padded_raw(wb, H, device):
+    """The effective W_0, b_0, .., W_L, b_L as the kernels' raw vector at kernel width H (PackedSiren's zero padding)."""
+    parts, nl = [], len(wb) // 2
+    for i in range(nl):
+        w = wb[2 * i].detach().to(device=device, dtype=torch.float32)
+        b = wb[2 * i + 1].detach().to(device=device, dtype=torch.float32)
+        rows = H if i < nl - 1 else w.shape[0]
+        cols = H if i > 0 else w.shape[1]
+        if (rows, cols) != tuple(w.shape):
+            wp = w.new_zeros((rows, cols))
+            wp[:w.shape[0], :w.shape[1]] = w
+            bp = b.new_zeros((rows,))
+            bp[:b.shape[0]] = b
+            w, b = wp, bp
+        parts += [w.reshape(-1), b.reshape(-1)]
+    return torch.cat(parts).contiguous()
+
+
+def _pack_raw(raw, H, L):
+    lib = _lib.load()
+    assert raw.numel() == lib.iso_siren_raw_floats(H, L)
+    packed = torch.empty((lib.iso_siren_packed_floats(H, L),), dtype=torch.float32, device=raw.device)
+    _lib.call("iso_siren_pack_weights", _lib.ptr(raw), _lib.ptr(packed), H, L, _lib.stream())
+    return packed
+
+
+class _SirenFunction(torch.autograd.Function):
+    """sdf (n,) and grad (n, 3) of the fused evaluation (iso_siren_sdf_grad, in whichever GEMM mode the library is in), with
+    the fused backward (csrc/sirengrad.hip, iso_sirengrad_backward: the f32-MFMA evaluation of the same network,
+    differentiated) into the points and the EFFECTIVE weights and biases W_0, b_0, .., W_L, b_L: those are made under grad
+    by the caller, so whatever parametrisation sits above them (a latent code folded into b_0, the xyz columns of a wider
+    W_0) gets its gradient from torch's own chain.  Only the inputs are kept; the backward packs the weight image again.
+    need_grad False: value only, the second output is an empty, non-differentiable tensor.
+    b0_tail (model width,) f32 or None: the bits layer 0's f32 bias lost when it was formed (a latent code folded in float64);
+    the backward adds them back in float64 (iso_sirengrad_backward_b0), the forward's values are those of the f32 bias."""
+
+    @staticmethod
+    def forward(ctx, shape, need_grad, b0_tail, pts, *wb):
+        H, L, w0, wh = shape
+        dev, n = pts.device, pts.shape[0]
+        lib = _lib.load()
+        if not lib.iso_sirengrad_form(H, L):
+            raise RuntimeError("iso_points_amd: no fused SIREN backward for hidden %d, %d hidden layers" % (H, L))
+        packed = _pack_raw(_padded_raw(wb, H, dev), H, L)
+        sdf = torch.empty((n,), dtype=torch.float32, device=dev)
+        grad = torch.empty((n, 3) if need_grad else (0, 3), dtype=torch.float32, device=dev)
+        ws = torch.empty((lib.iso_project_siren_workspace_bytes(n, H, L),), dtype=torch.uint8, device=dev)
+        _lib.call("iso_siren_sdf_grad", _lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(grad) if need_grad else None, n,
+                  _lib.ptr(packed), H, L, w0, wh, _lib.ptr(ws), ws.numel(), _lib.stream())
+        ctx.shape, ctx.need_grad, ctx.b0_tail = shape, need_grad, b0_tail
+        ctx.save_for_backward(pts, *wb)
+        ctx.set_materialize_grads(False)
+        if not need_grad:
+            ctx.mark_non_differentiable(grad)
+        return sdf, grad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_sdf, g_grad):
+        H, L, w0, wh = ctx.shape
+        pts, wb = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        dev, n = pts.device, pts.shape[0]
+        need = ctx.needs_input_grad
+        if g_sdf is None and (g_grad is None or not ctx.need_grad):
+            return (None,) * len(need)
+        lib = _lib.load()
+        raw = _padded_raw(wb, H, dev)
+        packed = _pack_raw(raw, H, L)
+        u = torch.zeros((n,), dtype=torch.float32, device=dev) if g_sdf is None else \
+            g_sdf.reshape(n).to(torch.float32).contiguous()
+        v = g_grad.reshape(n, 3).to(torch.float32).contiguous() if (ctx.need_grad and g_grad is not None) else None
+        g_pts = torch.empty_like(pts) if need[3] else None
+        g_raw = torch.empty_like(raw) if any(need[4:]) else None      # NULL: no dW / db work is done
+        tail = None
+        if ctx.b0_tail is not None:
+            tail = torch.zeros((H,), dtype=torch.float32, device=dev)
+            tail[:ctx.b0_tail.numel()] = ctx.b0_tail.detach().to(device=dev, dtype=torch.float32)
+        ws = torch.empty((lib.iso_sirengrad_workspace_bytes(n, H, L),), dtype=torch.uint8, device=dev)
+        args = [_lib.ptr(pts), _lib.ptr(u), _lib.ptr(v), n, _lib.ptr(raw), _lib.ptr(packed), H, L, w0, wh, _lib.ptr(g_raw),
+                _lib.ptr(g_pts), _lib.ptr(ws), ws.numel(), _lib.stream()]
+        if tail is None:
+            _lib.call("iso_sirengrad_backward", *args)
+        else:
+            _lib.call("iso_sirengrad_backward_b0", *args, _lib.ptr(tail))
+        grads, at, nl = [], 0, len(wb) // 2
+        for i in range(nl):
+            w, b = wb[2 * i], wb[2 * i + 1]
+            rows = H if i < nl - 1 else w.shape[0]
+            cols = H if i > 0 else w.shape[1]
+            grads.append(g_raw[at:at + rows * cols].reshape(rows, cols)[:w.shape[0], :w.shape[1]].to(w.dtype)
+                         if need[4 + 2 * i] else None)
+            at += rows * cols
+            grads.append(g_raw[at:at + rows][:b.shape[0]].to(b.dtype) if need[5 + 2 * i] else None)
+            at += rows
+        return (None, None, None, g_pts) + tuple(grads)
+
+
+_TORCH_WARNED = set()
+
+
+def _warn_torch_route(model, why):
+    key = (type(model).__name__, why)
+    if key in _TORCH_WARNED:
+        return
+    _TORCH_WARNED.add(key)
+    warnings.warn("iso_points_amd: no fused SIREN backward for %s (%s) -- siren_forward runs model.forward and torch autograd"
+                  % (type(model).__name__, why), RuntimeWarning, stacklevel=3)
+
+
+def _torch_forward(model, points, c, need_grad, train):
+    """model.forward (+ autograd.grad for the gradient) on the GPU: the route of whatever the fused kernels do not run.
+    A code of fewer dimensions than the points is repeated over the points of its row."""
+    shp = points.shape
+    if c is not None and c.numel() > 0 and c.ndim != points.ndim:
+        c = c.reshape((c.shape[0],) + (1,) * (points.ndim - 2) + (c.shape[-1],)) if c.ndim > 1 else \
+            c.reshape((1,) * (points.ndim - 1) + (-1,))
+    if c is not None and c.numel() > 0:
+        c = c.expand(shp[:-1] + (c.shape[-1],))
+    kw = {"c": c} if (c is not None and c.numel() > 0) else {}
+    with torch.enable_grad() if (train or need_grad) else torch.no_grad():
+        p = points if points.requires_grad else points.detach().requires_grad_(need_grad)
+        sdf = model.forward(p, **kw).sdf
+        grad = None
+        if need_grad:
+            grad = torch.autograd.grad(sdf, p, torch.ones_like(sdf), create_graph=train, retain_graph=train)[0]
+    sdf = sdf.reshape(shp[:-1])
+    if not train:
+        sdf, grad = sdf.detach(), (grad.detach() if grad is not None else None)
+    return sdf, grad
+
+
+def siren_forward(model, points, c=None, need_grad=True):
+    """sdf (...) and grad (..., 3) of `model` at points (..., 3) (grad None when need_grad is False), to TRAIN with.
+
+    Under grad mode, when a parameter of the model, the points or the code require grad, the results carry a grad_fn: the
+    fused evaluation with the fused backward (_SirenFunction) into every weight and bias, the points and -- for a
+    latent-conditioned SIREN with ONE code for all points, c (C,) / (1, C) -- the code, whose fold into layer 0's bias is
+    made in torch.  The outputs are those of the GEMM mode the library is in; the backward differentiates the f32-MFMA
+    evaluation of the same network.  Otherwise this is siren_sdf_and_grad, bit for bit.  One code per batch row under
+    grad, and any model siren_spec / coded_siren_spec refuse, take model.forward and torch autograd (one warning per model
+    class)."""
+    if not points.is_cuda:
+        raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
+    has_c = c is not None and torch.is_tensor(c) and c.numel() > 0
+    spec = siren_spec(model)
+    coded = coded_siren_spec(model) if spec is None else None
+    train = torch.is_grad_enabled() and (any(p.requires_grad for p in model.parameters()) or points.requires_grad
+                                         or (has_c and c.requires_grad))
+    if spec is not None and has_c:
+        raise ValueError("a latent-conditioned SIREN needs its code, an unconditioned one takes none")
+    if coded is not None and not has_c:
+        raise ValueError("iso_points_amd: this SIREN is conditioned on a latent code (c_dim = %d): pass c" % coded[3])
+    if spec is None and coded is None:
+        _warn_torch_route(model, "not a SIREN the fused kernels run")
+        return _torch_forward(model, points, c, need_grad, train)
+    if not train:
+        if spec is not None:
+            return siren_sdf_and_grad(model, points, need_grad=need_grad)
+        rows = points.shape[0] if points.ndim > 1 else 1
+        code = code_rows(c, coded[3], [points.numel() // 3 // max(rows, 1)] * rows)
+        if code is None:
+            _warn_torch_route(model, "code shape outside the kernels'")
+            return _torch_forward(model, points, c, need_grad, train)
+        return siren_sdf_and_grad(model, points, need_grad=need_grad, code=code)
+    b0_tail = None
+    if spec is not None:
+        lins, w0, wh = spec
+        wb = [t for lin in lins for t in (lin.weight, lin.bias)]
+    else:
+        lins, w0, wh, C = coded
+        if not (c.shape[-1] == C and c.numel() == C):
+            _warn_torch_route(model, "one code per batch row")
+            return _torch_forward(model, points, c, need_grad, train)
+        # the fold in float64, rounded to f32 once (iso_siren_fold_codes' rule); what the rounding drops is the same for
+        # every point and would not average out of the sums over the points: the backward gets it as b0_tail
+        W0 = lins[0].weight
+        b64 = lins[0].bias.double() + W0[:, :C].double() @ c.reshape(C).double()
+        b0 = b64.to(torch.float32)
+        b0_tail = (b64.detach() - b0.detach().double()).to(torch.float32)
+        wb = [W0[:, C:], b0] + [t for lin in lins[1:] for t in (lin.weight, lin.bias)]
+    Hm = lins[0].out_features
+    H = next(h for h in (64, 128, 256) if h >= Hm)
+    shp = points.shape
+    pts = points.reshape(-1, 3).to(torch.float32).contiguous()
+    sdf, grad = _SirenFunction.apply((H, len(lins) - 2, float(w0), float(wh)), bool(need_grad), b0_tail, pts, *wb)
+    return sdf.view(shp[:-1]), (grad.view(shp) if need_grad else None)
+
+
+def get_normals_from_grad(decoder, p_world, c=None, requires_grad=False, return_sdf=False, **kwargs):
+    """DSS/models/implicit_modeling.py:250-277 for a decoder handed in: the not normalised normals at p_world (N, *, 3), the
+    gradient of the SDF w.r.t. the points; with return_sdf also the sdf (N, *, 1).  requires_grad=True: the normals (and
+    the sdf) backpropagate into the decoder and the points, through siren_forward's fused backward for a SIREN;
+    requires_grad=False: detached normals.  Further forward kwargs take model.forward."""
+    if kwargs:
+        _warn_torch_route(decoder, "forward kwargs")
+        with torch.enable_grad():
+            p = p_world if p_world.requires_grad else p_world.detach().requires_grad_(True)
+            sdf = decoder.forward(p, c=c, **kwargs).sdf
+            normals = torch.autograd.grad(sdf, p, torch.ones_like(sdf), create_graph=requires_grad,
+                                          retain_graph=requires_grad or return_sdf)[0]
+        sdf = sdf.reshape(p_world.shape[:-1])
+    else:
+        # as the reference, the sdf handed back keeps its graph whether or not the normals do
+        with torch.enable_grad() if (requires_grad or return_sdf) else torch.no_grad():
+            sdf, normals = siren_forward(decoder, p_world, c=c, need_grad=True)
+    if not requires_grad:
+        normals = normals.detach()
+    if return_sdf:
+        return normals, sdf.unsqueeze(-1)
+    return normals
 
 
 # ----------------------------------------------------------------------------- IDR-style SDF
