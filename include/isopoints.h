@@ -379,6 +379,49 @@ int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, const float*
                               float* grad_raw_out, float* grad_pts_out, void* workspace, int64_t workspace_bytes, void* stream,
                               const float* b0_tail);
 
+/* Backward of the IDR SDF AND of its gradient (csrc/idrgrad.hip): given u = dL/d sdf (n) and v = dL/d grad (n,3) of one
+ * iso_idr_sdf_grad evaluation, the gradient of every EFFECTIVE weight and bias and of the points.  As iso_sirengrad_backward:
+ * with u, v held constant this is the derivative of u f + v . grad f, one tangent column per point:
+ *   et_k = dval_k v_c(k), zt_l = W_l int_l, s_l = sigmoid(beta z_l), ht_l = s_l zt_l, int_skip = [ht_(skip-1); et] / sqrt(2)
+ *   yt = w_n . ht_(n-1), d = 1 - f^2;  ybar = d (u - 2 f yt), ytbar = d;  dw_n = sum_p (ybar h_(n-1) + ytbar ht_(n-1)), db_n = sum_p ybar
+ *   ztbar_l = htbar_l s_l, zbar_l = hbar_l s_l + htbar_l zt_l s'_l, s'_l = beta s_l (1 - s_l)   (seeds ybar w_n, ytbar w_n)
+ *   dW_l = sum_p (zbar_l in_l^T + ztbar_l int_l^T), db_l = sum_p zbar_l, inbar_l = W_l^T zbar_l, intbar_l = W_l^T ztbar_l
+ *   d pts_c = sum over the encoding slots k of coordinate c of (ebar_k dval_k + etbar_k d2val_k v_c)
+ * All matrix products run on the exact f32 matrix instruction, whatever iso_idr_set_gemm_mode says: the sweeps are the staged
+ * f32 tile GEMM on the FW / BW / FW0 / W0v images inside `packed`, a wave's 16 columns being 8 points x {value, tangent}
+ * (k_idrgrad_sweep<hidden / 16, tangent>, one workgroup per CU, 160 KiB of LDS at hidden 512); dW_l is one product over 2 n
+ * rows (k_idrgrad_tn; dW_0 on a 64-wide stash of the encoding).  The reduction over the points is cut into chunks of
+ * iso_idrgrad_chunk_points() = 256 points BY INDEX: dW_l partials are f32 matrix-instruction chains over a chunk's rows; db_l,
+ * dw_n and db_n add exact products in float64 and round to f32 once per chunk (k_idrgrad_cols); the partials of one workspace
+ * chunk are added in chunk order in ONE float64 chain and rounded to f32 once, on top of the f32 sum of the earlier workspace
+ * chunks (k_idrgrad_reduce).  No float atomic, the same bits on every call; a point's d pts does not depend on the other
+ * points of the call.
+ *
+ * iso_idrgrad_form (host only): 900 + hidden / 16 for every shape iso_idr_pack_weights accepts (hidden 128 / 256 / 512, 2..12
+ *   layers, n_freq <= 10, skip_layer < 0 or in 1 .. n_layers - 1); 0 for a shape that is refused.
+ * iso_idrgrad_workspace_points / iso_idrgrad_workspace_bytes (host only): the points are processed
+ *   iso_idrgrad_workspace_points() = 8192 at a time (one 32-point tile for each of 256 workgroups), so the workspace stops
+ *   growing there.  In floats, with mw = min(max(n, 1), 8192):
+ *     512 zeros | 2 mw * 64 encoding stash | n_layers * 2 mw * hidden input stash (in_1 .. in_(n-1), h_(n-1)) |
+ *     n_layers * 2 mw * hidden derivative stash (s_l | zt_l s'_l, then zbar_l | ztbar_l) | 2 mw head | ceil(mw / 256) * raw_floats
+ *   every stash row-major, row 2 p the value row of point p and row 2 p + 1 its tangent row (row p without g_grad).  For the
+ *   reference's 8 x 512, skip 4, 6 frequencies that is 776 598 784 bytes from 8192 points on; 0 for a refused shape.
+ * iso_idrgrad_backward: pts (n,3), g_sdf (n), g_grad (n,3) or NULL (only the value was used: the first-order form, 16 value
+ *   columns per wave, no tangent work); packed from iso_idr_pack_weights of the same weights; raw is the vector packed was
+ *   made from and is not read by this version (it may be NULL); beta must be 100.  grad_raw_out in the layout of raw
+ *   (iso_idr_raw_floats: the narrow layer at its true hidden - D0 rows), NULL = the weight gradients are not wanted (no dW / db
+ *   work is done); grad_pts_out (n,3) or NULL; both NULL: nothing is launched.  Outputs are written, not accumulated.  An
+ *   unsupported shape or beta is ISO_ERR_UNSUPPORTED; n < 0, a NULL pts / g_sdf / packed / workspace, and a workspace or
+ *   packed that is not 16-byte aligned are ISO_ERR_INVALID; a workspace below iso_idrgrad_workspace_bytes is
+ *   ISO_ERR_WORKSPACE; nothing is launched on a refusal.  n == 0 writes zeros to grad_raw_out and is ISO_OK.               */
+int iso_idrgrad_form(int hidden, int n_layers, int skip_layer, int n_freq);
+int64_t iso_idrgrad_workspace_points(void);
+int64_t iso_idrgrad_chunk_points(void);
+int64_t iso_idrgrad_workspace_bytes(int64_t n, int hidden, int n_layers, int skip_layer, int n_freq);
+int iso_idrgrad_backward(const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* raw,
+                         const float* packed, int hidden, int n_layers, int skip_layer, int n_freq, float beta,
+                         float* grad_raw_out, float* grad_pts_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Nearest point to each ray (brute force, fused): the (R,M) point-to-ray search of
  * CombinedModel.sample_offsurface_using_isopoints, DSS/models/combined_modeling.py:336-352.
  *   pC = p - origin;  ray_sq = (pC . ray)^2;  dist = |pC|^2 - ray_sq;  nn = argmin_m dist

@@ -16,12 +16,6 @@
 
 namespace {
 
-bool idr_shape_ok(int H, int n_layers, int skip, int F) {
-  const int D0 = 3 + 6 * F;
-  return (H == 128 || H == 256 || H == 512) && n_layers >= 2 && n_layers <= 12 && F >= 0 && F <= 10 &&
-         D0 <= 63 && (skip < 0 || (skip >= 1 && skip < n_layers)) && H > D0;
-}
-
 // 1 = split-fp16 kernel (idr_x16.hip) where idr_x16_supported: H = 256 / 512 with encodings of <= 39 slots; 0 = the f32-MFMA
 // kernels of idr_f32.hip for every shape.  Default 1; ISO_IDR_GEMM=f32 in the environment selects 0 at load time.
 int g_idr_gemm_mode = -1;

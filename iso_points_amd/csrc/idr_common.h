@@ -35,6 +35,13 @@ constexpr int kD0Pad = 64;          // padded encoding width (D0 = 3 + 6F <= 63)
 constexpr int kW0Row = 64;          // floats per feature row of the VALU backward image
 constexpr int kIdrFsEncRows = 48;   // encoding rows of the feature-split f32 kernel: D0 <= 48 (F <= 7), wider ones are staged
 
+// the shapes every IDR entry point accepts (idr.hip's forward entries, idrgrad.hip's backward)
+inline bool idr_shape_ok(int H, int n_layers, int skip, int F) {
+  const int D0 = 3 + 6 * F;
+  return (H == 128 || H == 256 || H == 512) && n_layers >= 2 && n_layers <= 12 && F >= 0 && F <= 10 &&
+         D0 <= 63 && (skip < 0 || (skip >= 1 && skip < n_layers)) && H > D0;
+}
+
 // packed buffer (floats):
 //   [b0 H][FW0 (kD0Pad/16)*NT*256][W0v 4*(H/4)*kW0Row]
 //   per l = 1..n_layers-1: [b_l H][FW_l H*H][BW_l H*H]
@@ -116,6 +123,33 @@ __device__ __forceinline__ void softplus_b(float z, float beta, float& y, float&
   const bool lin = t > 20.0f;
   y = lin ? z : sp;
   dy = lin ? 1.0f : sg;
+}
+
+// softplus_b's sibling for the backward of the gradient (idrgrad.hip): the same y and dy, instruction for instruction, and
+// the second derivative d2y = beta s (1 - s) = beta u / (1 + u)^2 (0 on the linear branch), formed from u, not from 1 - s
+__device__ __forceinline__ void softplus_b2(float z, float beta, float& y, float& dy, float& d2y) {
+  const float t = z * beta;
+  const float inv_beta = 1.0f / beta;
+  const float at = __builtin_fabsf(t);
+  const float L2E_hi = 1.44269502162933349609375f, L2E_lo = 1.925963033500011e-08f;
+  const float n = __builtin_rintf(-at * L2E_hi);
+  float f = __builtin_fmaf(-at, L2E_hi, -n);
+  f = __builtin_fmaf(-at, L2E_lo, f);
+  const float u = __builtin_amdgcn_exp2f(f) * __builtin_amdgcn_exp2f(__builtin_fmaxf(n, -126.0f));
+  const float w = 1.0f + u;
+  const float d = w - 1.0f;
+  const float rw = iso_rcp_nr(w);
+  const float lnw = __builtin_amdgcn_logf(w) * 0.693147180559945309f;
+  const float rd = __builtin_amdgcn_rcpf(d);
+  float q = u * rd;
+  q = __builtin_fmaf(__builtin_fmaf(-q, d, u), rd, q);
+  const float l1p = d == 0.0f ? u : lnw * q;
+  const float sp = (__builtin_fmaxf(t, 0.0f) + l1p) * inv_beta;
+  const float sg = t >= 0.0f ? rw : u * rw;
+  const bool lin = t > 20.0f;
+  y = lin ? z : sp;
+  dy = lin ? 1.0f : sg;
+  d2y = lin ? 0.0f : beta * ((u * rw) * rw);
 }
 
 }  // namespace

@@ -478,7 +478,7 @@ def siren_forward(model, points, c=None, need_grad=True):
 def get_normals_from_grad(decoder, p_world, c=None, requires_grad=False, return_sdf=False, **kwargs):
     """DSS/models/implicit_modeling.py:250-277 for a decoder handed in: the not normalised normals at p_world (N, *, 3), the
     gradient of the SDF w.r.t. the points; with return_sdf also the sdf (N, *, 1).  requires_grad=True: the normals (and
-    the sdf) backpropagate into the decoder and the points, through siren_forward's fused backward for a SIREN;
+    the sdf) backpropagate into the decoder and the points, through sdf_forward's fused backward for a SIREN or an IDR network;
     requires_grad=False: detached normals.  Further forward kwargs take model.forward."""
     if kwargs:
         _warn_torch_route(decoder, "forward kwargs")
@@ -491,7 +491,7 @@ def get_normals_from_grad(decoder, p_world, c=None, requires_grad=False, return_
     else:
         # as the reference, the sdf handed back keeps its graph whether or not the normals do
         with torch.enable_grad() if (requires_grad or return_sdf) else torch.no_grad():
-            sdf, normals = siren_forward(decoder, p_world, c=c, need_grad=True)
+            sdf, normals = sdf_forward(decoder, p_world, c=c, need_grad=True)
     if not requires_grad:
         normals = normals.detach()
     if return_sdf:
@@ -593,6 +593,111 @@ def idr_sdf_and_grad(model, points, need_grad=True, packed=None):
     _lib.call("iso_idr_sdf_grad", _lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(grad), n, _lib.ptr(pk.packed), pk.hidden,
               pk.n_layers, pk.skip, pk.n_freq, 100.0, _lib.ptr(ws), ws.numel(), _lib.stream())
     return sdf.view(shp[:-1]), (grad.view(shp) if need_grad else None)
+
+
+# ----------------------------------------------------------------------------- training an IDR network on the fused kernels
+def _idr_raw(wb, device):
+    """The effective W_0, b_0, .., W_n, b_n as the kernels' raw vector (iso_idr_raw_floats: true shapes, no padding)"""
+    return torch.cat([t.detach().to(device=device, dtype=torch.float32).reshape(-1) for t in wb]).contiguous()
+
+
+def _idr_pack_raw(raw, H, nl, skip, F_):
+    lib = _lib.load()
+    assert raw.numel() == lib.iso_idr_raw_floats(H, nl, skip, F_)
+    packed = torch.empty((lib.iso_idr_packed_floats(H, nl),), dtype=torch.float32, device=raw.device)
+    _lib.call("iso_idr_pack_weights", _lib.ptr(raw), _lib.ptr(packed), H, nl, skip, F_, _lib.stream())
+    return packed
+
+
+class _IdrFunction(torch.autograd.Function):
+    """sdf (n,) and grad (n, 3) of the fused evaluation (iso_idr_sdf_grad, in whichever GEMM mode the library is in), with the
+    fused backward (csrc/idrgrad.hip, iso_idrgrad_backward: the f32-MFMA evaluation of the same network, differentiated) into
+    the points and the EFFECTIVE weights and biases W_0, b_0, .., W_n, b_n: those are made under grad by the caller
+    (_effective_weight, the oracle's model.weight(l)), so weight norm's g and v get their gradients from torch's own chain.
+    Only the inputs are kept; the backward packs the weight image again.  need_grad False: value only, the second output is
+    an empty, non-differentiable tensor."""
+
+    @staticmethod
+    def forward(ctx, shape, need_grad, pts, *wb):
+        H, nl, skip, F_ = shape
+        dev, n = pts.device, pts.shape[0]
+        lib = _lib.load()
+        if not lib.iso_idrgrad_form(H, nl, skip, F_):
+            raise RuntimeError("iso_points_amd: no fused IDR backward for hidden %d, %d layers, skip %d, %d frequencies"
+                               % (H, nl, skip, F_))
+        packed = _idr_pack_raw(_idr_raw(wb, dev), H, nl, skip, F_)
+        sdf = torch.empty((n,), dtype=torch.float32, device=dev)
+        grad = torch.empty((n, 3) if need_grad else (0, 3), dtype=torch.float32, device=dev)
+        ws = torch.empty((lib.iso_project_idr_workspace_bytes(n, H, nl),), dtype=torch.uint8, device=dev)
+        _lib.call("iso_idr_sdf_grad", _lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(grad) if need_grad else None, n, _lib.ptr(packed),
+                  H, nl, skip, F_, 100.0, _lib.ptr(ws), ws.numel(), _lib.stream())
+        ctx.shape, ctx.need_grad = shape, need_grad
+        ctx.save_for_backward(pts, *wb)
+        ctx.set_materialize_grads(False)
+        if not need_grad:
+            ctx.mark_non_differentiable(grad)
+        return sdf, grad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_sdf, g_grad):
+        H, nl, skip, F_ = ctx.shape
+        pts, wb = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        dev, n = pts.device, pts.shape[0]
+        need = ctx.needs_input_grad
+        if g_sdf is None and (g_grad is None or not ctx.need_grad):
+            return (None,) * len(need)
+        lib = _lib.load()
+        raw = _idr_raw(wb, dev)
+        packed = _idr_pack_raw(raw, H, nl, skip, F_)
+        u = torch.zeros((n,), dtype=torch.float32, device=dev) if g_sdf is None else \
+            g_sdf.reshape(n).to(torch.float32).contiguous()
+        v = g_grad.reshape(n, 3).to(torch.float32).contiguous() if (ctx.need_grad and g_grad is not None) else None
+        g_pts = torch.empty_like(pts) if need[2] else None
+        g_raw = torch.empty_like(raw) if any(need[3:]) else None      # NULL: no dW / db work is done
+        ws = torch.empty((lib.iso_idrgrad_workspace_bytes(n, H, nl, skip, F_),), dtype=torch.uint8, device=dev)
+        _lib.call("iso_idrgrad_backward", _lib.ptr(pts), _lib.ptr(u), _lib.ptr(v), n, _lib.ptr(raw), _lib.ptr(packed), H, nl,
+                  skip, F_, 100.0, _lib.ptr(g_raw), _lib.ptr(g_pts), _lib.ptr(ws), ws.numel(), _lib.stream())
+        grads, at = [], 0
+        for i, t in enumerate(wb):
+            grads.append(g_raw[at:at + t.numel()].reshape(t.shape).to(t.dtype) if need[3 + i] else None)
+            at += t.numel()
+        return (None, None, g_pts) + tuple(grads)
+
+
+def idr_forward(model, points, need_grad=True):
+    """sdf (...) and grad (..., 3) of an IDR-style SDF (idr_spec) at points (..., 3) (grad None when need_grad is False), to
+    TRAIN with.  Under grad mode, when a parameter of the model or the points require grad, the results carry a grad_fn: the
+    fused evaluation with the fused backward (_IdrFunction) into every effective weight and bias -- and through torch's chain
+    into weight norm's g and v -- and into the points.  The outputs are those of the GEMM mode the library is in; the backward
+    differentiates the f32-MFMA evaluation of the same network.  Otherwise this is idr_sdf_and_grad, bit for bit."""
+    if not points.is_cuda:
+        raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
+    train = torch.is_grad_enabled() and (any(p.requires_grad for p in model.parameters()) or points.requires_grad)
+    if not train:
+        return idr_sdf_and_grad(model, points, need_grad=need_grad)
+    spec = idr_spec(model)                       # the effective weights, made under grad
+    if spec is None:
+        raise ValueError("model is not an IDR-style SDF the fused kernel supports")
+    Ws, bs, H, nl, skip, F_ = spec
+    wb = [t for W, b in zip(Ws, bs) for t in (W, b)]
+    shp = points.shape
+    pts = points.reshape(-1, 3).to(torch.float32).contiguous()
+    sdf, grad = _IdrFunction.apply((H, nl, skip, F_), bool(need_grad), pts, *wb)
+    return sdf.view(shp[:-1]), (grad.view(shp) if need_grad else None)
+
+
+def sdf_forward(model, points, c=None, need_grad=True):
+    """siren_forward for a SIREN or a latent-conditioned SIREN, idr_forward for an IDR-style SDF (which takes no code), and
+    siren_forward's torch route with its one warning for anything else: sdf (...) and grad (..., 3) to train with."""
+    if siren_spec(model) is None and coded_siren_spec(model) is None:
+        with torch.no_grad():
+            is_idr = idr_spec(model) is not None
+        if is_idr:
+            if c is not None and torch.is_tensor(c) and c.numel() > 0:
+                raise ValueError("iso_points_amd: an IDR-style SDF takes no latent code")
+            return idr_forward(model, points, need_grad=need_grad)
+    return siren_forward(model, points, c=c, need_grad=need_grad)
 
 
 class FusedSdf(object):
