@@ -344,7 +344,7 @@ int iso_texgrad_backward(const float* points, const float* normals, const float*
  * reduction over the points is cut into chunks of iso_sirengrad_chunk_points() = 256 points BY INDEX: dW_l partials are f32
  * matrix-instruction chains over a chunk's rows; db_l, dW_0, dw_L and db_L add exact products in float64 and round to f32
  * once per chunk (k_sirengrad_cols); the partials of one workspace chunk are added in chunk order in ONE float64 chain and
- * rounded to f32 once, on top of the f32 sum of the earlier workspace chunks (k_sirengrad_reduce).  No float atomic, the same
+ * rounded to f32 once, on top of the f32 sum of the earlier workspace chunks (k_grad_reduce).  No float atomic, the same
  * bits on every call; a point's d pts does not depend on the other points of the call.
  *
  * iso_sirengrad_form (host only): 800 + H / 16, H the kernel width that serves a network of `hidden` units (64 / 128 / 256,
@@ -390,11 +390,11 @@ int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, const float*
  * All matrix products run on the exact f32 matrix instruction, whatever iso_idr_set_gemm_mode says: the sweeps are the staged
  * f32 tile GEMM on the FW / BW / FW0 / W0v images inside `packed`, a wave's 16 columns being 8 points x {value, tangent}
  * (k_idrgrad_sweep<hidden / 16, tangent>, one workgroup per CU, 160 KiB of LDS at hidden 512); dW_l is one product over 2 n
- * rows (k_idrgrad_tn; dW_0 on a 64-wide stash of the encoding).  The reduction over the points is cut into chunks of
+ * rows (k_grad_tn; dW_0 on a 64-wide stash of the encoding).  The reduction over the points is cut into chunks of
  * iso_idrgrad_chunk_points() = 256 points BY INDEX: dW_l partials are f32 matrix-instruction chains over a chunk's rows; db_l,
  * dw_n and db_n add exact products in float64 and round to f32 once per chunk (k_idrgrad_cols); the partials of one workspace
  * chunk are added in chunk order in ONE float64 chain and rounded to f32 once, on top of the f32 sum of the earlier workspace
- * chunks (k_idrgrad_reduce).  No float atomic, the same bits on every call; a point's d pts does not depend on the other
+ * chunks (k_grad_reduce).  No float atomic, the same bits on every call; a point's d pts does not depend on the other
  * points of the call.
  *
  * iso_idrgrad_form (host only): 900 + hidden / 16 for every shape iso_idr_pack_weights accepts (hidden 128 / 256 / 512, 2..12

@@ -16,7 +16,7 @@
 //   points    dx_c = sum over k with coord(k) = c of (ebar_k dval_k + etbar_k d2val_k v_c); d2val is 0 for the identity
 //             slots, -fr^2 sin for the sine slots, -fr^2 cos for the cosine slots.  No gradient flows into v.
 //   v absent  the first-order backward: no tangent column, zbar_l = hbar_l s_l, ybar = d u.
-// Kernels (sirengrad.hip's plan, restated: its kernels take square H x H layers of one width and stay as their tests pin them):
+// Kernels (sirengrad.hip's plan; the sweeps share sdf_grad_tile.h, the sums are grad_sums.hip's):
 //   sweep     both sweeps of one tile in one workgroup; a wave's 16 matrix-instruction columns are 8 points x {value,
 //             tangent} (lane j < 8 the value column of point j, lane j + 8 its tangent column).  Layer 0 multiplies the
 //             64-wide padded encoding by FW0 straight from L2 (4 q-chunks: 1 / NT of a hidden layer, no barrier, no second
@@ -29,12 +29,14 @@
 //             Staged layout: 5 * NT * 256 floats of LDS, the whole 160 KiB at NT = 32, as k_idr_step<32> runs.
 //                                                                                                  k_idrgrad_sweep<NT, TAN>
 //   weights   dW_l = [zbar_l; ztbar_l]^T [in_l; int_l] on the f32 matrix instruction over FIXED chunks of kIgPart points;
-//             dW_0 (H x D0) by the same kernel on the 64-wide encoding stash                                  k_idrgrad_tn
+//             dW_0 (H x D0) by the same kernel on the 64-wide encoding stash                     k_grad_tn (grad_sums.hip)
 //             db_l, dw_n, db_n: column sums in float64 by the same chunks                                   k_idrgrad_cols
-//   reduce    the partials added in chunk order, on top of the earlier workspace chunks                   k_idrgrad_reduce
+//   reduce    the partials added in chunk order, on top of the earlier workspace chunks     k_grad_reduce (grad_sums.hip)
 // No float atomic anywhere; a point's dx does not depend on its tile neighbours; the points are taken kIgWs at a time.
+#include "grad_sums.h"
 #include "idr_common.h"
 #include "mfma_split.h"
+#include "sdf_grad_tile.h"
 
 namespace {
 
@@ -241,9 +243,7 @@ __global__ __launch_bounds__(256, 1) void k_idrgrad_sweep(IgArgs a) {
       }
       if (l == 0) break;
       const float* base = a.packed + idr_off_layer(H, l);
-      gemm_pass<NT, false>(base + H + (int64_t)H * H, nullptr, hL, wbuf, acc, lane, g);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) hL4[t * 64 + lane] = acc[t];
+      sdf_grad_reverse_gemm<NT>(base + H + (int64_t)H * H, hL, wbuf, acc, lane, g);
       if (l == s.skip) {
         // adjoint of [h_(skip-1); e] / sqrt(2): all divided; the encoding slots' part leaves for dx (what stays in those
         // slots meets the narrow layer's stashed zeros)
@@ -290,11 +290,7 @@ __global__ __launch_bounds__(256, 1) void k_idrgrad_sweep(IgArgs a) {
         gy += c == 1 ? contrib : 0.0;
         gz += c == 2 ? contrib : 0.0;
       }
-      gx += __shfl_xor(gx, 16); gx += __shfl_xor(gx, 32);
-      gy += __shfl_xor(gy, 16); gy += __shfl_xor(gy, 32);
-      gz += __shfl_xor(gz, 16); gz += __shfl_xor(gz, 32);
-      if constexpr (TAN) { gx += __shfl_xor(gx, 8); gy += __shfl_xor(gy, 8); gz += __shfl_xor(gz, 8); }
-      if (valid && !tan && g == 0) { a.dx[p * 3] = (float)gx; a.dx[p * 3 + 1] = (float)gy; a.dx[p * 3 + 2] = (float)gz; }
+      sdf_grad_store_dx<TAN>(gx, gy, gz, a.dx, p, valid && !tan && g == 0);      // the tangent lane holds half the terms
     }
     __syncthreads();
   }
@@ -317,88 +313,6 @@ int ig_dispatch_sweep(const IgArgs& a, int H, hipStream_t st) {
   }
 }
 
-// ---- dW partial of one layer: part[c][o][i] = sum over the stash rows of chunk c of A[r][o] B[r][i] -----------------------
-// k_sirengrad_tn's tile (one wave per 64 x 64 tile of dW, both operands read row-major straight from the stashes, two rows per
-// matrix instruction in ascending order, two chains), with a row length per operand -- B is the 64-wide encoding stash for
-// layer 0 -- and the true size of the layer's matrix: rows past out_rows (the narrow layer) and columns past out_cols (the
-// encoding's padding) are not written.
-struct IgTnArgs {
-  const float* A;                    // zbar_l | ztbar_l rows (rows, ldA)
-  const float* B;                    // in_l | int_l rows (rows, ldB)
-  int ldA, ldB;
-  int64_t rows;
-  int64_t rows_per_chunk;
-  float* part;                       // partial c at part + c * part_stride, row-major (out_rows, out_cols)
-  int64_t part_stride;
-  int out_rows, out_cols;
-};
-
-__global__ __launch_bounds__(256) void k_idrgrad_tn(IgTnArgs a) {
-  const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, j = lane & 31, hh = lane >> 5;
-  const int tiles_o = a.ldA / 64, tiles_i = a.ldB / 64;
-  const int tile = blockIdx.x * 4 + w;
-  if (tile >= tiles_o * tiles_i) return;             // no barrier below
-  const int o0 = 64 * (tile / tiles_i), i0 = 64 * (tile % tiles_i);
-  if (o0 >= a.out_rows || i0 >= a.out_cols) return;
-  const int64_t ldA = a.ldA, ldB = a.ldB;
-  const int64_t p0 = (int64_t)blockIdx.y * a.rows_per_chunk;
-  const int64_t pend = p0 + a.rows_per_chunk < a.rows ? p0 + a.rows_per_chunk : a.rows;
-  f32x16 acc[2][2][2];
-#pragma unroll
-  for (int c = 0; c < 2; ++c)
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[c][t][u][r] = 0.f;
-  const float* __restrict__ Ap = a.A + o0 + j;
-  const float* __restrict__ Bp = a.B + i0 + j;
-  auto group = [&](int64_t p, f32x16 (&ac)[2][2]) {      // sixteen rows: 32 loads in flight, then 32 matrix instructions
-    float av[8][2], bv[8][2];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int64_t pp = p + 2 * u + hh;
-      av[u][0] = Ap[pp * ldA]; av[u][1] = Ap[pp * ldA + 32];
-      bv[u][0] = Bp[pp * ldB]; bv[u][1] = Bp[pp * ldB + 32];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      ac[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][0], bv[u][0], ac[0][0], 0, 0, 0);
-      ac[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][0], bv[u][1], ac[0][1], 0, 0, 0);
-      ac[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][1], bv[u][0], ac[1][0], 0, 0, 0);
-      ac[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[u][1], bv[u][1], ac[1][1], 0, 0, 0);
-    }
-  };
-  int64_t p = p0;
-  for (; p + 32 <= pend; p += 32) { group(p, acc[0]); group(p + 16, acc[1]); }
-  if (p + 16 <= pend) { group(p, acc[0]); p += 16; }
-  for (; p < pend; p += 2) {                   // the last rows, fewer than sixteen, on the second chain
-    const int64_t pp = p + hh;
-    float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f;
-    if (pp < pend) {
-      a0 = Ap[pp * ldA]; a1 = Ap[pp * ldA + 32];
-      b0 = Bp[pp * ldB]; b1 = Bp[pp * ldB + 32];
-    }
-    acc[1][0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[1][0][0], 0, 0, 0);
-    acc[1][0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[1][0][1], 0, 0, 0);
-    acc[1][1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][1][0], 0, 0, 0);
-    acc[1][1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1][1], 0, 0, 0);
-  }
-  float* __restrict__ out = a.part + (int64_t)blockIdx.y * a.part_stride;
-#pragma unroll
-  for (int t = 0; t < 2; ++t)
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int col = i0 + 32 * u + j;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int row = o0 + 32 * t + 8 * (r >> 2) + 4 * hh + (r & 3);
-        if (row < a.out_rows && col < a.out_cols) out[(int64_t)row * a.out_cols + col] = acc[0][t][u][r] + acc[1][t][u][r];
-      }
-    }
-}
-
 // ---- column sums of one partial chunk: db_l of every softplus layer, dw_n and db_n ---------------------------------------
 // The terms are exact products added in float64 and rounded to f32 once.  A workgroup is 64 columns x 4 quarters of the
 // chunk's points, the quarters added in order through LDS.  grid (chunks, H / 64, n + 1): z < n is layer z, z = n the head.
@@ -413,14 +327,10 @@ struct IgColArgs {
 
 __global__ __launch_bounds__(256) void k_idrgrad_cols(IgColArgs a) {
   __shared__ double sq[4][2][64];
-  constexpr int Q = kIgPart / 4;
   const int H = a.s.H, nL = a.s.n_layers, z = blockIdx.z, kq = threadIdx.x & 63, q = threadIdx.x >> 6, k = blockIdx.y * 64 + kq;
   const int R = a.R;
-  const int64_t c0 = (int64_t)blockIdx.x * kIgPart;
-  const int64_t cend = c0 + kIgPart < a.m ? c0 + kIgPart : a.m;
-  int64_t p0 = c0 + (int64_t)q * Q;
-  int64_t pend = p0 + Q < cend ? p0 + Q : cend;
-  if (p0 > pend) p0 = pend;
+  int64_t p0, pend;
+  grad_quarter_range(blockIdx.x, q, kIgPart, a.m, p0, pend);
   double s0 = 0.0, s1 = 0.0;
   if (z < nL) {
     const float* __restrict__ zb = a.sst + (int64_t)z * a.lstride + k;
@@ -446,16 +356,6 @@ __global__ __launch_bounds__(256) void k_idrgrad_cols(IgColArgs a) {
   } else {
     out[idr_raw_off(a.s, nL) + k] = (float)t0;
     if (k == 0) out[idr_raw_off(a.s, nL) + H] = (float)t1;
-  }
-}
-
-// out[i] = (accumulate ? out[i] : 0) + the partials in chunk order: one float64 chain, one f32 rounding per workspace chunk
-__global__ void k_idrgrad_reduce(const float* __restrict__ part, int64_t part_stride, int n_part, int64_t count, int accumulate,
-                                 float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
-    double s = accumulate ? (double)out[i] : 0.0;
-    for (int c = 0; c < n_part; ++c) s += (double)part[(int64_t)c * part_stride + i];
-    out[i] = (float)s;
   }
 }
 
@@ -542,21 +442,21 @@ extern "C" int iso_idrgrad_backward(const float* pts, const float* g_sdf, const 
     ISO_REQUIRE(rc == 0, ISO_ERR_UNSUPPORTED, "iso_idrgrad_backward: no kernel for hidden size %d", H);
     if (!grad_raw_out) continue;                 // weight gradients not wanted: no partials, no reduce
     for (int l = 0; l < nL; ++l) {
-      IgTnArgs t;
+      // zbar_l | ztbar_l against in_l | int_l: the 64-wide encoding stash for layer 0, and the true size of the layer's
+      // matrix -- the narrow layer's padded rows and the encoding's padded columns are not written
+      GradTnArgs t;
       t.A = a.sst + (int64_t)l * ws.lstride; t.ldA = H;
       t.B = l == 0 ? a.est : a.ast + (int64_t)(l - 1) * ws.lstride; t.ldB = l == 0 ? kD0Pad : H;
       t.rows = R * m; t.rows_per_chunk = (int64_t)R * kIgPart;
       t.part = part + idr_raw_off(s, l); t.part_stride = ws.raw;
       t.out_rows = idr_out_dim(s, l); t.out_cols = idr_in_dim(s, l);
-      const int tiles = (t.ldA / 64) * (t.ldB / 64);
-      hipLaunchKernelGGL(k_idrgrad_tn, dim3((tiles + 3) / 4, n_part), dim3(256), 0, st, t);
+      grad_tn_launch(t, n_part, st);
     }
     IgColArgs c;
     c.ast = a.ast; c.sst = a.sst; c.hd = a.hd; c.lstride = ws.lstride; c.R = R; c.m = m; c.s = s;
     c.part = part; c.part_stride = ws.raw;
     hipLaunchKernelGGL(k_idrgrad_cols, dim3(n_part, H / 64, nL + 1), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_idrgrad_reduce, dim3(iso_stream_grid(ws.raw, 256)), dim3(256), 0, st, (const float*)part, ws.raw,
-                       n_part, ws.raw, chunk > 0 ? 1 : 0, grad_raw_out);
+    grad_reduce_launch(part, ws.raw, n_part, ws.raw, chunk > 0, grad_raw_out, st);
   }
   ISO_CHECK_LAUNCH("iso_idrgrad_backward");
   return ISO_OK;

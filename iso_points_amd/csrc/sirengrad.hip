@@ -17,13 +17,15 @@
 //                                                                                                k_sirengrad_sweep<NT, TAN>
 //             TAN = false (v absent): 16 value columns per wave, no tangent, zbar_l = hbar_l s_l
 //   weights   dW_l = [zbar_l; ztbar_l]^T [h_(l-1); ht_(l-1)] on the f32 matrix instruction over FIXED chunks of kSgPart
-//             points (the pattern of k_texgrad_tn, restated: texgrad.hip stays as its tests pin it)        k_sirengrad_tn
+//             points, two accumulation chains (its own kernel for square H x H layers: DESIGN.md 3.1e)    k_sirengrad_tn
 //             db_l, dW_0, dw_L, db_L: column sums in float64 by the same chunks                          k_sirengrad_cols
-//   reduce    the partials added in chunk order, on top of the earlier workspace chunks                k_sirengrad_reduce
+//   reduce    the partials added in chunk order, on top of the earlier workspace chunks  k_grad_reduce (grad_sums.hip)
 // No float atomic anywhere; a point's dx does not depend on its tile neighbours; the points are taken kSgWs at a time.
+#include "grad_sums.h"
 #include "siren_common.h"
 #include "mlp_common.h"
 #include "mfma_split.h"
+#include "sdf_grad_tile.h"
 
 namespace {
 
@@ -188,9 +190,7 @@ __global__ __launch_bounds__(256, 2) void k_sirengrad_sweep(SgArgs a) {
       }
       if (l == 0) break;
       const float* base = a.packed + off_hidden(H, l - 1);
-      gemm_pass<NT, false>(base + H + (int64_t)H * H, nullptr, hL, wbuf, acc, lane, g);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) hL4[t * 64 + lane] = acc[t];
+      sdf_grad_reverse_gemm<NT>(base + H + (int64_t)H * H, hL, wbuf, acc, lane, g);
     }
     // ---- dx = W_0^T zbar_0 (the tangent lanes' sums are not used)
     if (a.dx) {
@@ -205,10 +205,7 @@ __global__ __launch_bounds__(256, 2) void k_sirengrad_sweep(SgArgs a) {
           gz += (double)w.z * (double)a4[i];
         }
       }
-      gx += __shfl_xor(gx, 16); gx += __shfl_xor(gx, 32);
-      gy += __shfl_xor(gy, 16); gy += __shfl_xor(gy, 32);
-      gz += __shfl_xor(gz, 16); gz += __shfl_xor(gz, 32);
-      if (valid && !tan && g == 0) { a.dx[p * 3] = (float)gx; a.dx[p * 3 + 1] = (float)gy; a.dx[p * 3 + 2] = (float)gz; }
+      sdf_grad_store_dx<false>(gx, gy, gz, a.dx, p, valid && !tan && g == 0);
     }
     __syncthreads();
   }
@@ -233,7 +230,9 @@ int dispatch_sweep(const SgArgs& a, int H, hipStream_t st) {
 
 // ---- dW partial of one hidden layer: part[c][o][i] = sum over the stash rows of chunk c of A[r][o] B[r][i] ----------------
 // One wave per 64 x 64 tile of dW, both operands read row-major straight from the stashes, two rows per matrix instruction in
-// ascending order (k_texgrad_tn's form, with two chains).  A chunk is `rows_per_chunk` stash rows: kSgPart points, value and tangent row.
+// ascending order (k_texgrad_tn's form, with two chains).  A chunk is `rows_per_chunk` stash rows: kSgPart points, value and
+// tangent row.  k_grad_tn of grad_sums.hip is this kernel with a row length per operand and the true size of the matrix as
+// arguments; it measured slower here, so the duplicate stays for now.
 struct SgTnArgs {
   const float* A;                    // zbar_l | ztbar_l rows (rows, H)
   const float* B;                    // h_(l-1) | ht_(l-1) rows (rows, H)
@@ -326,14 +325,10 @@ struct SgColArgs {
 
 __global__ __launch_bounds__(256) void k_sirengrad_cols(SgColArgs a) {
   __shared__ double sq[4][4][64];
-  constexpr int Q = kSgPart / 4;
   const int H = a.H, z = blockIdx.z, kq = threadIdx.x & 63, q = threadIdx.x >> 6, k = blockIdx.y * 64 + kq;
   const int R = a.v ? 2 : 1;
-  const int64_t c0 = (int64_t)blockIdx.x * kSgPart;
-  const int64_t cend = c0 + kSgPart < a.m ? c0 + kSgPart : a.m;
-  int64_t p0 = c0 + (int64_t)q * Q;
-  int64_t pend = p0 + Q < cend ? p0 + Q : cend;
-  if (p0 > pend) p0 = pend;
+  int64_t p0, pend;
+  grad_quarter_range(blockIdx.x, q, kSgPart, a.m, p0, pend);
   double s[4] = {0.0, 0.0, 0.0, 0.0};
   if (z <= a.L) {
     const float* __restrict__ zb = a.sst + (int64_t)z * a.lstride + k;
@@ -378,16 +373,6 @@ __global__ __launch_bounds__(256) void k_sirengrad_cols(SgColArgs a) {
   } else {
     out[sg_raw_head(H, a.L) + k] = (float)t[0];
     if (k == 0) out[sg_raw_head(H, a.L) + H] = (float)t[3];
-  }
-}
-
-// out[i] = (accumulate ? out[i] : 0) + the partials in chunk order: one float64 chain, one f32 rounding per workspace chunk
-__global__ void k_sirengrad_reduce(const float* __restrict__ part, int64_t part_stride, int n_part, int64_t count, int accumulate,
-                                   float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
-    double s = accumulate ? (double)out[i] : 0.0;
-    for (int c = 0; c < n_part; ++c) s += (double)part[(int64_t)c * part_stride + i];
-    out[i] = (float)s;
   }
 }
 
@@ -481,8 +466,7 @@ extern "C" int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, c
     c.ast = a.ast; c.sst = a.sst; c.lstride = ws.lstride; c.pts = a.pts; c.u = a.u; c.v = a.v; c.m = m; c.H = H; c.L = L;
     c.part = part; c.part_stride = ws.raw;
     hipLaunchKernelGGL(k_sirengrad_cols, dim3(n_part, H / 64, L + 2), dim3(256), 0, st, c);
-    hipLaunchKernelGGL(k_sirengrad_reduce, dim3(iso_stream_grid(ws.raw, 256)), dim3(256), 0, st, (const float*)part, ws.raw,
-                       n_part, ws.raw, chunk > 0 ? 1 : 0, grad_raw_out);
+    grad_reduce_launch(part, ws.raw, n_part, ws.raw, chunk > 0, grad_raw_out, st);
   }
   ISO_CHECK_LAUNCH("iso_sirengrad_backward");
   return ISO_OK;

@@ -10,10 +10,11 @@
 //             dropped                                                                                 k_texgrad_dx
 //   weights   dW_l = a_l^T h_{l-1} on the f32 matrix instruction over FIXED chunks of kTgPart points   k_texgrad_tn
 //             db_l, dW_head, db_head by the same chunks                         k_texgrad_bias / k_texgrad_head_partial
-//   reduce    the partials added in chunk order, on top of the earlier workspace chunks               k_texgrad_reduce
+//   reduce    the partials added in chunk order, on top of the earlier workspace chunks k_grad_reduce (grad_sums.hip)
 // The ReLU mask is torch's (h > 0 <=> z > 0).  A point's rows do not depend on its tile neighbours or on the workgroup that
 // drew its tile, no float atomic is used anywhere, and the points are taken kTgWs at a time so that the stashes stay bounded.
 // The head adjoint runs between the two tile kernels as a launch of its own.
+#include "grad_sums.h"
 #include "idr_common.h"
 #include "mfma_split.h"
 #include "texture_common.h"
@@ -230,7 +231,8 @@ __global__ __launch_bounds__(256) void k_texgrad_head(TgHeadArgs a) {
 
 // ---- dW partial of one layer: part[c][o][i] = sum over the points of chunk c of A[p][o] B[p][i] ---------------------------
 // One wave per 64 x 64 tile of dW, both operands read row-major straight from the stashes (32 consecutive floats per
-// half wave), two points per matrix instruction in ascending order.
+// half wave), two points per matrix instruction in ascending order, on ONE accumulation chain (k_grad_tn of grad_sums.hip
+// runs two and takes the chunk length as an argument; it measured slower here: DESIGN.md 3.1e).
 struct TgTnArgs {
   const float* A; int lda;           // a_l (m, H)
   const float* B; int ldb;           // h_{l-1} (m, H) or x_0 (m, K0)
@@ -303,23 +305,14 @@ __global__ __launch_bounds__(256) void k_texgrad_tn(TgTnArgs a) {
 // Column sums of one partial chunk (db_l, dW_head, db_head).  A bias gradient is a sum of terms of both signs, so its
 // largest entry is of the order of sqrt(points) terms and f32 chains of a few hundred adds showed in it (measured: 4.0e-7 of
 // the largest entry at 1500 points, torch's pairwise sum 0.7e-7): the terms are added in float64 and rounded to f32 once.
-// A workgroup is 64 columns x 4 quarters of the chunk's points; the quarters are added in order through LDS.
-constexpr int kTgQuarter = kTgPart / 4;
-
+// A workgroup is 64 columns x 4 quarters of the chunk's points (grad_quarter_range); the quarters are added in order through
+// LDS.  A quarter's sum runs two float64 chains.
 __device__ __forceinline__ double tg_quarter_sum(const float* __restrict__ v, int64_t ld, int64_t p0, int64_t pend) {
   double s0 = 0.0, s1 = 0.0;
   int64_t p = p0;
   for (; p + 2 <= pend; p += 2) { s0 += (double)v[p * ld]; s1 += (double)v[(p + 1) * ld]; }
   if (p < pend) s0 += (double)v[p * ld];
   return s0 + s1;
-}
-
-// the quarter's range of chunk `c` of m points
-__device__ __forceinline__ void tg_quarter_range(int c, int q, int64_t m, int64_t& p0, int64_t& pend) {
-  const int64_t cend = (int64_t)(c + 1) * kTgPart < m ? (int64_t)(c + 1) * kTgPart : m;
-  p0 = (int64_t)c * kTgPart + (int64_t)q * kTgQuarter;
-  pend = p0 + kTgQuarter < cend ? p0 + kTgQuarter : cend;
-  if (p0 > pend) p0 = pend;
 }
 
 // db_l partial: grid (chunks, H / 64, n_layers)
@@ -335,7 +328,7 @@ __global__ __launch_bounds__(256) void k_texgrad_bias(TgBiasArgs a) {
   __shared__ double sq[4][64];
   const int H = a.s.H, l = blockIdx.z, kq = threadIdx.x & 63, q = threadIdx.x >> 6, k = blockIdx.y * 64 + kq;
   int64_t p0, pend;
-  tg_quarter_range(blockIdx.x, q, a.m, p0, pend);
+  grad_quarter_range(blockIdx.x, q, kTgPart, a.m, p0, pend);
   sq[q][kq] = tg_quarter_sum(a.ast + (int64_t)l * a.layer_stride + k, H, p0, pend);
   __syncthreads();
   if (q == 0)
@@ -356,7 +349,7 @@ __global__ __launch_bounds__(256) void k_texgrad_head_partial(TgHeadPartArgs a) 
   __shared__ double sb[4][4];
   const int H = a.s.H, kq = threadIdx.x & 63, q = threadIdx.x >> 6, k = blockIdx.y * 64 + kq;
   int64_t p0, pend;
-  tg_quarter_range(blockIdx.x, q, a.m, p0, pend);
+  grad_quarter_range(blockIdx.x, q, kTgPart, a.m, p0, pend);
   // exact products added in float64
   double s[3] = {0.0, 0.0, 0.0};
   for (int64_t p = p0; p < pend; ++p) {
@@ -374,16 +367,6 @@ __global__ __launch_bounds__(256) void k_texgrad_head_partial(TgHeadPartArgs a) 
     for (int c = 0; c < 3; ++c)
       out[(int64_t)c * H + k] = (float)((sq[0][c][kq] + sq[1][c][kq]) + (sq[2][c][kq] + sq[3][c][kq]));
     if (blockIdx.y == 0 && kq < 3) out[3 * (int64_t)H + kq] = (float)((sb[0][kq] + sb[1][kq]) + (sb[2][kq] + sb[3][kq]));
-  }
-}
-
-// out[i] = (accumulate ? out[i] : 0) + the partials in chunk order
-__global__ void k_texgrad_reduce(const float* __restrict__ part, int64_t part_stride, int n_part, int64_t count, int accumulate,
-                                 float* __restrict__ out) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
-    double s = accumulate ? (double)out[i] : 0.0;               // up to 32 partials: one f32 rounding per workspace chunk
-    for (int c = 0; c < n_part; ++c) s += (double)part[(int64_t)c * part_stride + i];
-    out[i] = (float)s;
   }
 }
 
@@ -676,8 +659,7 @@ extern "C" int iso_texgrad_backward(const float* points, const float* normals, c
     TgHeadPartArgs hp;
     hp.h_top = hst(nL - 1); hp.dy = dy; hp.m = m; hp.part = part; hp.part_stride = ws.raw; hp.s = s;
     hipLaunchKernelGGL(k_texgrad_head_partial, dim3(n_part, H / 64), dim3(256), 0, st, hp);
-    hipLaunchKernelGGL(k_texgrad_reduce, dim3(iso_stream_grid(ws.raw, 256)), dim3(256), 0, st, (const float*)part, ws.raw, n_part,
-                       ws.raw, chunk > 0 ? 1 : 0, grad_raw_out);
+    grad_reduce_launch(part, ws.raw, n_part, ws.raw, chunk > 0, grad_raw_out, st);
   }
   ISO_CHECK_LAUNCH("iso_texgrad_backward");
   return ISO_OK;
