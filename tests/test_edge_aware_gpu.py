@@ -86,7 +86,8 @@ def test_ear_candidates_kernel(dev, sens):
     _lib.call("iso_ear_candidates", *[_lib.ptr(t) for t in a], P, K, float(sens), _lib.ptr(sp), _lib.ptr(cand),
               _lib.stream())
     assert rel_err(sp, sp_ref) < 2e-6
-    assert ((cand.cpu() - cand_ref).abs().amax(-1) > 1e-6).float().mean() < 2e-3     # near-equal maxima
+    # near-equal maxima (test_densify_gpu.py::test_ear_candidates holds every row to a float64 fence and needs no quota)
+    assert ((cand.cpu() - cand_ref).abs().amax(-1) > 1e-6).float().mean() < 2e-3
 
 
 def test_edge_aware_driver_golden(dev):
