@@ -379,6 +379,39 @@ int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, const float*
                               float* grad_raw_out, float* grad_pts_out, void* workspace, int64_t workspace_bytes, void* stream,
                               const float* b0_tail);
 
+/* The same backward with ONE LATENT CODE PER CLOUD: the auto-decoder training step of the reference's default decoder,
+ * Siren(c_dim = 256) (config.py:163-166), whose multi-shape callers gather one code per packed point
+ * (implicit_modeling.py:190-218: get_normals_from_grad on packed points with the codes taken by packed_to_cloud_idx).
+ * Only layer 0's bias depends on the code: z_0(p) = W0x x_p + t_u(p), t_u = b_0 + W0c c_u one row of a table per code
+ * (iso_siren_fold_codes).  The new output is the table's gradient dt_u = sum over the points of row u of zbar_0(p); the
+ * caller's chain over the fold gives d c_u = W0c^T dt_u, d W0c = sum_u dt_u c_u^T and d b_0 = sum_u dt_u.
+ * The points of a row are CONTIGUOUS: point p belongs to row u iff code_first[u] <= p < code_first[u + 1].  dt_u is
+ * summed in float64 over the same fixed 256-point pieces (and their quarters) as every other sum here, a partial per piece
+ * and row rounded to f32 once, the partials of a row added in piece order in one float64 chain per workspace chunk on top
+ * of the earlier chunks (k_sirencode_rows, k_sirencode_join): no float atomic, the same bits on every call, a long row is
+ * spread over the grid.  A row without points gets zeros.
+ *
+ * iso_sirencode_workspace_bytes (host only): iso_sirengrad_workspace_bytes(n, hidden, n_hidden) + 4 * 2 * hidden *
+ *   ceil(mw / 256), mw = min(max(n, 1), 16384) -- two partial rows per piece, placed after the uncoded layout; it does not
+ *   grow with n_codes.  0 for a shape that is refused and for n_codes < 1.
+ * iso_sirencode_backward: pts, g_sdf, g_grad or NULL, n, hidden, n_hidden and the omegas as iso_sirengrad_backward; packed
+ *   the image of the network whose W_0 is W0x (its b_0 is not read).  code_bias (n_codes, hidden) f32, the table, in natural
+ *   feature order; code_tail the same shape or NULL: the bits each row lost when it was rounded to f32, added in float64
+ *   inside z_0 (iso_sirengrad_backward_b0's tail, per row); code_of (n) int32 the row of every point, clamped into
+ *   [0, n_codes) before it is used; code_first (n_codes + 1) int64 ON THE DEVICE, every value read clamped into [0, n]; the
+ *   two must describe the same rows.  grad_raw_out (layout of iso_siren_raw_floats; its W_0 is d W0x and its b_0 the sum
+ *   over ALL points) or NULL, grad_code_bias_out (n_codes, hidden) or NULL, grad_pts_out (n,3) or NULL: NULL outputs select
+ *   the work; outputs are written, not accumulated; padded features get zeros.  With n_codes = 1 every output has the
+ *   bits of iso_sirengrad_backward_b0 run with row 0 as b_0 and tail.  Refusals as iso_sirengrad_backward, nothing launched:
+ *   shape ISO_ERR_UNSUPPORTED; n < 0, n_codes < 1, a NULL pts / g_sdf / packed / workspace / code_bias / code_of /
+ *   code_first, a workspace, packed, code_bias or code_tail that is not 16-byte aligned ISO_ERR_INVALID; a workspace below
+ *   iso_sirencode_workspace_bytes ISO_ERR_WORKSPACE.  n == 0 writes zeros to the outputs asked for except grad_pts_out.  */
+int64_t iso_sirencode_workspace_bytes(int64_t n, int hidden, int n_hidden, int64_t n_codes);
+int iso_sirencode_backward(const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* packed, int hidden,
+                           int n_hidden, float omega_first, float omega_hidden, const float* code_bias, const float* code_tail,
+                           const int32_t* code_of, const int64_t* code_first, int64_t n_codes, float* grad_raw_out,
+                           float* grad_code_bias_out, float* grad_pts_out, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Backward of the IDR SDF AND of its gradient (csrc/idrgrad.hip): given u = dL/d sdf (n) and v = dL/d grad (n,3) of one
  * iso_idr_sdf_grad evaluation, the gradient of every EFFECTIVE weight and bias and of the points.  As iso_sirengrad_backward:
  * with u, v held constant this is the derivative of u f + v . grad f, one tangent column per point:

@@ -78,6 +78,8 @@ SIGNATURES = {
     "iso_sirengrad_workspace_bytes": (_L, [_L, _I, _I]),
     "iso_sirengrad_backward": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _F, _P, _P, _P, _L, _P]),
     "iso_sirengrad_backward_b0": (_I, [_P, _P, _P, _L, _P, _P, _I, _I, _F, _F, _P, _P, _P, _L, _P, _P]),
+    "iso_sirencode_workspace_bytes": (_L, [_L, _I, _I, _L]),
+    "iso_sirencode_backward": (_I, [_P, _P, _P, _L, _P, _I, _I, _F, _F, _P, _P, _P, _P, _L, _P, _P, _P, _P, _L, _P]),
     "iso_idrgrad_form": (_I, [_I, _I, _I, _I]),
     "iso_idrgrad_workspace_points": (_L, []),
     "iso_idrgrad_chunk_points": (_L, []),

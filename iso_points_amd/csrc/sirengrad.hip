@@ -20,6 +20,8 @@
 //             points, two accumulation chains (its own kernel for square H x H layers: DESIGN.md 3.1e)    k_sirengrad_tn
 //             db_l, dW_0, dw_L, db_L: column sums in float64 by the same chunks                          k_sirengrad_cols
 //   reduce    the partials added in chunk order, on top of the earlier workspace chunks  k_grad_reduce (grad_sums.hip)
+//   codes     one latent code per cloud: z_0 = W0x x + t_u(p), t_u a row of a table (the sweep's layer 0 takes it per point);
+//             dt_u = sum of zbar_0 over the row's points by the same chunks          k_sirencode_rows, k_sirencode_join
 // No float atomic anywhere; a point's dx does not depend on its tile neighbours; the points are taken kSgWs at a time.
 #include "grad_sums.h"
 #include "siren_common.h"
@@ -50,6 +52,10 @@ struct SgArgs {
   const float* packed;               // iso_siren_pack_weights
   const float* zeros;                // kSgZeros floats of 0
   const float* b0_tail;              // (H) or null: layer 0's bias is packed's b_0 + b0_tail, added in float64
+  const float* code_bias;            // (n_codes, H) or null: layer 0's bias of point p is row code_of[p] of this table (natural
+  const float* code_tail;            //   feature order) + the same row of code_tail (or null), in place of packed's b_0 + b0_tail
+  const int32_t* code_of;            // (m) table row of every point, clamped into [0, n_codes) before it addresses anything
+  int64_t n_codes;
   float* ast;                        // sine layer l at ast + l * lstride: rows (R m, H), h_l (and ht_l: row 2p + 1)
   float* sst;                        // the same shape: s_l (and zt_l) after the forward sweep, zbar_l (and ztbar_l) after the reverse
   int64_t lstride;
@@ -92,8 +98,22 @@ __global__ __launch_bounds__(256, 2) void k_sirengrad_sweep(SgArgs a) {
     {
       float* __restrict__ A0 = a.ast;
       float* __restrict__ S0 = a.sst;
+      // one latent code per cloud (iso_sirencode_backward): the bias is the point's row of a table, a choice made at run
+      // time (the same for every lane of a point), so that the instances stay <NT, TAN>
+      const bool coded = a.code_bias != nullptr;
+      int64_t crow = 4 * g;
+      if (coded && valid) {
+        int64_t cu = a.code_of[p];
+        cu = cu < 0 ? 0 : (cu >= a.n_codes ? a.n_codes - 1 : cu);
+        crow += cu * H;
+      }
       for (int e4 = 0; e4 < NT; ++e4) {
         f32x4 oa, os;
+        f32x4 cb = {0.f, 0.f, 0.f, 0.f}, ct = {0.f, 0.f, 0.f, 0.f};
+        if (coded) {
+          cb = *reinterpret_cast<const f32x4*>(a.code_bias + crow + 16 * e4);
+          if (a.code_tail) ct = *reinterpret_cast<const f32x4*>(a.code_tail + crow + 16 * e4);
+        }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const f32x4 w = W0img[g * (H / 4) + e4 * 4 + i];
@@ -101,7 +121,8 @@ __global__ __launch_bounds__(256, 2) void k_sirengrad_sweep(SgArgs a) {
           // carries on (gain ~1 per layer) and which was the largest single term of the error against float64.  So z_0
           // and the argument are formed in float64 (exact products), cut into an f32 head and tail, and the tail enters
           // through sin(a + t) = sin a + t cos a, cos(a + t) = cos a - t sin a.
-          const double b0 = a.b0_tail ? (double)w.w + (double)a.b0_tail[16 * e4 + 4 * g + i] : (double)w.w;
+          const double b0 = coded ? (double)cb[i] + (double)ct[i]
+                                  : (a.b0_tail ? (double)w.w + (double)a.b0_tail[16 * e4 + 4 * g + i] : (double)w.w);
           const double zd = ((double)w.x * (double)px + (double)w.y * (double)py) + ((double)w.z * (double)pz + b0);
           const double ad = (double)a.w0 * zd;
           const float ah = (float)ad, al = (float)(ad - (double)ah);
@@ -376,6 +397,128 @@ __global__ __launch_bounds__(256) void k_sirengrad_cols(SgColArgs a) {
   }
 }
 
+// ---- dt_u = sum of zbar_0 over the points of code u: the gradient of the table of layer-0 biases (iso_sirencode_backward) ----
+// The rows are contiguous: point p of the call belongs to code u iff code_first[u] <= p < code_first[u + 1].  A row is cut at
+// the SAME fixed kSgPart-point pieces (and their quarters) as every other sum here, so a long row is spread over the grid
+// and its bits depend on the indices alone.  k_sirencode_rows, one workgroup per piece and 64 columns: every thread walks
+// its quarter in order, a float64 sum per row it meets; the quarters' first and last sums are joined in order through LDS.
+// A row that lies wholly inside the piece without holding its first or its last point is complete and is written to dt; the
+// row of the piece's first point and the row of its last go to edge[piece][0 / 1], rounded to f32 once.  k_sirencode_join,
+// one thread per entry of dt: the edge partials of the row's pieces in piece order, one float64 chain on top of the earlier
+// workspace chunks, as k_grad_reduce; a row with no point in the call gets zeros.  No atomic.
+struct ScArgs {
+  const float* zb;                   // the value rows of stash layer 0 after the reverse sweep: point p at zb + R p H
+  int R, H;
+  int64_t m, r0, n;                  // points of this workspace chunk, its first point in the call, points of the call
+  const int64_t* code_first;         // (n_codes + 1), every value read is clamped into [0, n]
+  int64_t n_codes;
+  float* edge;                       // (pieces, 2, H)
+  float* dt;                         // (n_codes, H)
+  int first_chunk;
+};
+
+__device__ __forceinline__ int64_t sc_first(const ScArgs& a, int64_t u) {
+  const int64_t f = a.code_first[u];
+  return f < 0 ? 0 : (f > a.n ? a.n : f);
+}
+
+// the last row in [0, n_codes) that starts at or before point P of the call (rows without points are passed over)
+__device__ __forceinline__ int64_t sc_row_of(const ScArgs& a, int64_t P) {
+  int64_t lo = 0, hi = a.n_codes - 1;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi + 1) >> 1;
+    if (sc_first(a, mid) <= P) lo = mid; else hi = mid - 1;
+  }
+  return lo;
+}
+
+// where row u ends, as a point of this workspace chunk; the last row takes whatever is left
+__device__ __forceinline__ int64_t sc_end(const ScArgs& a, int64_t u) {
+  return u + 1 < a.n_codes ? sc_first(a, u + 1) - a.r0 : INT64_MAX;
+}
+
+__global__ __launch_bounds__(256) void k_sirencode_rows(ScArgs a) {
+  __shared__ double sq[4][2][64];
+  __shared__ int64_t su[4][2];
+  const int H = a.H, kq = threadIdx.x & 63, q = threadIdx.x >> 6, k = blockIdx.y * 64 + kq;
+  int64_t p0, pend;
+  grad_quarter_range(blockIdx.x, q, kSgPart, a.m, p0, pend);
+  int64_t u_head = -1, u_tail = -1;
+  double s_head = 0.0, s_tail = 0.0;
+  if (p0 < pend) {
+    const float* __restrict__ zb = a.zb + k;
+    int64_t u = sc_row_of(a, a.r0 + p0), next = sc_end(a, u);
+    u_head = u;
+    bool head = true;
+    double s = 0.0;
+    for (int64_t p = p0; p < pend; ++p) {
+      if (p >= next) {                         // the same for every thread of the wave: a quarter is a wave's
+        if (head) { s_head = s; head = false; }
+        else a.dt[u * H + k] = (float)s;       // begun and ended inside this quarter: the whole row
+        s = 0.0;
+        do { ++u; next = sc_end(a, u); } while (p >= next);
+      }
+      s += (double)zb[a.R * p * H];
+    }
+    if (head) s_head = s;
+    else { u_tail = u; s_tail = s; }
+  }
+  sq[q][0][kq] = s_head; sq[q][1][kq] = s_tail;
+  if (kq == 0) { su[q][0] = u_head; su[q][1] = u_tail; }
+  __syncthreads();
+  if (q != 0) return;
+  const int64_t first = su[0][0];
+  int64_t last = first;
+#pragma unroll
+  for (int i = 0; i < 8; ++i)
+    if (su[i >> 1][i & 1] >= 0) last = su[i >> 1][i & 1];
+  float* __restrict__ edge = a.edge + (int64_t)blockIdx.x * 2 * H + k;
+  if (first == last) {                         // one row holds the whole piece: k_sirengrad_cols' sum of the quarters
+    edge[0] = (float)((sq[0][0][kq] + sq[1][0][kq]) + (sq[2][0][kq] + sq[3][0][kq]));
+    edge[H] = 0.f;
+    return;
+  }
+  int64_t cur = first;
+  double t = sq[0][0][kq];
+  auto close = [&](int64_t row, double sum) {
+    if (row == first) edge[0] = (float)sum;
+    else if (row == last) edge[H] = (float)sum;
+    else a.dt[row * H + k] = (float)sum;       // inside the piece, over a quarter's edge: the whole row
+  };
+#pragma unroll
+  for (int i = 1; i < 8; ++i) {
+    const int64_t row = su[i >> 1][i & 1];
+    if (row < 0) continue;
+    if (row == cur) { t += sq[i >> 1][i & 1][kq]; continue; }
+    close(cur, t);
+    cur = row; t = sq[i >> 1][i & 1][kq];
+  }
+  close(cur, t);
+}
+
+__global__ __launch_bounds__(256) void k_sirencode_join(ScArgs a) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.n_codes * a.H) return;
+  const int64_t u = i / a.H;
+  const int k = (int)(i % a.H);
+  int64_t ls = sc_first(a, u) - a.r0, le = sc_first(a, u + 1) - a.r0;
+  ls = ls < 0 ? 0 : ls;
+  le = le > a.m ? a.m : le;
+  if (ls >= le) {                              // no point of the row in this workspace chunk
+    if (a.first_chunk) a.dt[i] = 0.f;
+    return;
+  }
+  const int64_t c_lo = ls / kSgPart, c_hi = (le - 1) / kSgPart;
+  double s = a.first_chunk ? 0.0 : (double)a.dt[i];
+  for (int64_t c = c_lo; c <= c_hi; ++c) {
+    const int64_t c0 = c * kSgPart, cend = c0 + kSgPart < a.m ? c0 + kSgPart : a.m;
+    if (ls <= c0) s += (double)a.edge[(c * 2 + 0) * a.H + k];
+    else if (le >= cend) s += (double)a.edge[(c * 2 + 1) * a.H + k];
+    else return;                               // wholly inside the piece: k_sirencode_rows wrote the row
+  }
+  a.dt[i] = (float)s;
+}
+
 // workspace (floats) for chunks of mw = min(max(n, 1), kSgWs) points: zeros kSgZeros | h stash (L + 1) * 2 mw * H |
 //   s stash, the same | partials ceil(mw / kSgPart) * raw_floats.  Sized for the tangent form; the first-order form uses the
 //   first half of every stash layer.
@@ -397,6 +540,9 @@ SgWs sg_workspace(int64_t n, int H, int L) {
   return w;
 }
 
+// the per-code sum's edge partials, placed after the uncoded layout: two rows of H floats per piece of a workspace chunk
+int64_t sc_edge_floats(const SgWs& w, int H) { return w.n_part * 2 * (int64_t)H; }
+
 }  // namespace
 
 // 800 + (padded hidden) / 16 for a network the backward runs -- hidden 1 .. 256 (a width other than 64 / 128 / 256 is
@@ -415,29 +561,39 @@ extern "C" int64_t iso_sirengrad_workspace_bytes(int64_t n, int hidden, int n_hi
   return 4 * sg_workspace(n, hidden, n_hidden).end;
 }
 
-extern "C" int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* raw,
-                                         const float* packed, int hidden, int n_hidden, float omega_first, float omega_hidden,
-                                         float* grad_raw_out, float* grad_pts_out, void* workspace, int64_t workspace_bytes,
-                                         void* stream, const float* b0_tail) {
-  (void)raw;
+// one latent code per cloud: the table of layer-0 biases and the rows of the points (iso_sirencode_backward)
+struct SgCode {
+  const float* bias; const float* tail; const int32_t* of; const int64_t* first; int64_t n_codes;
+  float* grad_bias_out;
+};
+
+// the three entries: `who` names the caller in the error text, `code` null for the uncoded ones
+static int sg_backward(const char* who, const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* packed,
+                       int hidden, int n_hidden, float omega_first, float omega_hidden, float* grad_raw_out, float* grad_pts_out,
+                       void* workspace, int64_t workspace_bytes, void* stream, const float* b0_tail, const SgCode* code) {
   ISO_REQUIRE(sg_shape_ok(hidden, n_hidden), ISO_ERR_UNSUPPORTED,
-              "iso_sirengrad_backward: unsupported shape (hidden 64 / 128 / 256, 0..8 hidden layers)");
-  ISO_REQUIRE(n >= 0, ISO_ERR_INVALID, "iso_sirengrad_backward: n < 0");
+              "%s: unsupported shape (hidden 64 / 128 / 256, 0..8 hidden layers)", who);
+  ISO_REQUIRE(n >= 0, ISO_ERR_INVALID, "%s: n < 0", who);
+  ISO_REQUIRE(!code || code->n_codes >= 1, ISO_ERR_INVALID, "%s: n_codes < 1", who);
   const int H = hidden, L = n_hidden;
   hipStream_t st = (hipStream_t)stream;
   const SgWs ws = sg_workspace(n, H, L);
+  float* dt = code ? code->grad_bias_out : nullptr;
   if (n == 0) {
-    if (grad_raw_out) {
-      iso_zero_words(grad_raw_out, ws.raw, st);
-      ISO_CHECK_LAUNCH("iso_sirengrad_backward");
-    }
+    if (grad_raw_out) iso_zero_words(grad_raw_out, ws.raw, st);
+    if (dt) iso_zero_words(dt, code->n_codes * H, st);
+    if (grad_raw_out || dt) ISO_CHECK_LAUNCH(who);
     return ISO_OK;
   }
-  ISO_REQUIRE(pts && g_sdf && packed && workspace, ISO_ERR_INVALID, "iso_sirengrad_backward: null pointer");
-  ISO_REQUIRE(workspace_bytes >= 4 * ws.end, ISO_ERR_WORKSPACE, "iso_sirengrad_backward: workspace too small");
+  ISO_REQUIRE(pts && g_sdf && packed && workspace, ISO_ERR_INVALID, "%s: null pointer", who);
+  ISO_REQUIRE(!code || (code->bias && code->of && code->first), ISO_ERR_INVALID, "%s: null pointer", who);
+  ISO_REQUIRE(workspace_bytes >= 4 * (ws.end + (code ? sc_edge_floats(ws, H) : 0)), ISO_ERR_WORKSPACE, "%s: workspace too small",
+              who);
   ISO_REQUIRE(((uintptr_t)workspace & 15) == 0 && ((uintptr_t)packed & 15) == 0, ISO_ERR_INVALID,
-              "iso_sirengrad_backward: workspace and packed must be 16-byte aligned");
-  if (!grad_raw_out && !grad_pts_out) return ISO_OK;
+              "%s: workspace and packed must be 16-byte aligned", who);
+  ISO_REQUIRE(!code || (((uintptr_t)code->bias & 15) == 0 && ((uintptr_t)code->tail & 15) == 0), ISO_ERR_INVALID,
+              "%s: code_bias and code_tail must be 16-byte aligned", who);
+  if (!grad_raw_out && !grad_pts_out && !dt) return ISO_OK;
 
   float* base = (float*)workspace;
   float* part = base + ws.part;
@@ -449,10 +605,19 @@ extern "C" int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, c
     SgArgs a;
     a.pts = pts + r0 * 3; a.u = g_sdf + r0; a.v = g_grad ? g_grad + r0 * 3 : nullptr;
     a.packed = packed; a.b0_tail = b0_tail; a.zeros = base + ws.zeros; a.ast = base + ws.ast; a.sst = base + ws.sst; a.lstride = ws.lstride;
+    a.code_bias = code ? code->bias : nullptr; a.code_tail = code ? code->tail : nullptr;
+    a.code_of = code ? code->of + r0 : nullptr; a.n_codes = code ? code->n_codes : 0;
     a.dx = grad_pts_out ? grad_pts_out + r0 * 3 : nullptr;
     a.m = m; a.L = L; a.w0 = omega_first; a.wh = omega_hidden;
     const int rc = g_grad ? dispatch_sweep<true>(a, H, st) : dispatch_sweep<false>(a, H, st);
-    ISO_REQUIRE(rc == 0, ISO_ERR_UNSUPPORTED, "iso_sirengrad_backward: no kernel for hidden size %d", H);
+    ISO_REQUIRE(rc == 0, ISO_ERR_UNSUPPORTED, "%s: no kernel for hidden size %d", who, H);
+    if (dt) {                                    // the table's gradient: the per-code sums of zbar_0
+      ScArgs c;
+      c.zb = a.sst; c.R = R; c.H = H; c.m = m; c.r0 = r0; c.n = n; c.code_first = code->first; c.n_codes = code->n_codes;
+      c.edge = base + ws.end; c.dt = dt; c.first_chunk = chunk == 0;
+      hipLaunchKernelGGL(k_sirencode_rows, dim3(n_part, H / 64), dim3(256), 0, st, c);
+      hipLaunchKernelGGL(k_sirencode_join, dim3((unsigned)((code->n_codes * H + 255) / 256)), dim3(256), 0, st, c);
+    }
     if (!grad_raw_out) continue;                 // weight gradients not wanted: no partials, no reduce
     const int tiles = (H / 64) * (H / 64);
     for (int l = 1; l <= L; ++l) {
@@ -468,8 +633,17 @@ extern "C" int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, c
     hipLaunchKernelGGL(k_sirengrad_cols, dim3(n_part, H / 64, L + 2), dim3(256), 0, st, c);
     grad_reduce_launch(part, ws.raw, n_part, ws.raw, chunk > 0, grad_raw_out, st);
   }
-  ISO_CHECK_LAUNCH("iso_sirengrad_backward");
+  ISO_CHECK_LAUNCH(who);
   return ISO_OK;
+}
+
+extern "C" int iso_sirengrad_backward_b0(const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* raw,
+                                         const float* packed, int hidden, int n_hidden, float omega_first, float omega_hidden,
+                                         float* grad_raw_out, float* grad_pts_out, void* workspace, int64_t workspace_bytes,
+                                         void* stream, const float* b0_tail) {
+  (void)raw;
+  return sg_backward("iso_sirengrad_backward", pts, g_sdf, g_grad, n, packed, hidden, n_hidden, omega_first, omega_hidden,
+                     grad_raw_out, grad_pts_out, workspace, workspace_bytes, stream, b0_tail, nullptr);
 }
 
 extern "C" int iso_sirengrad_backward(const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* raw,
@@ -478,4 +652,21 @@ extern "C" int iso_sirengrad_backward(const float* pts, const float* g_sdf, cons
                                       void* stream) {
   return iso_sirengrad_backward_b0(pts, g_sdf, g_grad, n, raw, packed, hidden, n_hidden, omega_first, omega_hidden, grad_raw_out,
                                    grad_pts_out, workspace, workspace_bytes, stream, nullptr);
+}
+
+// ---- one latent code per cloud: layer 0's bias of a point is a row of a table (header: iso_sirencode_backward) -------------
+extern "C" int64_t iso_sirencode_workspace_bytes(int64_t n, int hidden, int n_hidden, int64_t n_codes) {
+  if (!sg_shape_ok(hidden, n_hidden) || n_codes < 1) return 0;
+  const SgWs ws = sg_workspace(n, hidden, n_hidden);
+  return 4 * (ws.end + sc_edge_floats(ws, hidden));
+}
+
+extern "C" int iso_sirencode_backward(const float* pts, const float* g_sdf, const float* g_grad, int64_t n, const float* packed,
+                                      int hidden, int n_hidden, float omega_first, float omega_hidden, const float* code_bias,
+                                      const float* code_tail, const int32_t* code_of, const int64_t* code_first, int64_t n_codes,
+                                      float* grad_raw_out, float* grad_code_bias_out, float* grad_pts_out, void* workspace,
+                                      int64_t workspace_bytes, void* stream) {
+  const SgCode code = {code_bias, code_tail, code_of, code_first, n_codes, grad_code_bias_out};
+  return sg_backward("iso_sirencode_backward", pts, g_sdf, g_grad, n, packed, hidden, n_hidden, omega_first, omega_hidden,
+                     grad_raw_out, grad_pts_out, workspace, workspace_bytes, stream, nullptr, &code);
 }

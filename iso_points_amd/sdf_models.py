@@ -384,6 +384,159 @@ class _SirenFunction(torch.autograd.Function):
         return (None, None, None, g_pts) + tuple(grads)
 
 
+def cloud_order(cloud_idx, n_codes):
+    """The packed order of points given with the row of each: cloud_idx (n,) integers in any order -> (order, inverse,
+    code_of, code_first), all on cloud_idx's device and made without a host read.  The indices are clamped into
+    [0, n_codes); order (n,) int64 is the stable argsort (points of a row keep their order), inverse its inverse
+    (sorted[inverse] is the caller's order), code_of (n,) int32 the sorted rows and code_first (n_codes + 1,) int64 where
+    each row starts in the sorted order (searchsorted; a row without points has code_first[u] == code_first[u + 1])."""
+    idx = cloud_idx.reshape(-1).to(torch.int64).clamp(0, n_codes - 1)
+    order = torch.argsort(idx, stable=True)
+    code_of = idx[order]
+    code_first = torch.searchsorted(code_of, torch.arange(n_codes + 1, dtype=torch.int64, device=idx.device))
+    inverse = torch.empty_like(order)
+    inverse[order] = torch.arange(order.numel(), dtype=torch.int64, device=idx.device)
+    return order, inverse, code_of.to(torch.int32), code_first
+
+
+def _per_cloud_arguments(model, points, c, cloud_idx, lengths):
+    """Checks of siren_forward's per-cloud call, before anything is launched: (coded spec, U, n)"""
+    if cloud_idx is not None and lengths is not None:
+        raise ValueError("iso_points_amd: give cloud_idx or lengths, not both")
+    coded = coded_siren_spec(model)
+    if coded is None:
+        raise ValueError("iso_points_amd: cloud_idx / lengths are for a latent-conditioned SIREN (coded_siren_spec)")
+    C = coded[3]
+    if not torch.is_tensor(c) or c.ndim != 2 or c.shape[0] < 1 or c.shape[1] != C or not c.is_floating_point():
+        raise ValueError("iso_points_amd: with cloud_idx / lengths the codes are c (U, %d), one row per cloud" % C)
+    if not torch.is_tensor(points) or points.ndim < 1 or points.shape[-1] != 3:
+        raise ValueError("iso_points_amd: points must be (..., 3)")
+    U, n = c.shape[0], points.numel() // 3
+    if lengths is not None:
+        lengths = [int(x) for x in lengths]
+        if len(lengths) != U or any(x < 0 for x in lengths) or sum(lengths) != n:
+            raise ValueError("iso_points_amd: lengths must be %d counts >= 0 that sum to the %d points" % (U, n))
+    else:
+        if not torch.is_tensor(cloud_idx) or cloud_idx.is_floating_point() or cloud_idx.is_complex() \
+                or cloud_idx.dtype == torch.bool or cloud_idx.numel() != n or cloud_idx.device != points.device:
+            raise ValueError("iso_points_amd: cloud_idx must be %d integers on the points' device" % n)
+    return coded, U, n, lengths
+
+
+class _SirenCodeFunction(torch.autograd.Function):
+    """_SirenFunction with one latent code per cloud: the evaluation is iso_siren_sdf_grad_coded on `table` (U, H), the
+    layer-0 biases of the codes as the no-grad route folds them (PackedSiren.fold); the backward is iso_sirencode_backward
+    with `tail` (U, H), what that table lost against the float64 fold.  The gradient of the table, dt (U, model width), is
+    handed to `t`, the caller's differentiable fold, whose values are not read: torch's chain over it delivers d codes, the
+    code columns of d W_0 and d b_0.  The points are in packed order (code_of sorted, code_first the row starts); wb is
+    W0x, W_1, b_1, .., W_L, b_L."""
+
+    @staticmethod
+    def forward(ctx, shape, need_grad, table, tail, code_of, code_first, t, pts, *wb):
+        H, L, w0, wh = shape
+        dev, n = pts.device, pts.shape[0]
+        lib = _lib.load()
+        if not lib.iso_sirengrad_form(H, L):
+            raise RuntimeError("iso_points_amd: no fused SIREN backward for hidden %d, %d hidden layers" % (H, L))
+        full = (wb[0], wb[0].new_zeros((wb[0].shape[0],))) + tuple(wb[1:])        # b_0 is not read: the table holds it
+        packed = _pack_raw(_padded_raw(full, H, dev), H, L)
+        sdf = torch.empty((n,), dtype=torch.float32, device=dev)
+        grad = torch.empty((n, 3) if need_grad else (0, 3), dtype=torch.float32, device=dev)
+        ws = torch.empty((lib.iso_project_siren_workspace_bytes(n, H, L),), dtype=torch.uint8, device=dev)
+        _lib.call("iso_siren_sdf_grad_coded", _lib.ptr(pts), _lib.ptr(sdf), _lib.ptr(grad) if need_grad else None, n,
+                  _lib.ptr(packed), H, L, w0, wh, _lib.ptr(ws), ws.numel(), _lib.stream(), _lib.ptr(table), _lib.ptr(code_of),
+                  table.shape[0])
+        ctx.shape, ctx.need_grad = shape, need_grad
+        ctx.save_for_backward(table, tail, code_of, code_first, pts, *wb)
+        ctx.set_materialize_grads(False)
+        if not need_grad:
+            ctx.mark_non_differentiable(grad)
+        return sdf, grad
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_sdf, g_grad):
+        H, L, w0, wh = ctx.shape
+        table, tail, code_of, code_first, pts = ctx.saved_tensors[:5]
+        wb = ctx.saved_tensors[5:]
+        dev, n, U = pts.device, pts.shape[0], table.shape[0]
+        need = ctx.needs_input_grad                      # .. 6: t, 7: pts, 8: W0x, 9..: W_1, b_1, ..
+        if g_sdf is None and (g_grad is None or not ctx.need_grad):
+            return (None,) * len(need)
+        lib = _lib.load()
+        full = (wb[0], wb[0].new_zeros((wb[0].shape[0],))) + tuple(wb[1:])
+        raw = _padded_raw(full, H, dev)
+        packed = _pack_raw(raw, H, L)
+        u = torch.zeros((n,), dtype=torch.float32, device=dev) if g_sdf is None else \
+            g_sdf.reshape(n).to(torch.float32).contiguous()
+        v = g_grad.reshape(n, 3).to(torch.float32).contiguous() if (ctx.need_grad and g_grad is not None) else None
+        g_pts = torch.empty_like(pts) if need[7] else None
+        g_raw = torch.empty_like(raw) if any(need[8:]) else None      # NULL: no dW / db work is done
+        g_tab = torch.empty_like(table) if need[6] else None
+        ws = torch.empty((lib.iso_sirencode_workspace_bytes(n, H, L, U),), dtype=torch.uint8, device=dev)
+        _lib.call("iso_sirencode_backward", _lib.ptr(pts), _lib.ptr(u), _lib.ptr(v), n, _lib.ptr(packed), H, L, w0, wh,
+                  _lib.ptr(table), _lib.ptr(tail), _lib.ptr(code_of), _lib.ptr(code_first), U, _lib.ptr(g_raw), _lib.ptr(g_tab),
+                  _lib.ptr(g_pts), _lib.ptr(ws), ws.numel(), _lib.stream())
+        Hm = wb[0].shape[0]
+        grads, at, nl = [], 0, len(full) // 2
+        for i in range(nl):
+            w, b = full[2 * i], full[2 * i + 1]
+            rows = H if i < nl - 1 else w.shape[0]
+            cols = H if i > 0 else w.shape[1]
+            k = 8 + 2 * i - (1 if i > 0 else 0)          # b_0 is no input
+            grads.append(g_raw[at:at + rows * cols].reshape(rows, cols)[:w.shape[0], :w.shape[1]].to(w.dtype)
+                         if need[k] else None)
+            at += rows * cols
+            if i > 0:
+                grads.append(g_raw[at:at + rows][:b.shape[0]].to(b.dtype) if need[k + 1] else None)
+            at += rows
+        return (None,) * 6 + (g_tab[:, :Hm] if need[6] else None, g_pts) + tuple(grads)
+
+
+def _siren_forward_per_cloud(model, points, c, need_grad, cloud_idx, lengths):
+    coded, U, n, lengths = _per_cloud_arguments(model, points, c, cloud_idx, lengths)
+    if not points.is_cuda:
+        raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
+    lins, w0, wh, C = coded
+    dev, shp = points.device, points.shape
+    train = torch.is_grad_enabled() and (any(p.requires_grad for p in model.parameters()) or points.requires_grad
+                                         or c.requires_grad)
+    codes = c.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if not train:
+        code_of = rows_of(lengths, dev) if lengths is not None else \
+            cloud_idx.reshape(-1).to(torch.int64).clamp(0, U - 1).to(torch.int32)
+        return siren_sdf_and_grad(model, points, need_grad=need_grad, code=CodeRows(codes, code_of))
+    pts = points.reshape(-1, 3).to(torch.float32)
+    if lengths is not None:
+        inverse, code_of = None, rows_of(lengths, dev)
+        starts = [0]
+        for x in lengths:
+            starts.append(starts[-1] + x)
+        code_first = torch.tensor(starts, dtype=torch.int64).to(dev)
+    else:
+        order, inverse, code_of, code_first = cloud_order(cloud_idx, U)
+        pts = pts[order]
+    Hm = lins[0].out_features
+    H = next(h for h in (64, 128, 256) if h >= Hm)
+    W0 = lins[0].weight
+    # the fold in float64 under grad; the kernels evaluate the table of the no-grad route (iso_siren_fold_codes), so that
+    # the values are its bits, and the backward gets what THAT table lost against float64, per row (b0_tail's role)
+    t64 = lins[0].bias.double() + c.to(dev).double() @ W0[:, :C].double().t()
+    with torch.no_grad():
+        table = torch.empty((U, H), dtype=torch.float32, device=dev)
+        _lib.call("iso_siren_fold_codes", _lib.ptr(W0[:, :C].detach().float().contiguous()),
+                  _lib.ptr(lins[0].bias.detach().float().contiguous()), _lib.ptr(codes), _lib.ptr(table), Hm, H, C, U,
+                  _lib.stream())
+        tail = torch.zeros((U, H), dtype=torch.float32, device=dev)
+        tail[:, :Hm] = (t64.detach() - table[:, :Hm].double()).to(torch.float32)
+    wb = [W0[:, C:]] + [t for lin in lins[1:] for t in (lin.weight, lin.bias)]
+    sdf, grad = _SirenCodeFunction.apply((H, len(lins) - 2, float(w0), float(wh)), bool(need_grad), table, tail, code_of,
+                                         code_first, t64.to(torch.float32), pts.contiguous(), *wb)
+    if inverse is not None:
+        sdf, grad = sdf[inverse], (grad[inverse] if need_grad else grad)
+    return sdf.view(shp[:-1]), (grad.view(shp) if need_grad else None)
+
+
 _TORCH_WARNED = set()
 
 
@@ -418,7 +571,7 @@ def _torch_forward(model, points, c, need_grad, train):
     return sdf, grad
 
 
-def siren_forward(model, points, c=None, need_grad=True):
+def siren_forward(model, points, c=None, need_grad=True, *, cloud_idx=None, lengths=None):
     """sdf (...) and grad (..., 3) of `model` at points (..., 3) (grad None when need_grad is False), to TRAIN with.
 
     Under grad mode, when a parameter of the model, the points or the code require grad, the results carry a grad_fn: the
@@ -427,7 +580,19 @@ def siren_forward(model, points, c=None, need_grad=True):
     made in torch.  The outputs are those of the GEMM mode the library is in; the backward differentiates the f32-MFMA
     evaluation of the same network.  Otherwise this is siren_sdf_and_grad, bit for bit.  One code per batch row under
     grad, and any model siren_spec / coded_siren_spec refuse, take model.forward and torch autograd (one warning per model
-    class)."""
+    class).
+
+    One code per cloud on the fused kernels, under grad too (the auto-decoder step; implicit_modeling.py:211-218 with
+    `c, cloud_idx=pointclouds.packed_to_cloud_idx()` in place of the gathered codes): c (U, C) and EITHER lengths, a host
+    sequence of U counts summing to the n points, the clouds in packed order (no sort, no host read), OR cloud_idx, an
+    (n,) integer device tensor in any order (clamped into [0, U), ordered by a stable device argsort, run sorted, handed
+    back in the caller's order).  Both is a ValueError, as a shape that does not fit, before any launch.  The gradients
+    go into every parameter, the points and every code (iso_sirencode_backward: the table of folded biases is a leaf of
+    the kernels, torch's chain over the fold does the rest); sdf and grad are bit-identical to the no-grad call.
+    The call WITHOUT these keywords keeps its route on purpose: padded points (N, P, 3) with c (N, C) under grad still go
+    to model.forward with the warning above; padded callers who want the fused route pass lengths=[P] * N."""
+    if cloud_idx is not None or lengths is not None:
+        return _siren_forward_per_cloud(model, points, c, need_grad, cloud_idx, lengths)
     if not points.is_cuda:
         raise RuntimeError("iso_points_amd: points must be on the GPU; there is no CPU path")
     has_c = c is not None and torch.is_tensor(c) and c.numel() > 0
@@ -475,11 +640,13 @@ def siren_forward(model, points, c=None, need_grad=True):
     return sdf.view(shp[:-1]), (grad.view(shp) if need_grad else None)
 
 
-def get_normals_from_grad(decoder, p_world, c=None, requires_grad=False, return_sdf=False, **kwargs):
+def get_normals_from_grad(decoder, p_world, c=None, requires_grad=False, return_sdf=False, cloud_idx=None, lengths=None,
+                          **kwargs):
     """DSS/models/implicit_modeling.py:250-277 for a decoder handed in: the not normalised normals at p_world (N, *, 3), the
     gradient of the SDF w.r.t. the points; with return_sdf also the sdf (N, *, 1).  requires_grad=True: the normals (and
     the sdf) backpropagate into the decoder and the points, through sdf_forward's fused backward for a SIREN or an IDR network;
-    requires_grad=False: detached normals.  Further forward kwargs take model.forward."""
+    requires_grad=False: detached normals.  cloud_idx / lengths: one code per cloud, c (U, C), as siren_forward takes them
+    (the reference's call at :211-218 on packed points).  Further forward kwargs take model.forward."""
     if kwargs:
         _warn_torch_route(decoder, "forward kwargs")
         with torch.enable_grad():
@@ -491,7 +658,7 @@ def get_normals_from_grad(decoder, p_world, c=None, requires_grad=False, return_
     else:
         # as the reference, the sdf handed back keeps its graph whether or not the normals do
         with torch.enable_grad() if (requires_grad or return_sdf) else torch.no_grad():
-            sdf, normals = sdf_forward(decoder, p_world, c=c, need_grad=True)
+            sdf, normals = sdf_forward(decoder, p_world, c=c, need_grad=True, cloud_idx=cloud_idx, lengths=lengths)
     if not requires_grad:
         normals = normals.detach()
     if return_sdf:
@@ -687,9 +854,10 @@ def idr_forward(model, points, need_grad=True):
     return sdf.view(shp[:-1]), (grad.view(shp) if need_grad else None)
 
 
-def sdf_forward(model, points, c=None, need_grad=True):
+def sdf_forward(model, points, c=None, need_grad=True, cloud_idx=None, lengths=None):
     """siren_forward for a SIREN or a latent-conditioned SIREN, idr_forward for an IDR-style SDF (which takes no code), and
-    siren_forward's torch route with its one warning for anything else: sdf (...) and grad (..., 3) to train with."""
+    siren_forward's torch route with its one warning for anything else: sdf (...) and grad (..., 3) to train with.
+    cloud_idx / lengths go to siren_forward (one code per cloud)."""
     if siren_spec(model) is None and coded_siren_spec(model) is None:
         with torch.no_grad():
             is_idr = idr_spec(model) is not None
@@ -697,7 +865,7 @@ def sdf_forward(model, points, c=None, need_grad=True):
             if c is not None and torch.is_tensor(c) and c.numel() > 0:
                 raise ValueError("iso_points_amd: an IDR-style SDF takes no latent code")
             return idr_forward(model, points, need_grad=need_grad)
-    return siren_forward(model, points, c=c, need_grad=need_grad)
+    return siren_forward(model, points, c=c, need_grad=need_grad, cloud_idx=cloud_idx, lengths=lengths)
 
 
 class FusedSdf(object):
